@@ -338,6 +338,35 @@ def timed_steps(step, args, world):
     return t.item(), stats, last
 
 
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs: all arrays of one run together
+DUMP_SAMPLE = 4096              # elements kept of each model parameter (all of a smaller one)
+
+
+def seeded_sample(t, k, seed):
+    """k elements of `t` at positions drawn from a CPU generator seeded with `seed` (the same positions on every run and
+    build), widened to float32 on the host; all of `t` when it has no more than k elements."""
+    flat = t.detach().reshape(-1)
+    if flat.numel() <= k:
+        return flat.float().cpu()
+    idx = torch.randint(0, flat.numel(), (k,), generator=torch.Generator().manual_seed(seed))
+    return flat[idx.to(flat.device)].float().cpu()
+
+
+def write_dump(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy -- float64 for float64 / integer data (exact), float32 otherwise."""
+    import numpy as np
+    conv = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu() if isinstance(a, torch.Tensor) else torch.as_tensor(a)
+        conv[name] = a.to(torch.float64 if a.dtype in (torch.float64, torch.int64, torch.int32) else torch.float32).numpy()
+    total = sum(a.nbytes for a in conv.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes, limit {DUMP_LIMIT_BYTES}"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in conv.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log(f"[bench] --dump-outputs: {len(conv)} arrays, {total / 2 ** 20:.1f} MB -> {out_dir}")
+
+
 def latest_profile(pattern):
     """Newest profiles/rNN_<pattern> (measured off-line, see tools/collect_traffic.sh), or None."""
     import glob
@@ -345,9 +374,11 @@ def latest_profile(pattern):
     return hits[-1] if hits else None
 
 
-def run_gpt(args, dtype_name, world, rank, mp, parity=False):
+def run_gpt(args, dtype_name, world, rank, mp, parity=False, dumps=None):
     """One measurement of the GPT train step in `dtype_name`; returns the JSON object (without cpu_baseline).
-    parity: after the timed steps, check the timed model against the CPU oracle at full depth (measure_parity)."""
+    parity: after the timed steps, check the timed model against the CPU oracle at full depth (measure_parity).
+    dumps: a dict that receives what the last timed step handed back -- its loss and skip flag, and a seeded sample of every
+    parameter of the model it updated (this rank's shard when mp > 1) -- under names prefixed with the dtype."""
     from cogview_amd import mpu, training
     from cogview_amd.fp16 import FP16_Module, FP16_Optimizer
     from cogview_amd.model import GPT2Model, PyTorchDistributedDataParallel, gpt2_get_params_for_weight_decay_optimization
@@ -399,6 +430,11 @@ def run_gpt(args, dtype_name, world, rank, mp, parity=False):
     elapsed, gemm_stats, (loss, skipped) = timed_steps(step, args, world)
     final_loss = loss.item()
     assert final_loss == final_loss, "loss is NaN"
+    if dumps is not None:
+        dumps[dtype_name + "_loss"] = loss.detach().double()
+        dumps[dtype_name + "_skipped"] = torch.tensor(float(skipped), dtype=torch.float64)
+        dumps[dtype_name + "_params_sample"] = torch.cat([seeded_sample(p, DUMP_SAMPLE, i) for i, (_, p) in
+                                                           enumerate(inner.named_parameters())])
 
     tokens_per_step = dp_world * args.batch * (row - 1)
     value = tokens_per_step * args.steps / elapsed
@@ -476,10 +512,11 @@ VQ_BATCH = 256
 VQ_FLOPS_PER_IMAGE = {"encode": 48.32e9, "decode": 176.29e9}
 
 
-def run_vqvae(args, world, rank):
+def run_vqvae(args, world, rank, dumps=None):
     """BASELINE configs[4]: one step = img2code then code2img of `batch` normalised 256x256 images already resident in
     HBM (production tokenizer: 512 channels, 256-d codes, 8192 entries; fp32 end to end on the exact-fp32 MFMA).
-    Replicas only: every rank tokenizes its own batch, no collective on the data path."""
+    Replicas only: every rank tokenizes its own batch, no collective on the data path.
+    dumps: a dict that receives the last step's codes (all of them) and a seeded sample of its decoded images."""
     from cogview_amd import vqvae
     torch.manual_seed(0)
     model = vqvae.new_model().cuda().eval()
@@ -494,6 +531,9 @@ def run_vqvae(args, world, rank):
 
     elapsed, stats, (ids, out) = timed_steps(step, args, world)
     assert ids.shape == (b, 1024) and out.shape == (b, 3, 256, 256) and bool(torch.isfinite(out).all())
+    if dumps is not None:
+        dumps["vqvae_ids"] = ids
+        dumps["vqvae_images_sample"] = seeded_sample(out, 1 << 20, 0)
     value = world * b * args.steps / elapsed
     fl = VQ_FLOPS_PER_IMAGE["encode"] + VQ_FLOPS_PER_IMAGE["decode"]
     res = {"metric": "VQ-VAE encode+decode images/sec (256x256 -> 32x32 codes -> 256x256), batch 256; % fp32-MFMA roofline",
@@ -548,7 +588,13 @@ def main():
     ap.add_argument("--no-parity", action="store_true",
                     help="skip the full-depth logits check of the timed model against the CPU oracle (about one CPU "
                          "minute per dtype at 4B; part of the cpu_baseline leg, so --no-cpu-baseline skips it too)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / "
+                         "float64, at most 64 MB: loss, skip flag and a seeded sample of the updated parameters per dtype "
+                         "leg; codes and a sample of the images for vqvae), from rank 0")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.batch <= 0:
         args.batch = VQ_BATCH if args.config == "vqvae" else DEFAULT_BATCH[args.config]
 
@@ -558,10 +604,11 @@ def main():
     world, rank = setup_dist(args)
     import torch.distributed as dist
     from cogview_amd import mpu
+    dumps = {} if args.dump_outputs else None
 
     if args.config == "vqvae":
         mpu.initialize_model_parallel(1)
-        out = run_vqvae(args, world, rank)
+        out = run_vqvae(args, world, rank, dumps=dumps)
         if rank == 0 and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_vqvae()
     else:
@@ -570,9 +617,9 @@ def main():
         mpu.initialize_model_parallel(mp)
         L, h, heads = CONFIGS[args.config]
         parity = world == 1 and mp == 1 and not args.no_cpu_baseline and not args.no_parity
-        out = run_gpt(args, args.dtype or "fp16", world, rank, mp, parity=parity)
+        out = run_gpt(args, args.dtype or "fp16", world, rank, mp, parity=parity, dumps=dumps)
         if args.dtype is None and world == 1 and not args.no_second_dtype:
-            leg = run_gpt(args, "bf16", world, rank, mp, parity=parity)
+            leg = run_gpt(args, "bf16", world, rank, mp, parity=parity, dumps=dumps)
             out["bf16_leg"] = {k: leg[k] for k in ("value", "unit", "ms_per_step", "dtype", "model_tflops_per_gpu",
                                                    "mfma_roofline_frac_end_to_end", "mfma_roofline_frac_causal_discounted",
                                                    "mfma_roofline_frac_hardware_flops")}
@@ -596,6 +643,8 @@ def main():
                     "value": r["reference"]["tokens_per_s"], "unit": "tokens/s", "cores": r["threads"], "kind": "reference",
                     "sample": r["config"], "measured_where": r["where"] + ", not on this box",
                     "port_on_the_same_cores": r["port"]["tokens_per_s"], "source": os.path.relpath(rpath, ROOT)}
+    if rank == 0 and dumps is not None:
+        write_dump(args.dump_outputs, dumps)
     if rank == 0:
         print(json.dumps(out), file=json_out, flush=True)
     if world > 1:

@@ -83,3 +83,48 @@ def test_bench_model_parallel_2_on_one_device():
     assert out["n_gpus"] == 2 and out["steps"] == 2 and out["config"]["global_batch"] == 2
     assert out["config"]["parallelism"].startswith("mp2") or "mp2" in out["config"]["parallelism"], out["config"]["parallelism"]
     assert out["value"] > 0 and out["config"]["skipped_last_step"] in (0, 1)
+
+
+def test_dump_helpers_write_fixed_samples_within_the_limit(tmp_path, monkeypatch):
+    """CPU: --dump-outputs' sample is the same on every call (seeded positions), small tensors are kept whole, integer and
+    float64 data are written as float64 and everything else as float32, and the 64 MB budget is enforced."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    t = torch.randn(100000).half()
+    a, b = bench.seeded_sample(t, 512, 7), bench.seeded_sample(t, 512, 7)
+    assert a.dtype == torch.float32 and a.shape == (512,) and torch.equal(a, b)
+    assert not torch.equal(a, bench.seeded_sample(t, 512, 8))
+    assert torch.equal(bench.seeded_sample(t[:100], 512, 7), t[:100].float())
+    bench.write_dump(str(tmp_path / "d"), {"loss": torch.tensor(2.5, dtype=torch.float64), "ids": torch.arange(6).view(2, 3),
+                                           "sample": a})
+    got = {n: np.load(str(tmp_path / "d" / (n + ".npy"))) for n in ("loss", "ids", "sample")}
+    assert got["loss"].dtype == np.float64 and got["loss"] == 2.5
+    assert got["ids"].dtype == np.float64 and got["ids"].tolist() == [[0, 1, 2], [3, 4, 5]]
+    assert got["sample"].dtype == np.float32 and np.array_equal(got["sample"], a.numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 1000)
+    with pytest.raises(AssertionError, match="limit"):
+        bench.write_dump(str(tmp_path / "e"), {"big": torch.zeros(1000)})
+    assert not (tmp_path / "e").exists()
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """GPU box: `bench.py --dump-outputs DIR` on configs[0] writes the loss the JSON line reports, the skip flag and the
+    parameter sample for each dtype leg, float32 / float64, within 64 MB."""
+    import numpy as np
+    out_dir = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "cogview-tiny-18M", "--steps", "3",
+                        "--warmup", "1", "--no-cpu-baseline", "--dump-outputs", str(out_dir)],
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert out["steps"] == 3
+    files = sorted(p.name for p in out_dir.iterdir())
+    assert files == sorted(f"{d}_{n}.npy" for d in ("fp16", "bf16") for n in ("loss", "skipped", "params_sample"))
+    arrs = {f[:-4]: np.load(str(out_dir / f)) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+    assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+    assert float(arrs["fp16_loss"]) == out["config"]["loss"] and float(arrs["bf16_loss"]) == out["bf16_leg"]["loss"]
+    assert arrs["fp16_params_sample"].shape == arrs["bf16_params_sample"].shape and np.isfinite(arrs["fp16_params_sample"]).all()
