@@ -105,6 +105,19 @@ class ConvDesc(C.Structure):
     ]
 
 
+class SampleDesc(C.Structure):
+    _fields_ = [
+        ("dtype", C.c_int), ("rows", C.c_int), ("vocab", C.c_int), ("row_stride", C.c_int64),
+        ("logits", C.c_void_p),
+        ("temperature", C.c_float), ("top_k", C.c_int), ("top_p", C.c_float), ("allow_lo", C.c_int), ("allow_hi", C.c_int),
+        ("seed", C.c_uint64), ("offset", C.c_void_p),
+        ("ids", C.c_void_p), ("logp", C.c_void_p), ("scores", C.c_void_p), ("probs", C.c_void_p),
+        ("tok", C.c_void_p), ("pos", C.c_void_p), ("pos_index", C.c_void_p), ("table", C.c_void_p), ("capacity", C.c_int),
+        ("out_tokens", C.c_void_p), ("out_len", C.c_int64), ("out_base", C.c_int64),
+        ("counter", C.c_void_p),
+    ]
+
+
 CONV_4X4_S2, CONV_1X1, CONVT_4X4_S2, CONV_3X3_S1 = 0, 1, 2, 3
 
 _vp, _i, _f, _u64, _i64, _sz = C.c_void_p, C.c_int, C.c_float, C.c_uint64, C.c_int64, C.c_size_t
@@ -162,6 +175,7 @@ SIGNATURES = {
     "cogv_vq_argmin_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "cogv_nchw3_to_nhwc4_f32": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "cogv_embed_code_f32": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp]),
+    "cogv_sample_logits": (_i, [C.POINTER(SampleDesc), _vp]),
     "cogv_conv1x1_to_rgb_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), _vp]),
 }
 

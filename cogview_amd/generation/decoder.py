@@ -73,7 +73,12 @@ class GraphDecoder:
     @torch.no_grad()
     def prefill(self, tokens, position_ids, attention_mask=0):
         """Run the context through the model once (eager, K/V-cache memories) and load the caches.  Returns its logits."""
-        assert tokens.shape[0] == self.batch and tokens.shape[1] < self.cap
+        assert tokens.shape[0] == self.batch
+        return self._prefill(tokens, position_ids, attention_mask)
+
+    def _prefill(self, tokens, position_ids, attention_mask):
+        """prefill's body; tokens of ONE row fill every cache row (the keys / values broadcast over the batch)."""
+        assert tokens.shape[0] in (1, self.batch) and tokens.shape[1] < self.cap
         tr = self.gpt.transformer
         kv_flag, tr.kv_cache = tr.kv_cache, True
         max_mem, tr.max_memory_length = tr.max_memory_length, max(tr.max_memory_length, self.cap)
@@ -104,3 +109,79 @@ class GraphDecoder:
             logits = self._step()
         self.length += 1
         return logits
+
+
+class SamplingDecoder(GraphDecoder):
+    """A GraphDecoder whose step ends with the token sampler (ops.sample_logits, cogv_sample_logits): the drawn ids go
+    straight into the static token buffer, and the same launch advances the positions, the write slot, the visible slot of
+    the index table, the generator offset and the output row -- so one replay of the captured graph is one generated token
+    and a run of them needs no host work.  Reference path: generation/sampling.py:139-186 (model call, filter, multinomial,
+    beam score) once per token.  Use start() + generate() (step() feeds tokens from the host and is not for this mode)."""
+
+    def __init__(self, model, batch=1, capacity=1152):
+        super().__init__(model, batch, capacity)
+        self.sampling = None
+
+    def enable_sampling(self, temperature=1.0, top_k=0, top_p=0.0, allow=None, seed=0, out_tokens=None, out_base=0):
+        """allow: (lo, hi) range of ids that may be drawn (None: all); out_tokens: int64 [batch, n] that receives the id
+        drawn for sequence position out_base + j in column j (None: not recorded)."""
+        dev = self.tok.device
+        assert out_tokens is None or (out_tokens.dtype == torch.int64 and out_tokens.shape[0] == self.batch)
+        self.sampling = dict(temperature=float(temperature), top_k=int(top_k), top_p=float(top_p), allow=allow, seed=int(seed))
+        self.offset = torch.zeros(1, dtype=torch.int64, device=dev)        # generator offset: one per draw
+        self.ids = torch.zeros(self.batch, dtype=torch.int64, device=dev)
+        self.logp = torch.zeros(self.batch, dtype=torch.float32, device=dev)
+        self.scores = torch.zeros(self.batch, dtype=torch.float32, device=dev)
+        self.counter = torch.zeros(1, dtype=torch.int32, device=dev)       # the sampler's completion counter
+        self.out_tokens, self.out_base = out_tokens, int(out_base)
+
+    def _sample(self, logits, rows=None):
+        dec = dict(tok=self.tok.view(-1), pos=self.pos.view(-1), pos_index=self.pos_index, table=self.table,
+                   counter=self.counter, out_tokens=self.out_tokens, out_base=self.out_base)
+        ops.sample_logits(logits, **self.sampling, offset=self.offset, rows=rows, ids=self.ids, logp=self.logp,
+                          scores=self.scores, decode=dec)
+
+    def _step(self):
+        logits = super()._step()
+        if self.sampling is not None:
+            self._sample(logits)
+        return logits
+
+    @torch.no_grad()
+    def start(self, tokens, position_ids, attention_mask=0):
+        """Prefill ONE context row [1, n] into every cache row, then draw the first token of every row from its last
+        logits (batch independent draws, multinomial(..., replacement=True) in the reference).  The draw's bookkeeping
+        leaves the decoder at the next step: slot n visible, the drawn ids and positions in the static buffers."""
+        assert self.sampling is not None and tokens.shape[0] == 1
+        logits = self._prefill(tokens, position_ids, attention_mask)
+        n = tokens.shape[1]
+        self.pos_index.fill_(n - 1)
+        self.pos.copy_(position_ids[:, -1:].expand(self.batch, 1))
+        self.scores.zero_()
+        self._sample(logits[:, -1], rows=self.batch)
+        return logits
+
+    def capture(self):
+        """GraphDecoder.capture, with the state the warm-up steps advance (tokens, positions, table, generator offset,
+        scores, output row) restored afterwards."""
+        state = [t.clone() for t in self._state()]
+        super().capture()
+        for t, s in zip(self._state(), state):
+            t.copy_(s)
+
+    def _state(self):
+        st = [self.tok, self.pos, self.pos_index, self.table, self.offset, self.ids, self.logp, self.scores]
+        return st + ([self.out_tokens] if self.out_tokens is not None else [])
+
+    @torch.no_grad()
+    def generate(self, n):
+        """n decode steps back to back (graph replays when captured, else the same launches eagerly): n more tokens per
+        row.  Returns (out_tokens, scores) -- device tensors; nothing is read back on the way."""
+        assert self.sampling is not None and self.length + n <= self.cap, "key/value cache capacity exhausted"
+        for _ in range(n):
+            if self.graph is not None:
+                self.graph.replay()
+            else:
+                self._step()
+        self.length += n
+        return self.out_tokens, self.scores

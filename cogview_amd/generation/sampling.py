@@ -66,6 +66,15 @@ def add_interlacing_beam_marks(seq, nb=12, period=3000):
             blk_cnt = 0
 
 
+def _slices_after(tok, current, n_img, n_txt, boi, eoi):
+    """The ids a marker forbids from the next position on (generation/sampling.py:88-95, 107-114)."""
+    if tok in boi:                                     # inside an image: only image codes may be generated
+        return [slice(n_img, None)]
+    if tok in eoi:                                     # after an image: only text pieces
+        return [slice(0, n_img), slice(n_img + n_txt, None)]
+    return current
+
+
 def filling_sequence(model, seq, args, mems=None, invalid_slices=[], tokenizer=None, **kwargs):
     """generation/sampling.py:65-186.  Returns the completed token rows [beams, len(seq)]."""
     tokenizer = tokenizer if tokenizer is not None else IdSpace()
@@ -80,11 +89,7 @@ def filling_sequence(model, seq, args, mems=None, invalid_slices=[], tokenizer=N
     invalid_slices = [slice(0, n_img)]
 
     def slices_after(tok, current):
-        if tok in boi:                                 # inside an image: only image codes may be generated
-            return [slice(n_img, None)]
-        if tok in eoi:                                 # after an image: only text pieces
-            return [slice(0, n_img), slice(n_img + n_txt, None)]
-        return current
+        return _slices_after(tok, current, n_img, n_txt, boi, eoi)
 
     while seq_l[context_length] >= 0:
         invalid_slices = slices_after(seq_l[context_length], invalid_slices)
@@ -198,3 +203,76 @@ def magnify(model, tokenizer, tokens_list, text_token_list, args, fill=None):
         done = fill(model, torch.cat([context, target.reshape(-1)], dim=0), args, invalid_slices=only_image_codes, tokenizer=tokenizer)
         big[16 * bi: 16 * bi + lines, 16 * bj: 16 * (bj + 2)] = done[0, len(context):].view(lines, 32)
     return big.view(1, 4 * side * side)
+
+
+def plan_device_generation(seq_l, tokenizer, vocab):
+    """Host planning of generate_on_device for a token list `seq_l` (filling_sequence's marks): a context of given ids, then
+    ONE run of equal marks (-nb / -1).  Returns dict(context, run, nb, allow=(lo, hi), offset, capacity); `allow` is the range
+    filling_sequence leaves drawable (its invalid slices after the context, by the same marker rule).  Raises
+    NotImplementedError for what only filling_sequence does."""
+    n_img, n_txt = tokenizer.img_tokenizer.num_tokens, tokenizer.txt_tokenizer.num_tokens
+    boi, eoi = (tokenizer['[BOI1]'], tokenizer['[BOI2]']), (tokenizer['[EOI1]'], tokenizer['[EOI2]'])
+    roi2 = tokenizer['[ROI2]']
+    n, offset, invalid = 0, 100000, [slice(0, n_img)]
+    while n < len(seq_l) and seq_l[n] >= 0:
+        invalid = _slices_after(seq_l[n], invalid, n_img, n_txt, boi, eoi)
+        if seq_l[n] == roi2:
+            offset = n
+        n += 1
+    if n == 0:
+        raise ValueError("the sequence must start with at least one given id")
+    if n == len(seq_l):
+        raise ValueError("nothing to generate: the sequence has no -1 / -nb marks")
+    run = seq_l[n:]
+    if any(t >= 0 for t in run):
+        raise NotImplementedError("given ids after generated ones (beams shrink there): use filling_sequence")
+    if any(t != run[0] for t in run):
+        raise NotImplementedError("the beam count changes inside the run: use filling_sequence")
+    keep = torch.ones(vocab, dtype=torch.bool)
+    for sl in invalid:
+        keep[sl] = False
+    idx = keep.nonzero().flatten().tolist()
+    if not idx or idx[-1] - idx[0] + 1 != len(idx):
+        raise NotImplementedError("the drawable ids are not one contiguous range: use filling_sequence")
+    capacity = -(-len(seq_l) // 64) * 64
+    if capacity > 4096:
+        raise NotImplementedError(f"{len(seq_l)} positions exceed the decode cache's 4096 slots: use filling_sequence")
+    return dict(context=n, run=len(run), nb=-run[0], allow=(idx[0], idx[-1] + 1), offset=offset, capacity=capacity)
+
+
+def generate_on_device(model, seq, args, tokenizer=None, seed=0, capture=True):
+    """filling_sequence for one run of generated tokens with the sampling on the device: prefill of the context (one row,
+    its keys / values broadcast into the nb cache rows), nb independent first draws from its last logits, then one
+    captured decode graph per token (generation/decoder.py SamplingDecoder) whose last launch filters, draws, and feeds
+    the drawn id to the next replay.  Same filter as filling_sequence (temperature, invalid slices, top_k_logits; top_p per
+    row); the draws come from the package's counter-based generator keyed (seed, step, row), not torch.multinomial.
+    Supported: dense attention (args.is_sparse == 0), one model-parallel partition, fp16 / bf16, <= 4096 positions.
+    Returns (tokens [nb, len(seq)], scores [nb] fp32: the summed log-probabilities of the drawn ids), on seq's device.
+    capture=False runs the same launches eagerly (the reference for the captured form)."""
+    from ..mpu.initialize import mp_world_size_or_1
+    from .decoder import SamplingDecoder
+    tokenizer = tokenizer if tokenizer is not None else IdSpace()
+    if args.is_sparse == 2:
+        raise NotImplementedError("sparse generation (is_sparse = 2): use filling_sequence")
+    if args.is_sparse != 0:
+        raise ValueError('set is_sparse==2 for inference.')
+    if mp_world_size_or_1() > 1:
+        raise NotImplementedError("model parallelism > 1: use filling_sequence")
+    assert seq.dim() == 1
+    m = model
+    while hasattr(m, "module"):
+        m = m.module
+    plan = plan_device_generation(seq.tolist(), tokenizer, m.word_embeddings.weight.shape[0])
+    n, run, nb = plan["context"], plan["run"], plan["nb"]
+    tokens, attention_mask, position_ids = get_batch(seq[:n], seq.device, args)
+    position_ids[position_ids > plan["offset"]] -= plan["offset"]
+    dec = SamplingDecoder(model, batch=nb, capacity=plan["capacity"])
+    out = torch.empty((nb, run), dtype=torch.long, device=tokens.device)
+    dec.enable_sampling(args.temperature, args.top_k, args.top_p, plan["allow"], seed, out_tokens=out, out_base=n)
+    with torch.no_grad():
+        dec.start(tokens, position_ids, attention_mask)
+        if run > 1:
+            if capture:
+                dec.capture()
+            dec.generate(run - 1)
+    return torch.cat((tokens.expand(nb, n), out), dim=1).to(seq.device), dec.scores.clone()

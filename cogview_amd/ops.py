@@ -954,3 +954,85 @@ def cast_flat_back(src_f32, dst_half):
     _need_gpu(src_f32, dst_half)
     L.check(L.lib().cogv_cast_flat_back(dt_code(dst_half), _p(src_f32), _p(dst_half), src_f32.numel(), _stream()),
             "cogv_cast_flat_back")
+
+
+# ------------------------------------------------------------------------------------------ token sampling
+def sample_logits(logits, *, temperature=1.0, top_k=0, top_p=0.0, allow=None, seed=0, offset=0, rows=None, ids=None,
+                  logp=None, scores=None, probs=False, decode=None):
+    """One draw per row of `logits` ([rows, vocab] or [rows, 1, vocab]; fp16 / bf16 / fp32; last dim contiguous) after the
+    reference's filter (generation/sampling.py:24-50, 168-186): x / temperature, ids outside `allow` = (lo, hi) masked,
+    top-k (ties at the threshold kept), top-p (per row), softmax, inverse-CDF draw keyed (seed, offset, row).
+    rows: number of draws when logits holds ONE row (row stride 0: `rows` draws from it).
+    offset: int, or a device int64 [1] tensor, which the launch advances by one.
+    ids / logp / scores: optional output tensors (int64 / fp32 / fp32 accumulator, [rows]).  probs=True also returns the
+    filtered distribution [rows, vocab] fp32.
+    decode: dict of the decode graph's buffers (generation/decoder.py SamplingDecoder): tok, pos, pos_index, table, counter,
+    out_tokens (optional), out_base.
+    Returns (ids, logp, probs or None).  Allocates nothing when every output is given (what a captured graph needs)."""
+    v = logits.shape[-1]
+    src = logits.reshape(-1, v) if logits.dim() != 2 else logits
+    _need_gpu(src)
+    assert src.stride(-1) == 1, "logits: the vocabulary dimension must be contiguous"
+    dev = src.device
+    n = src.shape[0] if rows is None else int(rows)
+    if rows is not None and src.shape[0] != 1:
+        raise ValueError("rows= broadcasts ONE row of logits")
+    lo, hi = (0, v) if allow is None else (int(allow[0]), int(allow[1]))
+    if not 0 <= lo < hi <= v:
+        raise ValueError(f"allowed range {allow} outside [0, {v})")
+    if not 0 <= int(top_k) <= hi - lo:
+        raise ValueError(f"top_k = {top_k} must lie in [0, {hi - lo}]")
+    if not temperature > 0 or not top_p >= 0:
+        raise ValueError("temperature must be > 0 and top_p >= 0")
+    if ids is None:
+        ids = torch.empty(n, dtype=torch.int64, device=dev)
+    if logp is None:
+        logp = torch.empty(n, dtype=torch.float32, device=dev)
+    pr = torch.empty((n, v), dtype=torch.float32, device=dev) if probs else None
+    for name, t, dt in (("ids", ids, torch.int64), ("logp", logp, torch.float32), ("scores", scores, torch.float32)):
+        if t is not None and (t.dtype != dt or t.numel() != n or not t.is_contiguous()):
+            raise ValueError(f"{name}: want a contiguous {dt} tensor of {n} elements")
+    d = L.SampleDesc()
+    d.dtype, d.rows, d.vocab = dt_code(src), n, v
+    d.row_stride = 0 if (rows is not None or n == 1) else src.stride(0)
+    d.logits = src.data_ptr()
+    d.temperature, d.top_k, d.top_p, d.allow_lo, d.allow_hi = float(temperature), int(top_k), float(top_p), lo, hi
+    d.seed = int(seed) & ((1 << 64) - 1)
+    if isinstance(offset, torch.Tensor):
+        assert offset.dtype == torch.int64 and offset.numel() == 1 and offset.device == dev
+        d.offset = offset.data_ptr()
+    elif offset:
+        off_t = torch.tensor([int(offset)], dtype=torch.int64, device=dev)     # read by the launch, not advanced
+        d.offset = off_t.data_ptr()
+    d.ids, d.logp, d.scores, d.probs = ids.data_ptr(), logp.data_ptr(), _ptr(scores), _ptr(pr)
+    if decode is not None:
+        tab = decode["table"]
+        assert tab.dtype == torch.int32 and tab.is_contiguous() and tab.shape[0] == n
+        for k in ("tok", "pos"):
+            assert decode[k].dtype == torch.int64 and decode[k].numel() == n and decode[k].is_contiguous()
+        d.tok, d.pos, d.pos_index = decode["tok"].data_ptr(), decode["pos"].data_ptr(), decode["pos_index"].data_ptr()
+        d.table, d.capacity = tab.data_ptr(), tab.shape[1]
+        d.counter = decode["counter"].data_ptr()
+        out = decode.get("out_tokens")
+        if out is not None:
+            assert out.dtype == torch.int64 and out.is_contiguous() and out.shape[0] == n
+            d.out_tokens, d.out_len, d.out_base = out.data_ptr(), out.shape[1], int(decode["out_base"])
+    elif isinstance(offset, torch.Tensor):
+        d.counter = _counter(dev).data_ptr()
+    L.check(L.lib().cogv_sample_logits(C.byref(d), _stream()), "cogv_sample_logits")
+    return ids, logp, pr
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+_COUNTERS = {}
+
+
+def _counter(dev):
+    """A zero-initialised completion counter per device (the sampler re-zeroes it at the end of every launch)."""
+    key = dev.index if dev.index is not None else torch.cuda.current_device()
+    if key not in _COUNTERS:
+        _COUNTERS[key] = torch.zeros(1, dtype=torch.int32, device=dev)
+    return _COUNTERS[key]

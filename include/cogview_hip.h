@@ -350,6 +350,33 @@ int cogv_adamw_step(const cogv_adam_desc* d, void* stream);
 int cogv_cast_flat(int dtype, const void* src_half, float* dst_f32, size_t n, void* stream);
 int cogv_cast_flat_back(int dtype, const float* src_f32, void* dst_half, size_t n, void* stream);
 
+/* ------------------------------------------------------------------ token sampling
+ * replaces the host sampling of generation/sampling.py:24-50 (top_k_logits) and :168-186 (temperature, invalid slices,
+ * softmax, multinomial, gather + log into the beam score).  One draw per row of logits[rows][vocab] (row_stride elements
+ * apart; 0 = every row reads the same logits, e.g. nb draws from one prefill row):
+ *   x = float(logit) / temperature (a division); ids outside [allow_lo, allow_hi) -> -inf;
+ *   top_k > 0: keep x >= the k-th largest value (ties at the threshold are all kept; 1 <= top_k <= allow_hi - allow_lo);
+ *   top_p > 0 (after top-k): keep the smallest descending prefix whose softmax mass exceeds top_p (first id always kept);
+ *   softmax over the kept ids; u from the counter-based generator keyed (seed, *offset), counter = row; the first kept id
+ *   (index order) whose inclusive prefix mass exceeds u * Z is drawn.  Fixed summation order: same (seed, *offset), same ids.
+ * Every output pointer may be NULL: ids int64 [rows]; logp fp32 [rows] = log p(id); scores fp32 [rows] += logp;
+ * probs fp32 [rows][vocab] = the filtered distribution.  vocab <= 65536.
+ * Decode-graph bookkeeping (generation/decoder.py SamplingDecoder; active when pos_index != NULL), with p = *pos_index:
+ *   tok[row] = id; pos[row] += 1; table[row][p + 1] = p + 1 (if < capacity); out_tokens[row][p + 1 - out_base] = id (if in
+ *   [0, out_len)); then the last workgroup to finish sets *pos_index = p + 1 and *offset += 1 and re-zeroes *counter, a
+ *   zero-initialised device word owned by this call site.  With these a replayed decode graph generates one token per replay. */
+typedef struct cogv_sample_desc {
+  int dtype; int rows; int vocab; int64_t row_stride;
+  const void* logits;
+  float temperature; int top_k; float top_p; int allow_lo; int allow_hi;
+  uint64_t seed; int64_t* offset;        /* offset: device int64 (NULL: 0); advanced only when counter != NULL */
+  int64_t* ids; float* logp; float* scores; float* probs;
+  int64_t* tok; int64_t* pos; int64_t* pos_index; int32_t* table; int capacity;
+  int64_t* out_tokens; int64_t out_len; int64_t out_base;
+  uint32_t* counter;
+} cogv_sample_desc;
+int cogv_sample_logits(const cogv_sample_desc* d, void* stream);
+
 /* ------------------------------------------------------------------ VQ-VAE tokenizer (fp32, exact-fp32 MFMA)
  * replaces the conv stacks of vqvae/vqvae_zc.py:121-129,159-164 (Encoder) and :172-192 (Decoder), the
  * nearest-code search :41-54 and embed_code :95-96 for the production config of vqvae/api.py:12-20.

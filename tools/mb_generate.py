@@ -1,0 +1,51 @@
+"""Text -> image generation latency of the 4B model (random weights, bf16): generation.generate_on_device (prefill +
+captured decode graph with the sampler inside) against filling_sequence with the in-place key/value cache (kv_cache=True:
+one eager model call and host sampling per token), for one 1024-code image at batch 1 and 8 (top_k 200, as the reference's
+scripts/text2image.sh).  `--sampler-only`: just the sampler kernel, 8 rows of 58 240 bf16 logits (for a rocprofv3 kernel
+trace of its own)."""
+import os, sys, time, types
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+
+if "--sampler-only" in sys.argv:
+    from cogview_amd import ops
+    x = torch.randn(8, 1, 58240, device="cuda").to(torch.bfloat16)
+    ids = torch.empty(8, dtype=torch.int64, device="cuda")
+    lp = torch.empty(8, dtype=torch.float32, device="cuda")
+    for top_p in (0.0, 0.9):
+        for i in range(50):
+            ops.sample_logits(x, temperature=1.0, top_k=200, top_p=top_p, allow=(0, 8192), seed=1, offset=i, ids=ids, logp=lp)
+    torch.cuda.synchronize()
+    print("sampler: 2 x 50 launches of 8 rows x 58240 (top_k 200, top_p 0 / 0.9)")
+    sys.exit(0)
+
+os.environ.setdefault("MASTER_ADDR", "127.0.0.1"); os.environ.setdefault("MASTER_PORT", "29591")
+import torch.distributed as dist
+dist.init_process_group("nccl", init_method="env://", world_size=1, rank=0)
+from cogview_amd import mpu
+from cogview_amd.fp16 import FP16_Module
+from cogview_amd.generation import IdSpace, add_interlacing_beam_marks, filling_sequence, generate_on_device
+from cogview_amd.model import GPT2Model
+mpu.initialize_model_parallel(1); torch.manual_seed(1); mpu.model_parallel_cuda_manual_seed(1)
+L, h, heads, V = 48, 2560, 40, 58240
+ids = IdSpace()
+model = FP16_Module(GPT2Model(L, V, h, heads, 0.1, 0.1, 0.1, 1089, 1089, False, kv_cache=True).cuda(), dtype=torch.bfloat16,
+                    keep_half_outputs=True).eval()
+text = torch.randint(8192, 58192, (20,)).tolist()
+args = types.SimpleNamespace(temperature=1.0, top_k=200, top_p=0.0, is_sparse=0)
+for nb in (1, 8):
+    seq = text + [ids["[BASE]"], ids["[BOI1]"]] + [-1] * 1024
+    add_interlacing_beam_marks(seq, nb=nb, period=3000)
+    seq = torch.tensor(seq, device="cuda")
+    generate_on_device(model, seq.clone(), args, seed=0)                       # warm-up (first-use allocations)
+    torch.cuda.synchronize(); t0 = time.time()
+    out, scores = generate_on_device(model, seq.clone(), args, seed=1)
+    torch.cuda.synchronize(); t_dev = time.time() - t0
+    assert int(out[:, -1024:].max()) < 8192 and torch.isfinite(scores).all()
+    torch.cuda.synchronize(); t0 = time.time()
+    ref = filling_sequence(model, seq.clone(), args)
+    torch.cuda.synchronize(); t_host = time.time() - t0
+    assert ref.shape == out.shape
+    print(f"batch {nb}: generate_on_device {t_dev:.2f} s = {t_dev / 1024 * 1e3:.2f} ms/token (prefill + capture included); "
+          f"filling_sequence kv_cache=True {t_host:.2f} s = {t_host / 1024 * 1e3:.2f} ms/token; speed-up {t_host / t_dev:.1f}x",
+          flush=True)
