@@ -14,6 +14,9 @@
 //          first id always included.
 //   draw   u = 24 bits of the counter-based generator keyed (seed, *offset), counter = row (common.cuh); the first kept id
 //          whose inclusive prefix mass exceeds u * Z wins.  Every sum has a fixed order: same (seed, offset) -> same ids.
+//   given  decode mode with a table of given ids (magnify's windows, generation/sampling.py DeviceFiller): where
+//          given[*pos_index + 1] >= 0 that id is fed instead of drawn -- the logits are not read, logp = 0, scores and the
+//          probabilities untouched; the bookkeeping and the counter are those of a draw.
 #include "common.cuh"
 #include "cogview_hip.h"
 
@@ -65,14 +68,29 @@ struct SampleSmem {
   int last;            // the last kept id
 };
 
+// the per-row results of one position (one thread): the id, its log-probability (added to the score when `score`), and in
+// decode mode the next step's token, position, visible slot and output column
+__device__ __forceinline__ void publish(const cogv_sample_desc& d, int row, int64_t id, float lp, bool score) {
+  if (d.ids) d.ids[row] = id;
+  if (d.logp) d.logp[row] = lp;
+  if (score && d.scores) d.scores[row] += lp;
+  if (d.pos_index) {
+    const int64_t p1 = *d.pos_index + 1;                 // sequence position the id will occupy
+    if (d.tok) d.tok[row] = id;
+    if (d.pos) d.pos[row] += 1;
+    if (d.table && p1 < d.capacity) d.table[(size_t)row * (size_t)d.capacity + p1] = (int32_t)p1;
+    const int64_t c = p1 - d.out_base;
+    if (d.out_tokens && c >= 0 && c < d.out_len) d.out_tokens[(size_t)row * (size_t)d.out_len + c] = id;
+  }
+}
+
+// filter + draw of one row (every thread of the workgroup).  Returns true on the thread that holds the drawn id, with the id
+// and its log-probability in *id_out / *lp_out
 template <typename T>
-__global__ __launch_bounds__(SB) void sample_kernel(cogv_sample_desc d) {
-  __shared__ SampleSmem sm;
-  const int row = blockIdx.x, t = threadIdx.x;
+__device__ __forceinline__ bool sample_row(const cogv_sample_desc& d, SampleSmem& sm, int row, int t, const T* src, int64_t off,
+                                           int64_t* id_out, float* lp_out) {
   const int vocab = d.vocab;
   const int64_t i0 = (int64_t)t * PER;
-  const T* src = reinterpret_cast<const T*>(d.logits) + (size_t)row * (size_t)d.row_stride;
-  const int64_t off = d.offset ? *d.offset : 0;
 
   // ---- load: x = float(logit) / temperature (a true division, as the host's `logits /= temperature`).  One base address
   // per thread and immediate offsets: per-element 64-bit addresses would not fit next to the 64 keys.
@@ -208,24 +226,37 @@ __global__ __launch_bounds__(SB) void sample_kernel(cogv_sample_desc d) {
 #pragma unroll
     for (int j = 0; j < PER; ++j) if (j < nv) pr[j] = any ? e[j] * rz : 0.f;
   }
-  // the winner's thread publishes the per-row results
+  // the winner's thread hands the per-row results back
   if (i0 <= id && id < i0 + PER) {
     float ew = 0.f;
 #pragma unroll
     for (int j = 0; j < PER; ++j) if (i0 + j == id) ew = e[j];
-    const float lp = any ? logf(ew / zall) : -INFINITY;
-    if (d.ids) d.ids[row] = id;
-    if (d.logp) d.logp[row] = lp;
-    if (d.scores) d.scores[row] += lp;
-    if (d.pos_index) {
-      const int64_t p1 = *d.pos_index + 1;                 // sequence position the drawn id will occupy
-      if (d.tok) d.tok[row] = id;
-      if (d.pos) d.pos[row] += 1;
-      if (d.table && p1 < d.capacity) d.table[(size_t)row * (size_t)d.capacity + p1] = (int32_t)p1;
-      const int64_t c = p1 - d.out_base;
-      if (d.out_tokens && c >= 0 && c < d.out_len) d.out_tokens[(size_t)row * (size_t)d.out_len + c] = id;
-    }
+    *id_out = id;
+    *lp_out = any ? logf(ew / zall) : -INFINITY;
+    return true;
   }
+  return false;
+}
+
+template <typename T>
+__global__ __launch_bounds__(SB) void sample_kernel(cogv_sample_desc d) {
+  __shared__ SampleSmem sm;
+  const int row = blockIdx.x, t = threadIdx.x;
+  const T* src = reinterpret_cast<const T*>(d.logits) + (size_t)row * (size_t)d.row_stride;
+  const int64_t off = d.offset ? *d.offset : 0;
+  // a given id for the position this launch fills (decode mode only, checked by the host): the same address for every
+  // thread, so the branch below is uniform across the workgroup and is taken before any barrier.  A given id is published
+  // by thread 0 with logp 0 and no score; one publish site for both paths keeps the register allocation of the draw
+  int64_t fed = -1;
+  if (d.given) {
+    const int64_t p1 = *d.pos_index + 1;
+    if (p1 >= 0 && p1 < d.capacity) fed = d.given[p1];
+  }
+  int64_t id = fed;
+  float lp = 0.f;
+  bool mine = t == 0;
+  if (fed < 0) mine = sample_row<T>(d, sm, row, t, src, off, &id, &lp);
+  if (mine) publish(d, row, id, lp, fed < 0);
   // the last workgroup to finish advances the shared scalars (every other one has read them by then) and resets the counter
   if (d.counter && (d.pos_index || d.offset)) {
     __shared__ bool last;
@@ -251,6 +282,7 @@ extern "C" int cogv_sample_logits(const cogv_sample_desc* d, void* stream) {
   if (d->top_k > d->allow_hi - d->allow_lo) return COGV_ERR_ARG;
   if (d->row_stride != 0 && d->row_stride < d->vocab) return COGV_ERR_ARG;
   if (d->pos_index && (!d->counter || (d->table && d->capacity <= 0) || (d->out_tokens && d->out_len <= 0))) return COGV_ERR_ARG;
+  if (d->given && (!d->pos_index || d->capacity <= 0)) return COGV_ERR_ARG;
   if (d->rows > 65535) return COGV_ERR_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
   switch (d->dtype) {

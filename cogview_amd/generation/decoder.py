@@ -33,7 +33,8 @@ class GraphDecoder:
         self.pos = torch.zeros((batch, 1), dtype=torch.long, device=dev)
         self.pos_index = torch.zeros(1, dtype=torch.long, device=dev)
         self.table = torch.arange(capacity, dtype=torch.int64, device=dev)
-        self.table = ((self.table | (1 << 31)) - (1 << 32)).to(torch.int32).unsqueeze(0).repeat(batch, 1).contiguous()
+        self.masked = ((self.table | (1 << 31)) - (1 << 32)).to(torch.int32)       # every slot flagged: nothing visible
+        self.table = self.masked.unsqueeze(0).repeat(batch, 1).contiguous()
         self.caches = [torch.zeros((batch, capacity, 2 * hp), dtype=dt, device=dev) for _ in tr.layers]
         self.slots = [StaticKVSlot(c, self.pos_index, self.table) for c in self.caches]
         self.slab = torch.zeros(8 * len(tr.layers) + 16, dtype=torch.float32, device=dev)
@@ -90,6 +91,7 @@ class GraphDecoder:
         for c, mem in zip(self.caches, mems):
             c[:, :n].copy_(mem)
         self.table[:, :n] = torch.arange(n, dtype=torch.int32, device=self.table.device)
+        self.table[:, n:] = self.masked[n:]           # a longer earlier run left these visible (the op-by-op step reads them)
         self.length = n
         return logits
 
@@ -122,22 +124,26 @@ class SamplingDecoder(GraphDecoder):
         super().__init__(model, batch, capacity)
         self.sampling = None
 
-    def enable_sampling(self, temperature=1.0, top_k=0, top_p=0.0, allow=None, seed=0, out_tokens=None, out_base=0):
+    def enable_sampling(self, temperature=1.0, top_k=0, top_p=0.0, allow=None, seed=0, out_tokens=None, out_base=0,
+                        given=None):
         """allow: (lo, hi) range of ids that may be drawn (None: all); out_tokens: int64 [batch, n] that receives the id
-        drawn for sequence position out_base + j in column j (None: not recorded)."""
+        drawn for sequence position out_base + j in column j (None: not recorded); given: int64 [capacity] device buffer,
+        by sequence position, of ids to feed instead of drawing (-1: draw), shared by all rows -- device data, so one
+        captured graph serves any table written into it (None: every position is drawn)."""
         dev = self.tok.device
         assert out_tokens is None or (out_tokens.dtype == torch.int64 and out_tokens.shape[0] == self.batch)
+        assert given is None or (given.dtype == torch.int64 and given.numel() >= self.cap and given.device == dev)
         self.sampling = dict(temperature=float(temperature), top_k=int(top_k), top_p=float(top_p), allow=allow, seed=int(seed))
         self.offset = torch.zeros(1, dtype=torch.int64, device=dev)        # generator offset: one per draw
         self.ids = torch.zeros(self.batch, dtype=torch.int64, device=dev)
         self.logp = torch.zeros(self.batch, dtype=torch.float32, device=dev)
         self.scores = torch.zeros(self.batch, dtype=torch.float32, device=dev)
         self.counter = torch.zeros(1, dtype=torch.int32, device=dev)       # the sampler's completion counter
-        self.out_tokens, self.out_base = out_tokens, int(out_base)
+        self.out_tokens, self.out_base, self.given = out_tokens, int(out_base), given
 
     def _sample(self, logits, rows=None):
         dec = dict(tok=self.tok.view(-1), pos=self.pos.view(-1), pos_index=self.pos_index, table=self.table,
-                   counter=self.counter, out_tokens=self.out_tokens, out_base=self.out_base)
+                   counter=self.counter, out_tokens=self.out_tokens, out_base=self.out_base, given=self.given)
         ops.sample_logits(logits, **self.sampling, offset=self.offset, rows=rows, ids=self.ids, logp=self.logp,
                           scores=self.scores, decode=dec)
 

@@ -205,14 +205,16 @@ def magnify(model, tokenizer, tokens_list, text_token_list, args, fill=None):
     return big.view(1, 4 * side * side)
 
 
-def plan_device_generation(seq_l, tokenizer, vocab):
-    """Host planning of generate_on_device for a token list `seq_l` (filling_sequence's marks): a context of given ids, then
-    ONE run of equal marks (-nb / -1).  Returns dict(context, run, nb, allow=(lo, hi), offset, capacity); `allow` is the range
-    filling_sequence leaves drawable (its invalid slices after the context, by the same marker rule).  Raises
-    NotImplementedError for what only filling_sequence does."""
+def _markers(tokenizer):
     n_img, n_txt = tokenizer.img_tokenizer.num_tokens, tokenizer.txt_tokenizer.num_tokens
     boi, eoi = (tokenizer['[BOI1]'], tokenizer['[BOI2]']), (tokenizer['[EOI1]'], tokenizer['[EOI2]'])
-    roi2 = tokenizer['[ROI2]']
+    return n_img, n_txt, boi, eoi, tokenizer['[ROI2]']
+
+
+def _plan_context(seq_l, tokenizer):
+    """The context walk of the device planners (filling_sequence's, up to its first model call): the given ids before the
+    first mark, the slices the marker rule forbids after them, and the [ROI2] offset.  Returns (n, offset, invalid)."""
+    n_img, n_txt, boi, eoi, roi2 = _markers(tokenizer)
     n, offset, invalid = 0, 100000, [slice(0, n_img)]
     while n < len(seq_l) and seq_l[n] >= 0:
         invalid = _slices_after(seq_l[n], invalid, n_img, n_txt, boi, eoi)
@@ -223,21 +225,89 @@ def plan_device_generation(seq_l, tokenizer, vocab):
         raise ValueError("the sequence must start with at least one given id")
     if n == len(seq_l):
         raise ValueError("nothing to generate: the sequence has no -1 / -nb marks")
-    run = seq_l[n:]
-    if any(t >= 0 for t in run):
-        raise NotImplementedError("given ids after generated ones (beams shrink there): use filling_sequence")
-    if any(t != run[0] for t in run):
-        raise NotImplementedError("the beam count changes inside the run: use filling_sequence")
+    return n, offset, invalid
+
+
+def _plan_allow(invalid, vocab):
+    """The ids `invalid` leaves drawable, as the sampler's one (lo, hi) range."""
     keep = torch.ones(vocab, dtype=torch.bool)
     for sl in invalid:
         keep[sl] = False
     idx = keep.nonzero().flatten().tolist()
     if not idx or idx[-1] - idx[0] + 1 != len(idx):
         raise NotImplementedError("the drawable ids are not one contiguous range: use filling_sequence")
-    capacity = -(-len(seq_l) // 64) * 64
+    return idx[0], idx[-1] + 1
+
+
+def _plan_capacity(length):
+    capacity = -(-length // 64) * 64
     if capacity > 4096:
-        raise NotImplementedError(f"{len(seq_l)} positions exceed the decode cache's 4096 slots: use filling_sequence")
-    return dict(context=n, run=len(run), nb=-run[0], allow=(idx[0], idx[-1] + 1), offset=offset, capacity=capacity)
+        raise NotImplementedError(f"{length} positions exceed the decode cache's 4096 slots: use filling_sequence")
+    return capacity
+
+
+def plan_device_generation(seq_l, tokenizer, vocab):
+    """Host planning of generate_on_device for a token list `seq_l` (filling_sequence's marks): a context of given ids, then
+    ONE run of equal marks (-nb / -1).  Returns dict(context, run, nb, allow=(lo, hi), offset, capacity); `allow` is the range
+    filling_sequence leaves drawable (its invalid slices after the context, by the same marker rule).  Raises
+    NotImplementedError for what only filling_sequence does."""
+    n, offset, invalid = _plan_context(seq_l, tokenizer)
+    run = seq_l[n:]
+    if any(t >= 0 for t in run):
+        raise NotImplementedError("given ids after generated ones (beams shrink there): use filling_sequence")
+    if any(t != run[0] for t in run):
+        raise NotImplementedError("the beam count changes inside the run: use filling_sequence")
+    allow = _plan_allow(invalid, vocab)
+    return dict(context=n, run=len(run), nb=-run[0], allow=allow, offset=offset, capacity=_plan_capacity(len(seq_l)))
+
+
+def plan_device_fill(seq_l, tokenizer, vocab):
+    """Host planning of DeviceFiller: what filling_sequence does with nb = 1 -- a context of given ids, then -1 marks with
+    given ids anywhere after them (magnify's windows: lines an earlier window wrote sit between generated ones).
+    Returns dict(context, given, replays, trailing, allow=(lo, hi), offset, capacity):
+      given     one entry per position of seq_l: the id a decode step feeds there instead of drawing, -1 elsewhere (the
+                context included: the prefill reads it);
+      replays   decode steps after the prefill's first draw: one per position from context + 1 to the last mark;
+      trailing  given ids after the last mark (copied on the host: no model call reads them).
+    Raises NotImplementedError (naming filling_sequence) for -nb marks with nb > 1, a given [BOI*] / [EOI*] inside the run
+    that changes the drawable range, [ROI2] inside the run, more than 4096 positions."""
+    _, _, boi, eoi, roi2 = _markers(tokenizer)
+    n_img, n_txt = tokenizer.img_tokenizer.num_tokens, tokenizer.txt_tokenizer.num_tokens
+    n, offset, invalid = _plan_context(seq_l, tokenizer)
+    marks = [i for i in range(n, len(seq_l)) if seq_l[i] < 0]
+    if any(seq_l[i] != -1 for i in marks):
+        raise NotImplementedError("-nb marks with nb > 1 (beams shrink at every given id): use filling_sequence")
+    last = marks[-1]
+    given = [-1] * len(seq_l)
+    for i in range(n + 1, last):
+        t = seq_l[i]
+        if t < 0:
+            continue
+        if t == roi2:
+            raise NotImplementedError("[ROI2] inside the run (positions restart there): use filling_sequence")
+        if _slices_after(t, invalid, n_img, n_txt, boi, eoi) != invalid:
+            raise NotImplementedError(f"given id {t} inside the run changes the drawable range: use filling_sequence")
+        given[i] = t
+    allow = _plan_allow(invalid, vocab)
+    return dict(context=n, given=given, replays=last - n, trailing=len(seq_l) - 1 - last, allow=allow, offset=offset,
+                capacity=_plan_capacity(len(seq_l)))
+
+
+def _refuse_unsupported(args):
+    """What only filling_sequence does, refused before the model is touched."""
+    from ..mpu.initialize import mp_world_size_or_1
+    if args.is_sparse == 2:
+        raise NotImplementedError("sparse generation (is_sparse = 2): use filling_sequence")
+    if args.is_sparse != 0:
+        raise ValueError('set is_sparse==2 for inference.')
+    if mp_world_size_or_1() > 1:
+        raise NotImplementedError("model parallelism > 1: use filling_sequence")
+
+
+def _unwrap(model):
+    while hasattr(model, "module"):
+        model = model.module
+    return model
 
 
 def generate_on_device(model, seq, args, tokenizer=None, seed=0, capture=True):
@@ -249,20 +319,11 @@ def generate_on_device(model, seq, args, tokenizer=None, seed=0, capture=True):
     Supported: dense attention (args.is_sparse == 0), one model-parallel partition, fp16 / bf16, <= 4096 positions.
     Returns (tokens [nb, len(seq)], scores [nb] fp32: the summed log-probabilities of the drawn ids), on seq's device.
     capture=False runs the same launches eagerly (the reference for the captured form)."""
-    from ..mpu.initialize import mp_world_size_or_1
     from .decoder import SamplingDecoder
     tokenizer = tokenizer if tokenizer is not None else IdSpace()
-    if args.is_sparse == 2:
-        raise NotImplementedError("sparse generation (is_sparse = 2): use filling_sequence")
-    if args.is_sparse != 0:
-        raise ValueError('set is_sparse==2 for inference.')
-    if mp_world_size_or_1() > 1:
-        raise NotImplementedError("model parallelism > 1: use filling_sequence")
+    _refuse_unsupported(args)
     assert seq.dim() == 1
-    m = model
-    while hasattr(m, "module"):
-        m = m.module
-    plan = plan_device_generation(seq.tolist(), tokenizer, m.word_embeddings.weight.shape[0])
+    plan = plan_device_generation(seq.tolist(), tokenizer, _unwrap(model).word_embeddings.weight.shape[0])
     n, run, nb = plan["context"], plan["run"], plan["nb"]
     tokens, attention_mask, position_ids = get_batch(seq[:n], seq.device, args)
     position_ids[position_ids > plan["offset"]] -= plan["offset"]
@@ -276,3 +337,73 @@ def generate_on_device(model, seq, args, tokenizer=None, seed=0, capture=True):
                 dec.capture()
             dec.generate(run - 1)
     return torch.cat((tokens.expand(nb, n), out), dim=1).to(seq.device), dec.scores.clone()
+
+
+class DeviceFiller:
+    """filling_sequence for nb = 1 on ONE captured decode graph that is reused call after call: magnify's sequence filler
+    (`magnify(model, tokenizer, code, text, args, fill=DeviceFiller(model, args))`, super-resolution).  Per call: the given
+    table goes to the device, the context is prefilled (one eager model call) and its last logits draw the first mark, then
+    one graph replay per later position up to the last mark -- the sampler inside it draws at a mark and feeds the given
+    id elsewhere (cogv_sample_desc.given); given ids after the last mark are copied on the host.
+    What changes from call to call is device data: the given table, the token / position / slot buffers, the generator
+    offset (it keeps counting across calls, so every window draws fresh numbers) and the output row ([1, capacity],
+    column = sequence position).  Temperature, top-k / top-p and the drawable range are baked into the capture: a call
+    with other values re-arms the sampler and captures again.
+    Same filter as filling_sequence; draws from the package's counter-based generator keyed (seed, step, row).  Dense
+    attention, one model-parallel partition, <= capacity positions (1408: the reference's MAXSEQLEN 1345 rounded up to 64).
+    capture=False runs the same launches eagerly.  After a call, .scores is [1] fp32: the summed log-probability of the
+    drawn ids (given ids add nothing)."""
+
+    def __init__(self, model, args, seed=0, capacity=1408, capture=True):
+        _refuse_unsupported(args)
+        if not 0 < capacity <= 4096:
+            raise ValueError(f"capacity {capacity} outside (0, 4096]: the decode cache's limit")
+        self.model, self.seed, self.capacity, self.capture = model, int(seed), int(capacity), capture
+        self.dec, self.key, self.scores = None, None, None
+
+    def _decoder(self, args, allow):
+        from .decoder import SamplingDecoder
+        if self.dec is None:
+            self.dec = SamplingDecoder(self.model, batch=1, capacity=self.capacity)
+            dev = self.dec.tok.device
+            self.out = torch.empty((1, self.capacity), dtype=torch.long, device=dev)
+            self.given = torch.full((self.capacity,), -1, dtype=torch.long, device=dev)
+        key = (float(args.temperature), int(args.top_k), float(args.top_p), tuple(allow))
+        if key != self.key:
+            offset = self.dec.offset.clone() if self.key is not None else None
+            self.dec.enable_sampling(*key[:3], allow=allow, seed=self.seed, out_tokens=self.out, out_base=0, given=self.given)
+            if offset is not None:
+                self.dec.offset.copy_(offset)
+            self.dec.graph, self.key = None, key
+        return self.dec
+
+    def __call__(self, model, seq, args, invalid_slices=None, tokenizer=None):
+        """filling_sequence's signature and result: the completed row [1, len(seq)] on seq's device.  invalid_slices is
+        ignored in favour of the marker rule, as filling_sequence ignores it."""
+        _refuse_unsupported(args)
+        if model is not self.model:
+            raise ValueError("this DeviceFiller was built for another model")
+        assert seq.dim() == 1
+        if len(seq) > self.capacity:
+            raise NotImplementedError(f"{len(seq)} positions exceed this filler's {self.capacity} decode slots: use "
+                                      f"filling_sequence or a larger capacity")
+        tokenizer = tokenizer if tokenizer is not None else IdSpace()
+        seq_l = seq.tolist()
+        plan = plan_device_fill(seq_l, tokenizer, _unwrap(model).word_embeddings.weight.shape[0])
+        n, replays = plan["context"], plan["replays"]
+        dec = self._decoder(args, plan["allow"])
+        tokens, attention_mask, position_ids = get_batch(seq[:n], dec.tok.device, args)
+        position_ids[position_ids > plan["offset"]] -= plan["offset"]
+        table = torch.full((self.capacity,), -1, dtype=torch.long)
+        table[:len(seq_l)] = torch.tensor(plan["given"], dtype=torch.long)
+        dec.given.copy_(table)                        # before start(): its draw reads the entry of position n (-1)
+        with torch.no_grad():
+            dec.start(tokens, position_ids, attention_mask)
+            if replays:
+                if self.capture and dec.graph is None:
+                    dec.capture()
+                dec.generate(replays)
+        out = seq.clone()
+        out[n:n + replays + 1] = self.out[0, n:n + replays + 1].to(seq.device)
+        self.scores = dec.scores.clone()
+        return out.unsqueeze(0)

@@ -967,7 +967,8 @@ def sample_logits(logits, *, temperature=1.0, top_k=0, top_p=0.0, allow=None, se
     ids / logp / scores: optional output tensors (int64 / fp32 / fp32 accumulator, [rows]).  probs=True also returns the
     filtered distribution [rows, vocab] fp32.
     decode: dict of the decode graph's buffers (generation/decoder.py SamplingDecoder): tok, pos, pos_index, table, counter,
-    out_tokens (optional), out_base.
+    out_tokens (optional), out_base, given (optional: int64 [>= capacity] by sequence position, shared by all rows; where
+    given[*pos_index + 1] >= 0 that id is fed instead of drawn, with logp 0 and no score).
     Returns (ids, logp, probs or None).  Allocates nothing when every output is given (what a captured graph needs)."""
     v = logits.shape[-1]
     src = logits.reshape(-1, v) if logits.dim() != 2 else logits
@@ -1017,6 +1018,11 @@ def sample_logits(logits, *, temperature=1.0, top_k=0, top_p=0.0, allow=None, se
         if out is not None:
             assert out.dtype == torch.int64 and out.is_contiguous() and out.shape[0] == n
             d.out_tokens, d.out_len, d.out_base = out.data_ptr(), out.shape[1], int(decode["out_base"])
+        given = decode.get("given")
+        if given is not None:
+            if given.dtype != torch.int64 or not given.is_contiguous() or given.numel() < d.capacity or given.device != dev:
+                raise ValueError(f"given: want a contiguous int64 tensor of >= {d.capacity} elements on {dev}")
+            d.given = given.data_ptr()
     elif isinstance(offset, torch.Tensor):
         d.counter = _counter(dev).data_ptr()
     L.check(L.lib().cogv_sample_logits(C.byref(d), _stream()), "cogv_sample_logits")

@@ -2,7 +2,9 @@
 captured decode graph with the sampler inside) against filling_sequence with the in-place key/value cache (kv_cache=True:
 one eager model call and host sampling per token), for one 1024-code image at batch 1 and 8 (top_k 200, as the reference's
 scripts/text2image.sh).  `--sampler-only`: just the sampler kernel, 8 rows of 58 240 bf16 logits (for a rocprofv3 kernel
-trace of its own)."""
+trace of its own).  `--super-resolution`: one generation.magnify of a random 32 x 32 code map (nine windows, top_k 200,
+temperature 1.02, as the reference's scripts/super_resolution.sh) with fill=DeviceFiller and with filling_sequence
+(kv_cache=True), wall seconds per image for each and the split of the device form's decode replays."""
 import os, sys, time, types
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -24,14 +26,46 @@ import torch.distributed as dist
 dist.init_process_group("nccl", init_method="env://", world_size=1, rank=0)
 from cogview_amd import mpu
 from cogview_amd.fp16 import FP16_Module
-from cogview_amd.generation import IdSpace, add_interlacing_beam_marks, filling_sequence, generate_on_device
+from cogview_amd.generation import (DeviceFiller, IdSpace, add_interlacing_beam_marks, filling_sequence, generate_on_device,
+                                    magnify, plan_device_fill)
 from cogview_amd.model import GPT2Model
 mpu.initialize_model_parallel(1); torch.manual_seed(1); mpu.model_parallel_cuda_manual_seed(1)
 L, h, heads, V = 48, 2560, 40, 58240
+SR = "--super-resolution" in sys.argv
 ids = IdSpace()
-model = FP16_Module(GPT2Model(L, V, h, heads, 0.1, 0.1, 0.1, 1089, 1089, False, kv_cache=True).cuda(), dtype=torch.bfloat16,
-                    keep_half_outputs=True).eval()
+# super-resolution windows reach 1305 positions: filling_sequence's memory must hold them all, as the decode graph does
+max_mem = 1408 if SR else 1089
+model = FP16_Module(GPT2Model(L, V, h, heads, 0.1, 0.1, 0.1, 1089, max_mem, False, kv_cache=True).cuda(),
+                    dtype=torch.bfloat16, keep_half_outputs=True).eval()
 text = torch.randint(8192, 58192, (20,)).tolist()
+
+if SR:
+    args = types.SimpleNamespace(temperature=1.02, top_k=200, top_p=0.0, is_sparse=0)
+    code = torch.randint(0, 8192, (1024,), device="cuda")
+    text_t = torch.tensor(text, device="cuda")
+    seqs = []
+    filler = DeviceFiller(model, args, seed=1)
+
+    def fill(model_, seq, args_, invalid_slices=None, tokenizer=None):
+        seqs.append(seq.tolist())
+        return filler(model_, seq, args_, invalid_slices, tokenizer)
+
+    torch.cuda.synchronize(); t0 = time.time()
+    big_dev = magnify(model, ids, code, text_t, args, fill=fill)
+    torch.cuda.synchronize(); t_dev = time.time() - t0
+    torch.cuda.synchronize(); t0 = time.time()
+    big_host = magnify(model, ids, code, text_t, args)
+    torch.cuda.synchronize(); t_host = time.time() - t0
+    assert big_dev.shape == big_host.shape == (1, 4096) and int(big_dev.max()) < 8192 and int(big_host.max()) < 8192
+    plans = [plan_device_fill(s, ids, V) for s in seqs]
+    replays = sum(p["replays"] for p in plans)
+    given = sum(sum(1 for g in p["given"] if g >= 0) for p in plans)
+    print(f"super-resolution, one image (9 windows, {sum(len(s) for s in seqs)} positions): DeviceFiller {t_dev:.2f} s "
+          f"(prefills + capture included); filling_sequence kv_cache=True {t_host:.2f} s; speed-up {t_host / t_dev:.2f}x")
+    print(f"device form: {len(plans)} prefills (each draws one code), {replays} decode replays = {replays - given} generated "
+          f"+ {given} given inside the runs; {sum(p['trailing'] for p in plans)} trailing given ids copied on the host; "
+          f"{t_dev / (replays + len(plans)) * 1e3:.2f} ms per model call", flush=True)
+    sys.exit(0)
 args = types.SimpleNamespace(temperature=1.0, top_k=200, top_p=0.0, is_sparse=0)
 for nb in (1, 8):
     seq = text + [ids["[BASE]"], ids["[BOI1]"]] + [-1] * 1024
