@@ -17,8 +17,13 @@ replica, BASELINE.json configs[3]) -- rows of 1089 random tokens (1088 model pos
 tokenizer: img2code + code2img of 256 images of 256x256 per step, replicas only); `--config cogview-tiny-18M` runs
 configs[0] (4 L / 256 h / 4 heads, rows of 256 -- the case the reference itself runs on a CPU).  Without `--dtype` the
 run measures fp16 -- the reference's own storage type (fp16/fp16.py) and the one whose logits meet north_star's 1e-3 bar
-at 48 layers: it is the headline `value` / `dtype` -- and, at N = 1, the same step in bf16 (BASELINE configs[3]'s
-extension; logits 2e-3..5e-3, above the bar) reported under "bf16_leg".  Prints ONE JSON line (rank 0).
+at 48 layers: it is the headline `value` / `dtype`.  Prints ONE JSON line (rank 0).
+
+A plain run does what the headline needs and nothing more: set up, warm up, time the steps, write --dump-outputs, print.
+`--full` adds, at N = 1, what takes runs of its own: the same step in bf16 when `--dtype` is not given (BASELINE
+configs[3]'s extension; logits 2e-3..5e-3, above the bar) reported under "bf16_leg", the logits of each timed model
+against the fp32 CPU oracle at full depth, and the CPU baselines (one to two minutes more at 4B).  --dump-outputs writes
+the arrays of both dtype legs, so a plain run given it runs the bf16 leg too (without the logits check).
 """
 import argparse
 import json
@@ -30,6 +35,10 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+if __name__ == "__main__":
+    # torch's host allocator puts blocks of 2 MB and more on transparent huge pages: the 4B model is initialised in 15.7 GB of
+    # host memory, and faulting that in and releasing it at .cuda() takes 10.5 s instead of 17.5 s of the set-up (same weights)
+    os.environ.setdefault("THP_MEM_ALLOC_ENABLE", "1")
 
 import torch  # noqa: E402
 
@@ -573,7 +582,10 @@ def main():
                     help="micro-batch per GPU (sequences of 1089 tokens / images); default per config")
     ap.add_argument("--dtype", default=None, choices=["bf16", "fp16"],
                     help="default: fp16 (the reference's dtype; meets the 1e-3 logits bar) as the headline value, plus a bf16 leg "
-                         "in the same line when N=1")
+                         "in the same line with --full or --dump-outputs when N=1")
+    ap.add_argument("--full", action="store_true",
+                    help="at N = 1 also run what the headline does not need: the bf16 leg (also run for --dump-outputs), the "
+                         "full-depth logits check of each timed model against the CPU oracle and the CPU baselines (off by default)")
     ap.add_argument("--model-parallel", type=int, default=1,
                     help="model-parallel size (BASELINE configs[2]: 2); ranks r, r+1 form a group (mpu/initialize.py)")
     ap.add_argument("--shard-optimizer", action="store_true",
@@ -582,12 +594,12 @@ def main():
     ap.add_argument("--dropout", type=float, default=0.1, help="reference default (arguments.py:30,40)")
     ap.add_argument("--checkpoint-activations", action="store_true",
                     help="recompute each layer in backward (the reference's scripts do; 288 GB HBM makes it unnecessary)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines and the logits check")
     ap.add_argument("--no-kernel-timing", action="store_true")
-    ap.add_argument("--no-second-dtype", action="store_true", help="skip the bf16 leg of the default run")
+    ap.add_argument("--no-second-dtype", action="store_true", help="skip the bf16 leg of --full / --dump-outputs")
     ap.add_argument("--no-parity", action="store_true",
-                    help="skip the full-depth logits check of the timed model against the CPU oracle (about one CPU "
-                         "minute per dtype at 4B; part of the cpu_baseline leg, so --no-cpu-baseline skips it too)")
+                    help="with --full: skip the full-depth logits check of the timed model against the CPU oracle (10-20 CPU "
+                         "seconds per dtype at 4B; part of the cpu_baseline leg, so --no-cpu-baseline skips it too)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / "
                          "float64, at most 64 MB: loss, skip flag and a seeded sample of the updated parameters per dtype "
@@ -605,20 +617,22 @@ def main():
     import torch.distributed as dist
     from cogview_amd import mpu
     dumps = {} if args.dump_outputs else None
+    cpu_legs = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
 
     if args.config == "vqvae":
         mpu.initialize_model_parallel(1)
         out = run_vqvae(args, world, rank, dumps=dumps)
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        if cpu_legs:
             out["cpu_baseline"] = cpu_baseline_vqvae()
     else:
         mp = args.model_parallel
         assert world % mp == 0, "--gpus must be a multiple of --model-parallel"
         mpu.initialize_model_parallel(mp)
         L, h, heads = CONFIGS[args.config]
-        parity = world == 1 and mp == 1 and not args.no_cpu_baseline and not args.no_parity
+        parity = cpu_legs and mp == 1 and not args.no_parity
         out = run_gpt(args, args.dtype or "fp16", world, rank, mp, parity=parity, dumps=dumps)
-        if args.dtype is None and world == 1 and not args.no_second_dtype:
+        # the bf16 leg: with --full, and with --dump-outputs, whose arrays hold both legs
+        if (args.full or dumps is not None) and args.dtype is None and world == 1 and not args.no_second_dtype:
             leg = run_gpt(args, "bf16", world, rank, mp, parity=parity, dumps=dumps)
             out["bf16_leg"] = {k: leg[k] for k in ("value", "unit", "ms_per_step", "dtype", "model_tflops_per_gpu",
                                                    "mfma_roofline_frac_end_to_end", "mfma_roofline_frac_causal_discounted",
@@ -629,7 +643,7 @@ def main():
             if "roofline" in leg:
                 out["bf16_leg"]["roofline"] = {k: leg["roofline"][k] for k in ("achieved", "peak", "unit", "frac", "launches",
                                                                                "avg_launch_ms", "share_of_step_time")}
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        if cpu_legs:
             out["cpu_baseline"] = cpu_baseline(L, h, heads, row=ROW_LEN.get(args.config, ROW))
             # the REFERENCE ITSELF timed beside the port where /root/reference exists (the build container): configs[0] whole
             # (oracle/time_reference_cfg1.py), the 4B headline on the same bounded sample as the port above

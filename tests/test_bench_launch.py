@@ -128,3 +128,33 @@ def test_bench_dump_outputs_writes_the_last_timed_step(tmp_path):
     assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
     assert float(arrs["fp16_loss"]) == out["config"]["loss"] and float(arrs["bf16_loss"]) == out["bf16_leg"]["loss"]
     assert arrs["fp16_params_sample"].shape == arrs["bf16_params_sample"].shape and np.isfinite(arrs["fp16_params_sample"]).all()
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_the_headline_of_the_full_run(tmp_path):
+    """GPU box: a plain run carries only what its headline needs.  On configs[0] its line has no bf16 leg, no CPU baseline
+    and no measured logits error, all of which the `--full` line has; given --dump-outputs it writes the same arrays as the
+    `--full` run, bit for bit (both dtype legs)."""
+    import numpy as np
+    runs = {}
+    for name, extra in (("plain", []), ("plain_dump", ["--dump-outputs", str(tmp_path / "plain_dump")]),
+                        ("full_dump", ["--full", "--dump-outputs", str(tmp_path / "full_dump")])):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "cogview-tiny-18M", "--steps", "3",
+                            "--warmup", "1"] + extra, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        out_dir = tmp_path / name
+        runs[name] = json.loads(lines[0]), ({p.name[:-4]: np.load(str(p)) for p in out_dir.iterdir()} if out_dir.exists() else None)
+    plain, full = runs["plain"][0], runs["full_dump"][0]
+    plain_arrs, full_arrs = runs["plain_dump"][1], runs["full_dump"][1]
+    assert runs["plain"][1] is None
+    assert sorted(plain_arrs) == sorted(full_arrs) == sorted(f"{d}_{n}" for d in ("fp16", "bf16") for n in ("loss", "skipped", "params_sample"))
+    assert all(np.array_equal(a, full_arrs[k]) for k, a in plain_arrs.items())
+    assert plain["dtype"] == full["dtype"] == "fp16" and plain["steps"] == full["steps"] == 3
+    assert plain["config"]["loss"] == full["config"]["loss"] == float(plain_arrs["fp16_loss"])
+    assert "bf16_leg" not in plain and "cpu_baseline" not in plain and "cpu_baseline_reference" not in plain
+    assert plain["config"]["logits_rel_l2_vs_fp32_reference"]["measured"] is None
+    assert runs["plain_dump"][0]["config"]["logits_rel_l2_vs_fp32_reference"]["measured"] is None
+    assert full["bf16_leg"]["dtype"] == "bf16" and full["cpu_baseline"]["value"] > 0
+    assert full["config"]["logits_rel_l2_vs_fp32_reference"]["measured"] < full["config"]["logits_rel_l2_vs_fp32_reference"]["tolerance_in_tests"]

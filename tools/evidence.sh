@@ -2,9 +2,9 @@
 # One entry point for every kind of evidence file under profiles/ (GPU box; `gpurun -- 'bash tools/evidence.sh <what> ...'`).
 # Everything is written under gpurun_out/ev/; copy what should be judged into profiles/rNN_<name>.
 #
-#   suite                     the whole GPU suite (--durations), smoke(), the driver's bench command
+#   suite                     the whole GPU suite (--durations), smoke(), the driver's bench command with --full
 #                             -> profiles/rNN_gpu_tests_final_full_suite.log, rNN_smoke_final.log, rNN_bench_4B_b24_fp16_bf16leg_final.json
-#   lines                     the other configurations' bench lines: 336M, VQ-VAE, cfg 1 (tiny-18M)
+#   lines                     the other configurations' bench lines with --full: 336M, VQ-VAE, cfg 1 (tiny-18M)
 #                             -> profiles/rNN_bench_336M_*.json, rNN_bench_vqvae_*.json, rNN_bench_cfg1_*.json
 #   kernel-stats [bench args] rocprofv3 --kernel-trace --stats of 5 steps of the bench command
 #                             -> profiles/rNN_bench_4B_b24_fp16_kernel_stats.csv
@@ -46,11 +46,11 @@ case $what in
 suite)
   ( time timeout 1500 python -m pytest tests -m gpu -q --durations=25 ) > $OUT/gpu_tests.log 2>&1; tail -40 $OUT/gpu_tests.log
   timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 | tee $OUT/smoke.log
-  ( time timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 ) > $OUT/bench_default.json 2> $OUT/bench_default.err
+  ( time timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full ) > $OUT/bench_default.json 2> $OUT/bench_default.err
   line $OUT/bench_default.json; grep -E "logits rel-L2|real" $OUT/bench_default.err ;;
 lines)
   for c in cogview-small-336M vqvae cogview-tiny-18M; do
-    timeout 900 python bench.py --config $c --steps 20 --warmup 5 > $OUT/bench_$c.json 2> $OUT/bench_$c.err; echo "== $c"; line $OUT/bench_$c.json
+    timeout 900 python bench.py --config $c --steps 20 --warmup 5 --full > $OUT/bench_$c.json 2> $OUT/bench_$c.err; echo "== $c"; line $OUT/bench_$c.json
   done ;;
 kernel-stats)
   rm -rf $OUT/kstats

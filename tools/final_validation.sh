@@ -3,7 +3,7 @@
 bash tools/evidence.sh suite
 R=${GRAFT_REPO_ROOT:-$(pwd)}; cd $R; OUT=$R/gpurun_out/ev
 for c in cogview-tiny-18M vqvae; do
-  timeout 900 python bench.py --config $c --steps 20 --warmup 5 > $OUT/bench_$c.json 2> $OUT/bench_$c.err
+  timeout 900 python bench.py --config $c --steps 20 --warmup 5 --full > $OUT/bench_$c.json 2> $OUT/bench_$c.err
   python - $OUT/bench_$c.json <<'P'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
