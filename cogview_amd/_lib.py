@@ -143,6 +143,8 @@ SIGNATURES = {
                                        _vp, _sz, _vp]),
     "cogv_ln_bwd_pair_workspace_bytes": (_sz, [_i, _i]),
     "cogv_ln_bwd_num_blocks": (_i, [_i]),
+    "cogv_ln_bwd_plan": (_i, [_i, _i, _i, _f, _i, _i, C.POINTER(C.c_int)]),
+    "cogv_ln_bwd_pair_plan": (_i, [_i, _i, _f, C.POINTER(C.c_int)]),
     "cogv_gemm_reserve_cus": (_i, [_i]),
     "cogv_attention_fwd": (_i, [C.POINTER(AttnDesc), _vp]),
     "cogv_attention_bwd": (_i, [C.POINTER(AttnDesc), _vp]),

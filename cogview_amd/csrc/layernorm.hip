@@ -10,14 +10,8 @@
 #include "common.cuh"
 #include "cogview_hip.h"
 
+#include <algorithm>
 #include <cstdlib>
-
-// rows in flight of the wide STREAM_IN backward (fp32 x, add_in, dx: 20 prefetch registers per row instead of 12).
-// h = 2560, 26112 rows (tools/r3/mb_ln_stream.py): two rows at 162 registers 171.6 us, four rows at 256 registers
-// (+12 B of scratch) 184.7 us.  COGV_LN_BWD_ROWS overrides at run time.
-#ifndef COGV_LN_BWD_STREAM_IN_ROWS
-#define COGV_LN_BWD_STREAM_IN_ROWS 2
-#endif
 
 namespace {
 
@@ -466,11 +460,9 @@ __global__ __launch_bounds__(1024) void ln_bwd_reduce_kernel(const float* partia
 
 // Forward grid: ONE resident round of workgroups, each wave looping over its rows (h = 2560: 152 registers = 3
 // workgroups per CU = 768; the former 4096 ran 5.3 rounds with a third-full last one: 47.4 -> 45.1 us plain,
-// 95.8 -> 84.2 us with the fused residual add; h = 1024: 1536 resident, same time as 4096).  COGV_LN_FWD_BLOCKS overrides.
+// 95.8 -> 84.2 us with the fused residual add; h = 1024: 1536 resident, same time as 4096).
 template <typename T, int NV, int MODE> void launch_fwd_m(const LnFwdArgs& a, int blocks, hipStream_t st) {
   static const int resident = [] {
-    const char* e = getenv("COGV_LN_FWD_BLOCKS");
-    if (e && atoi(e) > 0) return atoi(e);
     int per_cu = 0, dev = 0;
     hipDeviceProp_t prop;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, ln_fwd_kernel<T, NV, MODE>, 256, 0) != hipSuccess || per_cu < 1) return 4096;
@@ -485,51 +477,6 @@ template <typename T, int NV> void launch_fwd(const LnFwdArgs& a, int mode, int 
   else if (mode == COGV_LN_STREAM_OUT) launch_fwd_m<T, NV, 2>(a, blocks, st);
   else launch_fwd_m<T, NV, 0>(a, blocks, st);
 }
-inline int ln_bwd_stream_in_rows() {
-  static const int rows_env = [] { const char* e = getenv("COGV_LN_BWD_ROWS"); return e ? atoi(e) : 0; }();
-  return rows_env ? rows_env : COGV_LN_BWD_STREAM_IN_ROWS;
-}
-#ifndef COGV_LN_BWD_LEAN_DEFAULT
-#define COGV_LN_BWD_LEAN_DEFAULT 1
-#endif
-inline bool ln_bwd_lean() {
-  const char* e = getenv("COGV_LN_BWD_LEAN");        // read per launch (A/B runs, tests)
-  return e ? atoi(e) != 0 : COGV_LN_BWD_LEAN_DEFAULT != 0;
-}
-// rows in flight of the marked-zeros form at wide rows: 4 (the no-dropout geometry: one workgroup per CU) or 2 (the replay
-// form's geometry: lean, three workgroups per CU).  COGV_LN_BWD_MARKED_ROWS overrides.  h = 2560, 26112 rows, LN4' with column
-// sums (profiles/r06_ln_marked_zeros_rows_ab.log): replaying form 116.6 us (4.59 TB/s), marked two rows 125.0, marked four rows
-// 110.2 (4.85 TB/s), no dropout at all 107.5 -- the hash was never the bound, the rows in flight are.
-#ifndef COGV_LN_BWD_MARKED_ROWS_DEFAULT
-#define COGV_LN_BWD_MARKED_ROWS_DEFAULT 4
-#endif
-inline int ln_bwd_marked_rows() {
-  const char* e = getenv("COGV_LN_BWD_MARKED_ROWS");
-  return e ? atoi(e) : COGV_LN_BWD_MARKED_ROWS_DEFAULT;
-}
-template <typename T, int MODE> void launch_bwd_m(const LnBwdArgs& a, int blocks, hipStream_t st) {
-  const int nw = (a.h + 511) / 512;             // waves per row (h <= 4096 -> <= 8)
-  // wide rows with the dropout replay: two rows in flight at 128 registers (two workgroups per CU) beat four rows at
-  // 206 (one per CU) -- 112 vs 129 us at h = 2560; without the replay four rows and one workgroup per CU win (109 vs 116)
-  if (a.marked && a.thr16 && MODE != 1) {
-    if constexpr (MODE != 1) {
-      if (nw >= 4 && ln_bwd_marked_rows() == 4) hipLaunchKernelGGL((ln_bwd_kernel<T, 4, MODE, false, true>), dim3(blocks), dim3(nw * 64), 0, st, a);
-      else if (MODE == 2 && nw >= 4 && !a.add_in && ln_bwd_lean()) {
-        if constexpr (MODE == 2) hipLaunchKernelGGL((ln_bwd_kernel<T, 2, MODE, true, true>), dim3(blocks), dim3(nw * 64), 0, st, a);
-      } else if (nw >= 4) hipLaunchKernelGGL((ln_bwd_kernel<T, 2, MODE, false, true>), dim3(blocks), dim3(nw * 64), 0, st, a);
-      else hipLaunchKernelGGL((ln_bwd_kernel<T, 4, MODE, false, true>), dim3(blocks), dim3(nw * 64), 0, st, a);
-    }
-  } else if (MODE == 2 && nw >= 4 && a.thr16 && !a.add_in && ln_bwd_lean()) {
-    if constexpr (MODE == 2) hipLaunchKernelGGL((ln_bwd_kernel<T, 2, MODE, true>), dim3(blocks), dim3(nw * 64), 0, st, a);
-  } else if (nw >= 4 && (a.thr16 || (MODE == 1 && ln_bwd_stream_in_rows() == 2)))
-    hipLaunchKernelGGL((ln_bwd_kernel<T, 2, MODE>), dim3(blocks), dim3(nw * 64), 0, st, a);
-  else hipLaunchKernelGGL((ln_bwd_kernel<T, 4, MODE>), dim3(blocks), dim3(nw * 64), 0, st, a);
-}
-template <typename T> void launch_bwd(const LnBwdArgs& a, int mode, int blocks, hipStream_t st) {
-  if (mode == COGV_LN_STREAM_IN) launch_bwd_m<T, 1>(a, blocks, st);
-  else if (mode == COGV_LN_STREAM_OUT) launch_bwd_m<T, 2>(a, blocks, st);
-  else launch_bwd_m<T, 0>(a, blocks, st);
-}
 
 #define NV_SWITCH(FN, T, nv, ...)                          \
   switch (nv) {                                            \
@@ -543,23 +490,103 @@ template <typename T> void launch_bwd(const LnBwdArgs& a, int mode, int blocks, 
     default: FN<T, 8>(__VA_ARGS__); break;                 \
   }
 
+// Every environment switch of this file: the other sides of the backward's A/B pairs (the defaults are the measured winners).
+struct LnSwitches { int stream_in_rows; bool lean; int marked_rows, pair_blocks; };
+LnSwitches ln_switches() {
+  const auto env = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
+  // rows in flight of the wide STREAM_IN backward (fp32 x, add_in, dx: 20 prefetch registers per row instead of 12).  h = 2560,
+  // 26112 rows (tools/mb_ln_stream.py): two rows at 162 registers 171.6 us, four rows at 256 registers (+12 B of scratch) 184.7 us.
+  static const int stream_in_rows = env("COGV_LN_BWD_ROWS", 0);             // these two once per process (tools set them)
+  static const int pair_blocks = env("COGV_LN_BWD_PAIR_BLOCKS", 0);         // workgroups of the LN2' + LN3' pair: two per CU
+  // rows in flight of the marked-zeros form at wide rows: 4 (the no-dropout geometry: one workgroup per CU) or 2 (the replay
+  // form's geometry: lean, three workgroups per CU).  h = 2560, 26112 rows, LN4' with column sums
+  // (profiles/r06_ln_marked_zeros_rows_ab.log): replaying form 116.6 us (4.59 TB/s), marked two rows 125.0, marked four rows
+  // 110.2 (4.85 TB/s), no dropout at all 107.5 -- the hash was never the bound, the rows in flight are.
+  const int marked_rows = env("COGV_LN_BWD_MARKED_ROWS", 4);                // these two per launch (A/B runs, tests)
+  const bool lean = env("COGV_LN_BWD_LEAN", 1) != 0;                        // 0: the regular two-row form replays the dropout
+  return {stream_in_rows ? stream_in_rows : 2, lean, marked_rows, pair_blocks > 0 ? pair_blocks : 512};
+}
 
-}  // namespace
+inline uint32_t ln_thr16(float dropout_p) { return (uint32_t)(dropout_p * 65536.0f + 0.5f); }
 
-// Workgroups of the backward kernel: exactly ONE round of resident workgroups (each loops over its rows) measured best
-// at the wide rows -- h = 2560 (5 waves per workgroup): 256 workgroups of the four-row form (one per CU) 96 / 110 us
+// what one backward launch runs: the instantiation (R, LEAN, MARK of ln_bwd_kernel) and its geometry
+struct LnBwdPlan { int rows_in_flight; bool lean, marked; int blocks, threads; };
+// The one grid rule: a workgroup per `rows_per_wg` rows up to `cap`, the resident workgroups the form was tuned for, and never
+// more than cogv_ln_bwd_num_blocks(rows), which sizes the partial-sum workspace.
+int ln_bwd_grid(int rows, int rows_per_wg, int cap) {
+  return std::min({(rows + rows_per_wg - 1) / rows_per_wg, cap, cogv_ln_bwd_num_blocks(rows)});
+}
+
+// Form and grid of cogv_sandwich_ln_bwd[_marked].  Exactly ONE round of resident workgroups (each loops over its rows) measured
+// best at the wide rows -- h = 2560 (5 waves per workgroup): 256 workgroups of the four-row form (one per CU) 96 / 110 us
 // (plain / residual-gradient add) vs 101 / 115 with 512, and 512 of the two-row form (two per CU) for the dropout-replay
 // variant 112 vs 134 us; a third resident workgroup or a second round is 10-30 % slower.  h = 1024 (2 waves per
 // workgroup): 1024 workgroups 44 us vs 59 with 512, 79 with 256.
-static int ln_bwd_blocks(int rows, int h, bool dropout_replay /* or any other use of the two-row form */) {
-  static const int forced = [] { const char* e = getenv("COGV_LN_BWD_BLOCKS"); return e ? atoi(e) : 0; }();
-  const int nw = (h + 511) / 512;
-  int cap = nw >= 4 ? (dropout_replay ? 512 : 256) : 2560 / nw;
-  if (forced > 0) cap = forced > 1024 ? 1024 : forced;
-  else cap = cap < 256 ? 256 : (cap > 1024 ? 1024 : cap);
-  int b = (rows + 3) / 4;                       // 4 rows per workgroup iteration
-  return b < 1 ? 1 : (b > cap ? cap : b);
+LnBwdPlan ln_bwd_plan(int mode, int rows, int h, bool drop, bool marked, bool add_in) {
+  const LnSwitches sw = ln_switches();
+  const int nw = (h + 511) / 512;               // waves per row (h <= 4096 -> <= 8)
+  const bool wide = nw >= 4;
+  const bool lean_ok = mode == COGV_LN_STREAM_OUT && wide && drop && !add_in && sw.lean;
+  LnBwdPlan p{4, false, false, 0, 64 * nw};
+  // wide rows with the dropout replay: two rows in flight at 128 registers (two workgroups per CU) beat four rows at
+  // 206 (one per CU) -- 112 vs 129 us at h = 2560; without the replay four rows and one workgroup per CU win (109 vs 116)
+  if (marked && drop && mode != COGV_LN_STREAM_IN) {      // the marks live in a 16-bit x
+    p.marked = true;
+    if (wide && sw.marked_rows != 4) { p.rows_in_flight = 2; p.lean = lean_ok; }
+  } else if (lean_ok) { p.rows_in_flight = 2; p.lean = true; }
+  else if (wide && (drop || (mode == COGV_LN_STREAM_IN && sw.stream_in_rows == 2))) p.rows_in_flight = 2;
+  // One workgroup per 4 rows up to one resident round, whatever the rows in flight: two workgroups per CU for the two-row forms
+  // with dropout, else one (the two-row STREAM_IN form without dropout replay too: 256 workgroups 167 us vs 178 with 512 at
+  // h = 2560); the narrow rows' many small workgroups end at the workspace bound.  Lean: four waves per SIMD, three per CU.
+  const int cap = wide ? (p.rows_in_flight == 2 && drop ? 512 : 256) : 2560 / nw;
+  p.blocks = p.lean ? ln_bwd_grid(rows, 2, 768) : ln_bwd_grid(rows, 4, cap);
+  return p;
 }
+// the pair kernel: two rows in flight, two workgroups per CU, wide rows only
+LnBwdPlan ln_bwd_pair_plan(int rows, int h, bool drop) {
+  return LnBwdPlan{2, false, drop, ln_bwd_grid(rows, 2, ln_switches().pair_blocks), 64 * ((h + 511) / 512)};
+}
+
+// the shape / dropout arguments that the launching entry points and the plan queries refuse alike
+inline bool ln_bwd_args_ok(int mode, int rows, int h, float dropout_p) {
+  return mode >= 0 && mode <= 2 && rows > 0 && h > 0 && !(h & 7) && h <= 4096 && dropout_p >= 0.f && dropout_p < 1.f;
+}
+int ln_plan_out(const LnBwdPlan& p, int out[5]) {
+  out[0] = p.rows_in_flight, out[1] = p.lean, out[2] = p.marked, out[3] = p.blocks, out[4] = p.threads;
+  return COGV_OK;
+}
+template <typename T> void ln_bwd_reduce(const float* partial, int nblk, int h, void* dgamma, void* dbeta, void* colsum,
+                                         int accumulate, hipStream_t st) {
+  if (!dgamma && !dbeta && !colsum) return;
+  hipLaunchKernelGGL((ln_bwd_reduce_kernel<T>), dim3((h + 63) / 64, 3), dim3(1024), 0, st, partial, nblk, h, dgamma, dbeta, colsum, accumulate);
+}
+// The instantiated forms of ln_bwd_kernel, all of them; a plan outside this list is an error, never one more instantiation.
+constexpr int ln_form(int mode, int r, bool lean, bool mark) { return mode * 100 + r * 10 + lean * 2 + mark; }
+template <typename T> int ln_bwd_run(const LnBwdArgs& a, int mode, const LnBwdPlan& p, void* dgamma, void* dbeta, void* colsum,
+                                     int accumulate, hipStream_t st) {
+  switch (ln_form(mode, p.rows_in_flight, p.lean, p.marked)) {
+#define LN_FORM(MODE, R, LEAN, MARK) \
+  case ln_form(MODE, R, LEAN, MARK): hipLaunchKernelGGL((ln_bwd_kernel<T, R, MODE, LEAN, MARK>), dim3(p.blocks), dim3(p.threads), 0, st, a); break;
+    LN_FORM(0, 4, false, false) LN_FORM(0, 2, false, false) LN_FORM(0, 4, false, true) LN_FORM(0, 2, false, true)
+    LN_FORM(1, 4, false, false) LN_FORM(1, 2, false, false)
+    LN_FORM(2, 4, false, false) LN_FORM(2, 2, false, false) LN_FORM(2, 4, false, true) LN_FORM(2, 2, false, true)
+    LN_FORM(2, 2, true, false) LN_FORM(2, 2, true, true)
+#undef LN_FORM
+    default: return COGV_ERR_UNSUPPORTED;
+  }
+  ln_bwd_reduce<T>(a.partial, p.blocks, a.h, dgamma, dbeta, colsum, accumulate, st);
+  return cogv_check_launch();
+}
+template <typename T> int ln_bwd_pair_run(const LnPairArgs& a, const LnBwdPlan& p, void* dgamma2, void* dbeta2, void* dgamma3,
+                                          void* dbeta3, void* colsum, int accumulate, hipStream_t st) {
+  hipLaunchKernelGGL((ln_bwd_pair_kernel<T, 2>), dim3(p.blocks), dim3(p.threads), 0, st, a);
+  ln_bwd_reduce<T>(a.partial2, p.blocks, a.h, dgamma2, dbeta2, nullptr, accumulate, st);
+  ln_bwd_reduce<T>(a.partial3, p.blocks, a.h, dgamma3, dbeta3, colsum, accumulate, st);
+  return cogv_check_launch();
+}
+
+}  // namespace
+
 // upper bound of the workgroup count over all widths (sizes the partial-sum workspace)
 extern "C" int cogv_ln_bwd_num_blocks(int rows) {
   const int b = (rows + 3) / 4;
@@ -567,6 +594,16 @@ extern "C" int cogv_ln_bwd_num_blocks(int rows) {
 }
 extern "C" size_t cogv_ln_bwd_workspace_bytes(int rows, int h) {
   return (size_t)cogv_ln_bwd_num_blocks(rows) * 3 * (size_t)h * sizeof(float);      // sized for the largest block count
+}
+extern "C" int cogv_ln_bwd_plan(int stream_mode, int rows, int h, float dropout_p, int marked, int has_add_in, int out[5]) {
+  if (marked && stream_mode == COGV_LN_STREAM_IN) return COGV_ERR_ARG;
+  if (!ln_bwd_args_ok(stream_mode, rows, h, dropout_p)) return COGV_ERR_ARG;
+  return ln_plan_out(ln_bwd_plan(stream_mode, rows, h, ln_thr16(dropout_p) != 0, marked != 0, has_add_in != 0), out);
+}
+extern "C" int cogv_ln_bwd_pair_plan(int rows, int h, float dropout_p, int out[5]) {
+  if (!ln_bwd_args_ok(COGV_LN_ALL_T, rows, h, dropout_p)) return COGV_ERR_ARG;
+  if ((h + 511) / 512 < 4) return COGV_ERR_UNSUPPORTED;
+  return ln_plan_out(ln_bwd_pair_plan(rows, h, ln_thr16(dropout_p) != 0), out);
 }
 
 extern "C" int cogv_sandwich_ln_fwd(int dtype, const void* x, const void* gamma, const void* beta, const void* residual,
@@ -593,41 +630,17 @@ static int ln_bwd_impl(int dtype, const void* dy, const void* x, const void* gam
                        uint64_t seed, uint64_t stream_id, void* workspace, size_t workspace_bytes,
                        int stream_mode, void* stream, int marked) {
   if (dtype != COGV_F16 && dtype != COGV_BF16) return COGV_ERR_UNSUPPORTED;
-  if (stream_mode < 0 || stream_mode > 2) return COGV_ERR_ARG;
-  if (rows <= 0 || h <= 0 || (h & 7) || h > 4096) return COGV_ERR_ARG;
+  if (!ln_bwd_args_ok(stream_mode, rows, h, dropout_p)) return COGV_ERR_ARG;
   if (!dy || !x || !gamma || !mean || !rstd || !dx || !workspace) return COGV_ERR_ARG;
   if (workspace_bytes < cogv_ln_bwd_workspace_bytes(rows, h)) return COGV_ERR_ARG;
   if (((uintptr_t)dy | (uintptr_t)x | (uintptr_t)gamma | (uintptr_t)dx | (uintptr_t)add_in) & 15) return COGV_ERR_ARG;
-  if (!(dropout_p >= 0.f && dropout_p < 1.f)) return COGV_ERR_ARG;
-  LnBwdArgs a;
-  a.dy = dy; a.x = x; a.gamma = gamma; a.mean = mean; a.rstd = rstd; a.add_in = add_in; a.dx = dx;
-  a.partial = reinterpret_cast<float*>(workspace); a.rows = rows; a.h = h; a.want_colsum = colsum ? 1 : 0;
-  a.seed = seed; a.stream_id = stream_id; a.marked = marked;
-  a.thr16 = (uint32_t)(dropout_p * 65536.0f + 0.5f);
-  a.keep_scale = 65536.0f / (65536.0f - (float)a.thr16);
-  // (the two-row STREAM_IN form without dropout replay keeps the one-workgroup-per-CU cap: 256 workgroups 167 us vs 178
-  // with 512 at h = 2560, tools/r3/exp1.sh)
-  int blocks = ln_bwd_blocks(rows, h, a.thr16 != 0);
-  if (marked && a.thr16 && (h + 511) / 512 >= 4 && ln_bwd_marked_rows() == 4) blocks = ln_bwd_blocks(rows, h, false);
-  else if (stream_mode == COGV_LN_STREAM_OUT && a.thr16 && !add_in && (h + 511) / 512 >= 4 && ln_bwd_lean()) {
-    // the lean dropout-replay form: three resident workgroups per CU (COGV_LN_BWD_BLOCKS still overrides)
-    static const int forced = [] { const char* e = getenv("COGV_LN_BWD_BLOCKS"); return e ? atoi(e) : 0; }();
-    if (forced <= 0) {
-      const int want = (rows + 1) / 2, cap = cogv_ln_bwd_num_blocks(rows);      // (the partial-sum workspace is sized by `cap`)
-      blocks = want < 768 ? want : 768;
-      if (blocks > cap) blocks = cap;
-    }
-  }
+  const uint32_t thr16 = ln_thr16(dropout_p);
+  const LnBwdArgs a{dy, x, gamma, mean, rstd, add_in, dx, reinterpret_cast<float*>(workspace), rows, h, colsum ? 1 : 0,
+                    seed, stream_id, thr16, 65536.0f / (65536.0f - (float)thr16), marked};
+  const LnBwdPlan plan = ln_bwd_plan(stream_mode, rows, h, thr16 != 0, marked != 0, add_in != nullptr);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == COGV_F16) launch_bwd<f16_t>(a, stream_mode, blocks, st); else launch_bwd<bf16_t>(a, stream_mode, blocks, st);
-  if (dgamma || dbeta || colsum) {
-    dim3 grid((h + 63) / 64, 3);
-    if (dtype == COGV_F16)
-      hipLaunchKernelGGL((ln_bwd_reduce_kernel<f16_t>), grid, dim3(1024), 0, st, a.partial, blocks, h, dgamma, dbeta, colsum, accumulate_param_grads);
-    else
-      hipLaunchKernelGGL((ln_bwd_reduce_kernel<bf16_t>), grid, dim3(1024), 0, st, a.partial, blocks, h, dgamma, dbeta, colsum, accumulate_param_grads);
-  }
-  return cogv_check_launch();
+  return dtype == COGV_F16 ? ln_bwd_run<f16_t>(a, stream_mode, plan, dgamma, dbeta, colsum, accumulate_param_grads, st)
+                           : ln_bwd_run<bf16_t>(a, stream_mode, plan, dgamma, dbeta, colsum, accumulate_param_grads, st);
 }
 
 extern "C" int cogv_sandwich_ln_bwd(int dtype, const void* dy, const void* x, const void* gamma, const float* mean,
@@ -656,37 +669,18 @@ extern "C" int cogv_sandwich_ln_bwd_pair(int dtype, const void* dc, const void* 
                                          void* dgamma3, void* dbeta3, void* colsum, int accumulate_param_grads, int rows, int h,
                                          float dropout_p, void* workspace, size_t workspace_bytes, void* stream) {
   if (dtype != COGV_F16 && dtype != COGV_BF16) return COGV_ERR_UNSUPPORTED;
-  if (rows <= 0 || h <= 0 || (h & 7) || h > 4096) return COGV_ERR_ARG;
+  if (!ln_bwd_args_ok(COGV_LN_ALL_T, rows, h, dropout_p)) return COGV_ERR_ARG;
   if (!dc || !y || !gamma2 || !mean2 || !rstd2 || !dout || !dy || !ao || !gamma3 || !mean3 || !rstd3 || !d_ao || !workspace) return COGV_ERR_ARG;
   if (workspace_bytes < cogv_ln_bwd_pair_workspace_bytes(rows, h)) return COGV_ERR_ARG;
   if (((uintptr_t)dc | (uintptr_t)y | (uintptr_t)gamma2 | (uintptr_t)dout | (uintptr_t)dy | (uintptr_t)ao | (uintptr_t)gamma3 | (uintptr_t)d_ao) & 15)
     return COGV_ERR_ARG;
-  if (!(dropout_p >= 0.f && dropout_p < 1.f)) return COGV_ERR_ARG;
-  const int nw = (h + 511) / 512;
-  if (nw < 4) return COGV_ERR_UNSUPPORTED;        // narrow rows: the two launches (their many-workgroup geometry) stay
-  LnPairArgs a;
-  a.dc = dc; a.y = y; a.gamma2 = gamma2; a.mean2 = mean2; a.rstd2 = rstd2; a.dout = dout; a.dy = dy;
-  a.ao = ao; a.gamma3 = gamma3; a.mean3 = mean3; a.rstd3 = rstd3; a.d_ao = d_ao;
-  a.partial2 = reinterpret_cast<float*>(workspace);
-  a.partial3 = a.partial2 + (size_t)cogv_ln_bwd_num_blocks(rows) * 3 * (size_t)h;
-  a.rows = rows; a.h = h;
-  const uint32_t thr16 = (uint32_t)(dropout_p * 65536.0f + 0.5f);
-  a.marked = thr16 != 0; a.keep_scale = 65536.0f / (65536.0f - (float)thr16);
-  static const int forced = [] { const char* e = getenv("COGV_LN_BWD_PAIR_BLOCKS"); return e ? atoi(e) : 0; }();
-  int blocks = forced > 0 ? forced : 512;
-  const int want = (rows + 1) / 2, cap = cogv_ln_bwd_num_blocks(rows);
-  if (blocks > want) blocks = want;
-  if (blocks > cap) blocks = cap;
+  if ((h + 511) / 512 < 4) return COGV_ERR_UNSUPPORTED;      // narrow rows: the two launches (their many-workgroup geometry) stay
+  const uint32_t thr16 = ln_thr16(dropout_p);
+  float* const partial = reinterpret_cast<float*>(workspace);
+  const LnPairArgs a{dc, y, gamma2, mean2, rstd2, dout, dy, ao, gamma3, mean3, rstd3, d_ao, partial,
+                     partial + (size_t)cogv_ln_bwd_num_blocks(rows) * 3 * (size_t)h, rows, h, thr16 != 0, 65536.0f / (65536.0f - (float)thr16)};
+  const LnBwdPlan plan = ln_bwd_pair_plan(rows, h, thr16 != 0);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == COGV_F16) hipLaunchKernelGGL((ln_bwd_pair_kernel<f16_t, 2>), dim3(blocks), dim3(nw * 64), 0, st, a);
-  else hipLaunchKernelGGL((ln_bwd_pair_kernel<bf16_t, 2>), dim3(blocks), dim3(nw * 64), 0, st, a);
-  dim3 grid((h + 63) / 64, 3);
-  if (dtype == COGV_F16) {
-    if (dgamma2 || dbeta2) hipLaunchKernelGGL((ln_bwd_reduce_kernel<f16_t>), grid, dim3(1024), 0, st, a.partial2, blocks, h, dgamma2, dbeta2, (void*)nullptr, accumulate_param_grads);
-    if (dgamma3 || dbeta3 || colsum) hipLaunchKernelGGL((ln_bwd_reduce_kernel<f16_t>), grid, dim3(1024), 0, st, a.partial3, blocks, h, dgamma3, dbeta3, colsum, accumulate_param_grads);
-  } else {
-    if (dgamma2 || dbeta2) hipLaunchKernelGGL((ln_bwd_reduce_kernel<bf16_t>), grid, dim3(1024), 0, st, a.partial2, blocks, h, dgamma2, dbeta2, (void*)nullptr, accumulate_param_grads);
-    if (dgamma3 || dbeta3 || colsum) hipLaunchKernelGGL((ln_bwd_reduce_kernel<bf16_t>), grid, dim3(1024), 0, st, a.partial3, blocks, h, dgamma3, dbeta3, colsum, accumulate_param_grads);
-  }
-  return cogv_check_launch();
+  return dtype == COGV_F16 ? ln_bwd_pair_run<f16_t>(a, plan, dgamma2, dbeta2, dgamma3, dbeta3, colsum, accumulate_param_grads, st)
+                           : ln_bwd_pair_run<bf16_t>(a, plan, dgamma2, dbeta2, dgamma3, dbeta3, colsum, accumulate_param_grads, st);
 }

@@ -484,15 +484,11 @@ def sandwich_ln_bwd(dy, x, gamma, mean, rstd, add_in=None, dropout=None, dgamma=
         raise L.CogviewHipError("Sandwich-LN backward: marked zeros need a 16-bit x")
     label = lambda: "ln_bwd " + _LN_MODE_NAME[mode] + ((" + dropout from marked zeros" if marked else " + dropout replay") if p > 0.0 else "") + \
         (" + add" if a2 is not None else "")
+    # the marked entry point is the replaying one without (seed, stream)
+    name, replay = ("cogv_sandwich_ln_bwd_marked", ()) if marked else ("cogv_sandwich_ln_bwd", (int(seed), int(sid)))
     with timed_launch("layernorm", 0.0, nb, label):
-        if marked:
-            L.check(lib.cogv_sandwich_ln_bwd_marked(dt_code(gamma), _p(dy2), _p(x2), _p(gamma), _p(mean), _p(rstd), _p(a2), _p(dx),
-                                                    _p(dgamma), _p(dbeta), _p(colsum), int(accumulate), rows, h, float(p),
-                                                    _p(ws), ws.numel(), mode, _stream()), "cogv_sandwich_ln_bwd_marked")
-            return dx.view(x.shape)
-        L.check(lib.cogv_sandwich_ln_bwd(dt_code(gamma), _p(dy2), _p(x2), _p(gamma), _p(mean), _p(rstd), _p(a2), _p(dx),
-                                         _p(dgamma), _p(dbeta), _p(colsum), int(accumulate), rows, h, float(p), int(seed),
-                                         int(sid), _p(ws), ws.numel(), mode, _stream()), "cogv_sandwich_ln_bwd")
+        L.check(getattr(lib, name)(dt_code(gamma), _p(dy2), _p(x2), _p(gamma), _p(mean), _p(rstd), _p(a2), _p(dx), _p(dgamma), _p(dbeta),
+                                   _p(colsum), int(accumulate), rows, h, float(p), *replay, _p(ws), ws.numel(), mode, _stream()), name)
     return dx.view(x.shape)
 
 

@@ -175,7 +175,8 @@ int cogv_sandwich_ln_bwd_marked(int dtype, const void* dy, const void* x, const 
  * dy still goes to memory (LN1' adds it later) but is not read back: 18 instead of 22 bytes per element for the pair.  dy and
  * d_ao are bit-identical to cogv_sandwich_ln_bwd(STREAM_IN, add_in = dout) followed by cogv_sandwich_ln_bwd_marked(STREAM_OUT);
  * the five column reductions (dgamma2, dbeta2, dgamma3, dbeta3, colsum of d_ao; T, [h], any may be NULL) equal theirs up to the
- * fp32 summation order.  h >= 2048 (narrower rows: COGV_ERR_UNSUPPORTED, issue the two launches). */
+ * fp32 summation order.  1536 < h <= 4096, h % 8 == 0: at least four waves per row (narrower rows: COGV_ERR_UNSUPPORTED, issue
+ * the two launches). */
 int cogv_sandwich_ln_bwd_pair(int dtype, const void* dc, const void* y, const void* gamma2, const float* mean2,
                               const float* rstd2, const void* dout, void* dy, void* dgamma2, void* dbeta2,
                               const void* ao, const void* gamma3, const float* mean3, const float* rstd3, void* d_ao,
@@ -184,6 +185,11 @@ int cogv_sandwich_ln_bwd_pair(int dtype, const void* dc, const void* y, const vo
 size_t cogv_ln_bwd_pair_workspace_bytes(int rows, int h);
 size_t cogv_ln_bwd_workspace_bytes(int rows, int h);
 int cogv_ln_bwd_num_blocks(int rows);   /* upper bound of the backward kernel's workgroup count (workspace sizing) */
+/* Host-only queries (no device is touched): what cogv_sandwich_ln_bwd[_marked] (marked = 1: the _marked entry point) and
+ * cogv_sandwich_ln_bwd_pair would launch for these arguments, from the function the launch itself uses.  out = { rows in flight,
+ * lean form, mask from marked zeros, workgroups, threads per workgroup }; the argument errors of the launching entry points. */
+int cogv_ln_bwd_plan(int stream_mode, int rows, int h, float dropout_p, int marked, int has_add_in, int out[5]);
+int cogv_ln_bwd_pair_plan(int rows, int h, float dropout_p, int out[5]);
 
 /* ------------------------------------------------------------------ attention (head dim 64)
  * replaces standard_attention, mpu/sparse_transformer.py:652-673, plus the head permutes at :112-120,:159.
