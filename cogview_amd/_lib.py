@@ -148,6 +148,7 @@ SIGNATURES = {
     "cogv_gemm_reserve_cus": (_i, [_i]),
     "cogv_attention_fwd": (_i, [C.POINTER(AttnDesc), _vp]),
     "cogv_attention_bwd": (_i, [C.POINTER(AttnDesc), _vp]),
+    "cogv_attention_plan": (_i, [C.POINTER(AttnDesc), _i, C.POINTER(C.c_int)]),
     "cogv_gemv_ln": (_i, [C.POINTER(GemmDesc), C.POINTER(LnPrologue), _vp]),
     "cogv_gemv_attn": (_i, [C.POINTER(GemmDesc), _vp, _i, _i, _vp]),
     "cogv_attention_decode": (_i, [C.POINTER(AttnDecodeDesc), _vp]),

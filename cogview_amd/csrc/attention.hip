@@ -50,29 +50,47 @@ constexpr int TILE = 8192;      // one 64 x 64 16-bit tile
 #define COGV_ATTN_STAGES 2
 #endif
 constexpr int NSTG = COGV_ATTN_STAGES;
-// dK.dV register diet (round 5 experiment, profiles/r05_attention_dkdv_diet_ab.log): the training instantiation needs 226
-// registers = two waves per SIMD.  COGV_DKDV_AHEAD=0 drops the ahead-of-time request of the transposed dO / Q fragments (-32),
-// COGV_DKDV_VLDS=1 keeps the V fragments of the wave's own keys in LDS behind the ring instead of in registers (-16; +16 KiB
-// per workgroup: three still fit a CU with the two-stage ring), COGV_DKDV_WAVES=3 asks the allocator for three waves per SIMD
-// (168 registers, 24 B of spill outside the asm-read windows).  The runtime then grants three workgroups per CU -- and the
-// kernel is NOT faster: backward 1018-1031 us against 1000-1013 with two waves (same call), the 4B step unchanged.  A third
-// wave per SIMD does not cover the parked cycles; the defaults (two waves, fragments requested ahead) stay.
-#ifndef COGV_DKDV_KW_PITCH
-#define COGV_DKDV_KW_PITCH 272
-#endif
-#ifndef COGV_DKDV_AHEAD
-#define COGV_DKDV_AHEAD 1
-#endif
-#ifndef COGV_DKDV_VLDS
-#define COGV_DKDV_VLDS 0
-#endif
-#ifndef COGV_DKDV_WAVES
-#define COGV_DKDV_WAVES 2
-#endif
-constexpr int DKDV_OWN_V = COGV_DKDV_VLDS ? 4 * 4 * 64 * 16 : 0;      // bytes of the waves' own V fragments behind the ring
+// dK.dV register diet (round 5 experiment, profiles/r05_attention_dkdv_diet_ab.log; the code is in commit 1568d58 and before, behind
+// the build switches COGV_DKDV_AHEAD / COGV_DKDV_VLDS / COGV_DKDV_WAVES): the training instantiation needs 226 registers = two
+// waves per SIMD.  Not requesting the transposed dO / Q fragments ahead of time saves 32 of them, keeping the V fragments of the
+// wave's own keys in LDS behind the ring instead of in registers another 16 (+16 KiB per workgroup: three still fit a CU with the
+// two-stage ring), and __launch_bounds__(256, 3) then gives 168 registers with 24 B of spill outside the asm-read windows.  The
+// runtime then grants three workgroups per CU -- and the kernel is NOT faster: backward 1018-1031 us against 1000-1013 with two
+// waves (same call), the 4B step unchanged.  A third wave per SIMD does not cover the parked cycles; two waves and fragments
+// requested ahead are what the kernel does, and the switches are gone.
 static_assert(NSTG == 2 || NSTG == 3, "ring of two or three stages");
 constexpr int COLSUM_SMEM = (128 * 68 + 256) * 4;      // tile_colsum's scratch (the ring is free by then)
-constexpr int ring_bytes(int stage, bool colsum) { return (colsum && NSTG * stage < COLSUM_SMEM) ? COLSUM_SMEM : NSTG * stage; }
+
+// The byte layout of ONE ring stage, per kernel.  The kernel takes its offsets, the stage size and the DMA count of its counted
+// wait from here; the host (attn_plan) and tools/probes/attn_occupancy.hip take the dynamic LDS size.
+//   SIZE           bytes of a stage; INDEX = NSTG * SIZE: where the index table of the gathered / sparse forms starts
+//   DMAS           LDS-DMA instructions per thread and stage = what the kernel's `issue` lambda emits (dma_tile: DMA_TILE,
+//                  dma_stat or a keep word: 1; a static_assert beside each lambda restates the sum); wait_vmcnt<(NSTG - 2) * DMAS>
+//   dynamic_lds(n) the ring -- raised to tile_colsum's scratch where the kernel may run it in the ring's place (COLSUM) -- plus an
+//                  index table of n slots rounded to 16 bytes (n = 0: none)
+constexpr int DMA_TILE = 2;
+template <int SIZE_, int DMAS_, bool COLSUM_> struct RingStage {
+  static constexpr int SIZE = SIZE_, DMAS = DMAS_, INDEX = NSTG * SIZE_;
+  static constexpr int dynamic_lds(int index_slots) {
+    return ((COLSUM_ && INDEX < COLSUM_SMEM) ? COLSUM_SMEM : INDEX) + ((index_slots * 4 + 15) / 16) * 16;
+  }
+};
+// forward: K tile | V tile
+struct FwdStage : RingStage<2 * TILE, 2 * DMA_TILE, false> { static constexpr int K = 0, V = TILE; };
+// dQ: K tile | V tile | with stored keep bits (KB): one segment of 64 keep words per wave
+constexpr int DQ_KW_PITCH = 256;
+template <bool KB> struct DqStage : RingStage<2 * TILE + (KB ? 4 * DQ_KW_PITCH : 0), 2 * DMA_TILE + (KB ? 1 : 0), true> {
+  static constexpr int K = 0, V = TILE, KW = 2 * TILE, KW_PITCH = DQ_KW_PITCH;
+};
+// dK.dV: Q tile | dO tile | LSE[64] (KB: -LSE log2 e) | -D[64] | the dropout row keys RK[64], or with stored keep bits (KB) four
+// segments of 64 keep words.  KW_PITCH, the pitch of those segments: 272 instead of 256 (round 6): a lane group reads two segments
+// in one ds_read_b128 (its key's bit 2 selects which), and at a 256-byte pitch the two hit the same banks -- the 12 % LDS
+// bank-conflict cycles of this kernel alone among the three (profiles/r05_attention_pmc.txt)
+constexpr int DKDV_KW_PITCH = 272;
+template <bool KB> struct DkdvStage : RingStage<2 * TILE + 512 + (KB ? 4 * DKDV_KW_PITCH : 256), 2 * DMA_TILE + 3, true> {
+  static constexpr int Q = 0, DO = TILE, LSE = 2 * TILE, D = LSE + 256;
+  static constexpr int RK = D + 256, KW = D + 256, KW_PITCH = DKDV_KW_PITCH;      // one region: RK exists without KB, KW with it
+};
 
 struct AttnArgs {
   const void* q; const void* k; const void* v; void* o;        // forward
@@ -132,7 +150,7 @@ template <typename T>
 __device__ __forceinline__ void dma_tile(const T* base, long long rs, int row0, int nrows, char* lds, int wave, int lane,
                                          const int* lds_index = nullptr) {
 #pragma unroll
-  for (int i = 0; i < 2; ++i) {
+  for (int i = 0; i < DMA_TILE; ++i) {
     const int piece = wave + 4 * i;
     const int row = piece * 8 + (lane >> 3);
     const int c = (lane & 7) ^ aswz(row);
@@ -208,6 +226,9 @@ __device__ __forceinline__ bool visible(int q, int key, int off, int sep_k) { re
 // raw v_exp_f32 (2^x): no denormal-range fix-up sequence (softmax terms that small are zero anyway)
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 
+// accumulator element e of a 32x32 fragment <-> index 4 fg + elem_idx(e) along the register axis (keys in forward / dQ, queries in dK.dV)
+__device__ __forceinline__ constexpr int elem_idx(int e) { return (e & 3) + 8 * (e >> 2); }
+
 // Masking of one 32-element accumulator fragment whose element e has index base + (e&3) + 8*(e>>2) along the
 // masked axis.  `lim` = largest visible index relative to `base` (visible iff rel <= lim) and `bound` = number of
 // valid indices relative to `base`; both are per-lane scalars, the per-element offsets are compile-time constants.
@@ -215,7 +236,7 @@ __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_ex
 __device__ __forceinline__ void mask_frag(f32x16& a, int lim, int lim_sep, int bound, float masked_raw) {
 #pragma unroll
   for (int e = 0; e < 16; ++e) {
-    const int rel = (e & 3) + 8 * (e >> 2);
+    const int rel = elem_idx(e);
     float v = a[e];
     v = (rel <= lim || rel < lim_sep) ? v : masked_raw;     // reference: score*M - 10000*(1-M)
     v = (rel < bound) ? v : -INFINITY;                       // padding beyond the sequence: not a key at all
@@ -326,14 +347,77 @@ __device__ __forceinline__ void tile_colsum(const float (&vals)[2][16], float* l
 }
 
 // =====================================================================================================
+// What the two lane = query kernels (forward, dQ) share: the index table and slot attributes of the gathered / sparse forms, the
+// mask tensor, the masking at the diagonal and the sequence end.
+// =====================================================================================================
+// gathered form (sparse_attention_inference, mpu/sparse_transformer.py:727-750): key slot j is row kv_index[b][j] of K and V; the
+// table (<= 4096 slots) is staged once behind the ring.  Returns nullptr when there is none.
+template <bool IDX> __device__ __forceinline__ int* stage_index_table(const AttnArgs& p, int b, int gblk, char* behind_ring) {
+  if (!(IDX && p.kv_index)) return nullptr;
+  int* lidx = reinterpret_cast<int*>(behind_ring);
+  const int* gi = p.kv_index + (long long)b * p.kv_index_bs + (long long)gblk * p.kv_index_gs;
+  for (int i = threadIdx.x; i < p.s_k; i += NT) lidx[i] = gi[i];
+  __syncthreads();
+  return lidx;
+}
+// slot attributes of key block kb, one slot per lane, as lane masks: masked flag (bit 31 of the index entry) and "is a pivot"
+// (training form only: sp_npiv = 0 otherwise)
+struct SlotAttrs { unsigned long long masked, pivot; };
+__device__ __forceinline__ SlotAttrs slot_attrs(const int* lidx, int kb, int lane, const AttnArgs& p) {
+  int raw;
+  const uint32_t ia = (uint32_t)(uintptr_t)(lidx + min(kb * 64 + lane, p.s_k - 1));
+  asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(raw) : "v"(ia) : "memory");
+  SlotAttrs a;
+  a.masked = __ballot(raw < 0); a.pivot = __ballot(kb * 64 + lane < p.sp_npiv);
+  return a;
+}
+// ... applied to the fragment of the block's 32-key half sb: a masked slot takes the masked value, a pivot the bias (raw scores)
+__device__ __forceinline__ void apply_slot_attrs(f32x16& s, const SlotAttrs& a, int sb, int fg, float masked_raw, float bias_raw) {
+  const uint32_t fm = (uint32_t)(a.masked >> (32 * sb)) >> (4 * fg), pm = (uint32_t)(a.pivot >> (32 * sb)) >> (4 * fg);
+#pragma unroll
+  for (int e = 0; e < 16; ++e) {
+    const int bit = elem_idx(e);
+    float v = s[e];
+    v = ((fm >> bit) & 1u) ? masked_raw : v;
+    v += ((pm >> bit) & 1u) ? bias_raw : 0.f;
+    s[e] = v;
+  }
+}
+// arbitrary mask tensor, the row of query myq: raw' = raw * M + (-10000 / scale) * (1 - M) on the 32-key fragment that starts at key
+// `kfirst`; mk returns the multipliers (d raw = d raw' * M in the dQ kernel)
+template <typename T> __device__ __forceinline__ void apply_mask_tensor(f32x16& s, float (&mk)[16], const AttnArgs& p, int b, int myq,
+                                                                        int kfirst, int fg, float masked_raw) {
+  const T* mrow = reinterpret_cast<const T*>(p.mask) + (long long)b * p.mask_bs + (long long)min(myq, p.s_q - 1) * p.s_k;
+#pragma unroll
+  for (int e = 0; e < 16; ++e) {
+    const int key = kfirst + 4 * fg + elem_idx(e);
+    mk[e] = HT<T>::to_f(mrow[min(key, p.s_k - 1)]);
+    s[e] = fmaf(s[e], mk[e], masked_raw * (1.f - mk[e]));
+  }
+}
+// Masking at the diagonal and the sequence end of NF consecutive 32-key fragments that start at key kfirst: one wave-uniform
+// test for all of them (do they touch the diagonal of the wave's queries q0w .. or the end of the keys?), then element by element
+template <int NF> __device__ __forceinline__ void mask_edge(f32x16* s, int kfirst, int q0w, int myq, int off, int fg, const AttnArgs& p,
+                                                            float masked_raw) {
+  const bool all_visible = (kfirst + (32 * NF - 1) <= q0w + off) || (kfirst + (32 * NF - 1) < p.sep_k);
+  if (!all_visible || kfirst + 32 * NF > p.s_k) {
+#pragma unroll
+    for (int sb = 0; sb < NF; ++sb) {
+      const int base = kfirst + sb * 32 + 4 * fg;
+      mask_frag(s[sb], myq + off - base, p.sep_k - base, p.s_k - base, masked_raw);
+    }
+  }
+}
+
+// =====================================================================================================
 // forward: grid (ceil(s_q/128), H, B); wave w owns queries q0 + 32w .. +31.  Ring stage = K tile | V tile.
 // =====================================================================================================
 template <typename T, bool IDX, int DROP>       // DROP: 1 / 0 = dropout on / off at compile time, -1 = decided by p.thr16,
                                                 //       2 = on, and the keep bits are stored in p.keepbits for the backward pass
 __global__ __launch_bounds__(NT, 2) void attn_fwd_kernel(const AttnArgs p) {
   const bool drop = DROP < 0 ? (p.thr16 != 0u) : (DROP != 0);
-  extern __shared__ __attribute__((aligned(16))) char smem[];   // 3 stages x 16 KiB
-  constexpr int STAGE = 2 * TILE, LPT = 4;
+  extern __shared__ __attribute__((aligned(16))) char smem[];   // NSTG stages of K | V
+  using L = FwdStage;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int fr = lane & 31, fg = lane >> 5;
@@ -378,31 +462,24 @@ __global__ __launch_bounds__(NT, 2) void attn_fwd_kernel(const AttnArgs p) {
   const uint32_t loff[2] = {tr_lane_off(0, lane) ^ tr_lane_fix(lane), tr_lane_off(1, lane) ^ tr_lane_fix(lane)};
   const uint32_t smem_addr = (uint32_t)(uintptr_t)smem;
 
-  // gathered form (sparse_attention_inference, mpu/sparse_transformer.py:727-750): key slot j is row kv_index[b][j] of
-  // K and V; the table (<= 4096 slots) is staged once behind the ring
-  int* lidx = nullptr;
-  if (IDX && p.kv_index) {
-    lidx = reinterpret_cast<int*>(smem + NSTG * STAGE);
-    const int* gi = p.kv_index + (long long)b * p.kv_index_bs + (long long)gblk * p.kv_index_gs;
-    for (int i = threadIdx.x; i < p.s_k; i += NT) lidx[i] = gi[i];
-    __syncthreads();
-  }
+  int* const lidx = stage_index_table<IDX>(p, b, gblk, smem + L::INDEX);
   const float sp_bias_raw = spw ? p.sp_bias / p.scale : 0.f;      // added to RAW scores of pivot slots
   auto issue = [&](int kb, int st) {
-    dma_tile<T>(K, p.k_rs, kb * 64, p.s_k, smem + st * STAGE, wave, lane, lidx);
-    dma_tile<T>(V, p.v_rs, kb * 64, p.s_k, smem + st * STAGE + TILE, wave, lane, lidx);
+    dma_tile<T>(K, p.k_rs, kb * 64, p.s_k, smem + st * L::SIZE + L::K, wave, lane, lidx);
+    dma_tile<T>(V, p.v_rs, kb * 64, p.s_k, smem + st * L::SIZE + L::V, wave, lane, lidx);
   };
+  static_assert(L::DMAS == 2 * DMA_TILE, "issue(): K tile, V tile");
   // DROP == 2: this lane's keep word of key block kb goes to kwp[kb * 2 * s_q]
   uint32_t* const kwp = DROP == 2 ? p.keepbits + ((((long long)b * p.H + head) * ((p.s_k + 63) >> 6)) * 2 + fg) * p.s_q + min(myq, p.s_q - 1) : nullptr;
   if (nkb > 0) { issue(0, 0); if (NSTG > 2) issue(nkb > 1 ? 1 : 0, 1); }
   int st = 0;
   for (int kb = 0; kb < nkb; ++kb) {
-    wait_vmcnt<(NSTG - 2) * LPT>();
+    wait_vmcnt<(NSTG - 2) * L::DMAS>();
     __builtin_amdgcn_s_barrier();
     issue(min(kb + NSTG - 1, nkb - 1), st == 0 ? NSTG - 1 : st - 1);
     if (kb * 64 < kend_w) {
-      const char* lk = smem + st * STAGE;
-      const uint32_t lv = smem_addr + st * STAGE + TILE;
+      const char* lk = smem + st * L::SIZE + L::K;
+      const uint32_t lv = smem_addr + st * L::SIZE + L::V;
       f32x16 sacc[2];
 #pragma unroll
       for (int sb = 0; sb < 2; ++sb) {
@@ -416,46 +493,19 @@ __global__ __launch_bounds__(NT, 2) void attn_fwd_kernel(const AttnArgs p) {
       TrRaw vr[2][2];
       tr_frags_issue<T, 0>(lv, loff, vr);
       if (IDX && lidx) {
-        // slot attributes of this block, one slot per lane: masked flag (bit 31 of the index entry; honoured in both
-        // gathered forms -- a decode step over a fixed-capacity key/value cache flags the slots not written yet) and
-        // "is a pivot" (training form only: sp_npiv = 0 otherwise)
-        int raw;
-        const uint32_t ia = (uint32_t)(uintptr_t)(lidx + min(kb * 64 + lane, p.s_k - 1));
-        asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(raw) : "v"(ia) : "memory");
-        const unsigned long long mflag = __ballot(raw < 0), mpiv = __ballot(kb * 64 + lane < p.sp_npiv);
+        // the slot flags are honoured in BOTH gathered forms here (the dQ kernel: training form only) -- a decode step over a
+        // fixed-capacity key/value cache flags the slots not written yet
+        const SlotAttrs sa = slot_attrs(lidx, kb, lane, p);
 #pragma unroll
-        for (int sb = 0; sb < 2; ++sb) {
-          const uint32_t fm = (uint32_t)(mflag >> (32 * sb)) >> (4 * fg), pm = (uint32_t)(mpiv >> (32 * sb)) >> (4 * fg);
-#pragma unroll
-          for (int e = 0; e < 16; ++e) {
-            const int bit = (e & 3) + 8 * (e >> 2);
-            float v = sacc[sb][e];
-            v = ((fm >> bit) & 1u) ? masked_raw : v;
-            v += ((pm >> bit) & 1u) ? sp_bias_raw : 0.f;
-            sacc[sb][e] = v;
-          }
-        }
+        for (int sb = 0; sb < 2; ++sb) apply_slot_attrs(sacc[sb], sa, sb, fg, masked_raw, sp_bias_raw);
       }
       const int kfirst = kb * 64;
-      if (IDX && p.mask) {      // arbitrary mask tensor: raw' = raw * M + (-10000 / scale) * (1 - M)
-        const T* mrow = reinterpret_cast<const T*>(p.mask) + (long long)b * p.mask_bs + (long long)min(myq, p.s_q - 1) * p.s_k;
+      if (IDX && p.mask) {
+        float mk[16];
 #pragma unroll
-        for (int sb = 0; sb < 2; ++sb)
-#pragma unroll
-          for (int e = 0; e < 16; ++e) {
-            const int key = kfirst + sb * 32 + 4 * fg + (e & 3) + 8 * (e >> 2);
-            const float m = HT<T>::to_f(mrow[min(key, p.s_k - 1)]);
-            sacc[sb][e] = fmaf(sacc[sb][e], m, masked_raw * (1.f - m));
-          }
+        for (int sb = 0; sb < 2; ++sb) apply_mask_tensor<T>(sacc[sb], mk, p, b, myq, kfirst + sb * 32, fg, masked_raw);
       }
-      const bool all_visible = (kfirst + 63 <= q0w + off) || (kfirst + 63 < p.sep_k);
-      if (!all_visible || kfirst + 64 > p.s_k) {
-#pragma unroll
-        for (int sb = 0; sb < 2; ++sb) {
-          const int base = kfirst + sb * 32 + 4 * fg;
-          mask_frag(sacc[sb], myq + off - base, p.sep_k - base, p.s_k - base, masked_raw);
-        }
-      }
+      mask_edge<2>(sacc, kfirst, q0w, myq, off, fg, p, masked_raw);      // tested per 64 keys (the dQ kernel: per 32)
       // row maximum of the 32 scores: v_max3_f32 (the maxnum of fmaxf costs an extra canonicalising v_max per operand)
       float mb = sacc[0][0];
       asm("v_max3_f32 %0, %1, %2, %3" : "=v"(mb) : "v"(mb), "v"(sacc[1][0]), "v"(sacc[0][1]));
@@ -562,7 +612,7 @@ __global__ __launch_bounds__(NT, 2) void attn_bwd_dq_kernel(const AttnArgs p) {
   const bool drop = DROP < 0 ? (p.thr16 != 0u) : (DROP != 0);
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr bool KB = DROP == 2;
-  constexpr int STAGE = 2 * TILE + (KB ? 1024 : 0), LPT = KB ? 5 : 4;
+  using L = DqStage<KB>;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int fr = lane & 31, fg = lane >> 5;
@@ -631,43 +681,33 @@ __global__ __launch_bounds__(NT, 2) void attn_bwd_dq_kernel(const AttnArgs p) {
   const uint32_t loff[2] = {tr_lane_off(0, lane) ^ tr_lane_fix(lane), tr_lane_off(1, lane) ^ tr_lane_fix(lane)};
   const uint32_t smem_addr = (uint32_t)(uintptr_t)smem;
 
-  int* lidx = nullptr;
-  if (IDX && p.kv_index) {
-    lidx = reinterpret_cast<int*>(smem + NSTG * STAGE);
-    const int* gi = p.kv_index + (long long)b * p.kv_index_bs + (long long)gblk * p.kv_index_gs;
-    for (int i = threadIdx.x; i < p.s_k; i += NT) lidx[i] = gi[i];
-    __syncthreads();
-  }
+  int* const lidx = stage_index_table<IDX>(p, b, gblk, smem + L::INDEX);
   const float sp_bias_raw = spw ? p.sp_bias / p.scale : 0.f;
   const uint32_t* KWQ = KB ? p.keepbits + ((long long)b * p.H + head) * ((p.s_k + 63) >> 6) * 2 * p.s_q + (long long)fg * p.s_q + min(myq, p.s_q - 1)
                            : nullptr;
   auto issue = [&](int kb, int st) {
-    dma_tile<T>(K, p.k_rs, kb * 64, p.s_k, smem + st * STAGE, wave, lane, lidx);
-    dma_tile<T>(V, p.v_rs, kb * 64, p.s_k, smem + st * STAGE + TILE, wave, lane, lidx);
+    dma_tile<T>(K, p.k_rs, kb * 64, p.s_k, smem + st * L::SIZE + L::K, wave, lane, lidx);
+    dma_tile<T>(V, p.v_rs, kb * 64, p.s_k, smem + st * L::SIZE + L::V, wave, lane, lidx);
     if (KB) __builtin_amdgcn_global_load_lds((gbl_void_t*)(KWQ + (long long)kb * 2 * p.s_q),
-                                             (lds_void_t*)(smem + st * STAGE + 2 * TILE + wave * 256), 4, 0, 0);
+                                             (lds_void_t*)(smem + st * L::SIZE + L::KW + wave * L::KW_PITCH), 4, 0, 0);
   };
+  static_assert(L::DMAS == 2 * DMA_TILE + (KB ? 1 : 0), "issue(): K tile, V tile, KB: the wave's keep words");
   if (nkb > 0) { issue(0, 0); if (NSTG > 2) issue(nkb > 1 ? 1 : 0, 1); }
   int st = 0;
   for (int kb = 0; kb < nkb; ++kb) {
-    wait_vmcnt<(NSTG - 2) * LPT>();
+    wait_vmcnt<(NSTG - 2) * L::DMAS>();
     __builtin_amdgcn_s_barrier();
     issue(min(kb + NSTG - 1, nkb - 1), st == 0 ? NSTG - 1 : st - 1);
     if (kb * 64 < kend_w) {
-      const char* lk = smem + st * STAGE; const char* lv = lk + TILE;
-      const uint32_t lkt = smem_addr + st * STAGE;
+      const char* lk = smem + st * L::SIZE + L::K; const char* lv = smem + st * L::SIZE + L::V;
+      const uint32_t lkt = smem_addr + st * L::SIZE + L::K;
       uint32_t kwv = 0u;                                    // this lane's 32 keep bits of the block (forward's order)
       if (KB) {
-        const uint32_t ka = lkt + 2 * TILE + wave * 256 + lane * 4;
+        const uint32_t ka = smem_addr + st * L::SIZE + L::KW + wave * L::KW_PITCH + lane * 4;
         asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(kwv) : "v"(ka) : "memory");
       }
-      unsigned long long mflag = 0ull, mpiv = 0ull;         // slot attributes of this block (sparse training form)
-      if (spw) {
-        int raw;
-        const uint32_t ia = (uint32_t)(uintptr_t)(lidx + min(kb * 64 + lane, p.s_k - 1));
-        asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(raw) : "v"(ia) : "memory");
-        mflag = __ballot(raw < 0); mpiv = __ballot(kb * 64 + lane < p.sp_npiv);
-      }
+      SlotAttrs sa = {0ull, 0ull};                          // honoured in the sparse training form only (the forward kernel: both gathered forms)
+      if (spw) sa = slot_attrs(lidx, kb, lane, p);
       auto half = [&](auto SBc) {
         constexpr int sb = decltype(SBc)::value;
         f32x16 sacc, pacc;
@@ -680,28 +720,11 @@ __global__ __launch_bounds__(NT, 2) void attn_bwd_dq_kernel(const AttnArgs p) {
         }
         TrRaw kr[2][2];
         tr_frags_issue<T, sb>(lkt, loff, kr);
-        if (spw) {
-          const uint32_t fm = (uint32_t)(mflag >> (32 * sb)) >> (4 * fg), pm = (uint32_t)(mpiv >> (32 * sb)) >> (4 * fg);
-#pragma unroll
-          for (int e = 0; e < 16; ++e) {
-            const int bit = (e & 3) + 8 * (e >> 2);
-            float v = sacc[e];
-            v = ((fm >> bit) & 1u) ? masked_raw : v;
-            v += ((pm >> bit) & 1u) ? sp_bias_raw : 0.f;
-            sacc[e] = v;
-          }
-        }
+        if (spw) apply_slot_attrs(sacc, sa, sb, fg, masked_raw, sp_bias_raw);
         const int kfirst = kb * 64 + sb * 32;
-        float mk[16];                                          // arbitrary mask tensor (see attn_fwd_kernel): d raw = d raw' * M
-        if (IDX && p.mask) {
-          const T* mrow = reinterpret_cast<const T*>(p.mask) + (long long)b * p.mask_bs + (long long)min(myq, p.s_q - 1) * p.s_k;
-#pragma unroll
-          for (int e = 0; e < 16; ++e) {
-            const int key = kfirst + 4 * fg + (e & 3) + 8 * (e >> 2);
-            mk[e] = HT<T>::to_f(mrow[min(key, p.s_k - 1)]);
-            sacc[e] = fmaf(sacc[e], mk[e], masked_raw * (1.f - mk[e]));
-          }
-        }
+        float mk[16];                                          // arbitrary mask tensor: d raw = d raw' * M
+        if (IDX && p.mask) apply_mask_tensor<T>(sacc, mk, p, b, myq, kfirst, fg, masked_raw);
+        // (as mask_edge, per 32 keys; kept in place: through the helper this kernel's instruction stream changes)
         const bool all_visible = (kfirst + 31 <= q0w + off) || (kfirst + 31 < p.sep_k);
         if (!all_visible || kfirst + 32 > p.s_k) {
           const int base = kfirst + 4 * fg;
@@ -785,15 +808,11 @@ __device__ unsigned long long g_attn_ts[1024 * 8];      // 1024 slots of 8 count
 #define ATS(k_) do { } while (0)
 #endif
 template <typename T, bool IDX, int DROP>
-__global__ __launch_bounds__(NT, (!IDX && DROP == 2) ? COGV_DKDV_WAVES : 2) void attn_bwd_dkdv_kernel(const AttnArgs p) {
+__global__ __launch_bounds__(NT, 2) void attn_bwd_dkdv_kernel(const AttnArgs p) {
   const bool drop = DROP < 0 ? (p.thr16 != 0u) : (DROP != 0);
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr bool KB = DROP == 2;
-  // KWP: pitch (bytes) of the four keep-word segments of a stage.  272 instead of 256 (round 6): a lane group reads two segments
-  // in one ds_read_b128 (its key's bit 2 selects which), and at a 256-byte pitch the two hit the same banks -- the 12 % LDS
-  // bank-conflict cycles of this kernel alone among the three (profiles/r05_attention_pmc.txt)
-  constexpr int KWP = COGV_DKDV_KW_PITCH;
-  constexpr int STAGE = 2 * TILE + (KB ? 512 + 4 * KWP : 768), LPT = 7;
+  using L = DkdvStage<KB>;
 #if defined(COGV_ATTN_TS)
   unsigned long long ats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   const unsigned long long ats_begin = __builtin_readcyclecounter();
@@ -837,14 +856,6 @@ __global__ __launch_bounds__(NT, (!IDX && DROP == 2) ? COGV_DKDV_WAVES : 2) void
     kf[t] = load_frag_global<T>(K + (long long)krow * p.k_rs + 16 * t + 8 * fg, kvalid);
     vf[t] = load_frag_global<T>(V + (long long)krow * p.v_rs + 16 * t + 8 * fg, kvalid);
   }
-  // (diet) the V fragments parked in LDS behind the ring, one 16-byte slot per (wave, t, lane): lane-private, so the in-order LDS
-  // queue is all the ordering the write and the later reads need
-  constexpr bool VLDS = KB && !IDX && (COGV_DKDV_VLDS != 0);
-  typename HT<T>::v8* const own_v = reinterpret_cast<typename HT<T>::v8*>(smem + ring_bytes(STAGE, true)) + (wave * 4) * 64 + lane;
-  if (VLDS) {
-#pragma unroll
-    for (int t = 0; t < 4; ++t) own_v[t * 64] = vf[t];
-  }
   const int qbeg_blk = (k0 < p.sep_k) ? qlo : max(qlo, k0 - off);
   const int qbeg_w = (k0w < p.sep_k) ? qlo : max(qlo, k0w - off);
   const int qb0 = qbeg_blk >> 6;
@@ -871,23 +882,24 @@ __global__ __launch_bounds__(NT, (!IDX && DROP == 2) ? COGV_DKDV_WAVES : 2) void
   const uint32_t* KWS = KB ? p.keepbits + ((((long long)b * p.H + head) * nkbt + min((k0 >> 6) + (wave >> 1), nkbt - 1)) * 2 + (wave & 1)) * p.s_q
                            : nullptr;
   auto issue = [&](int qb, int st) {
-    char* base = smem + st * STAGE;
-    dma_tile<T>(Q, p.q_rs, qb * 64, p.s_q, base, wave, lane);
-    dma_tile<T>(DO, p.do_rs, qb * 64, p.s_q, base + TILE, wave, lane);
-    dma_stat(KB ? RK : LSE, qb * 64, p.s_q, base + 2 * TILE, lane);      // KB: plane 1 holds -LSE * log2(e) (dQ kernel)
-    dma_stat(DV, qb * 64, p.s_q, base + 2 * TILE + 256, lane);
-    if (KB) dma_stat(reinterpret_cast<const float*>(KWS), qb * 64, p.s_q, base + 2 * TILE + 512 + wave * KWP, lane);
-    else dma_stat(RK, qb * 64, p.s_q, base + 2 * TILE + 512, lane);
+    char* base = smem + st * L::SIZE;
+    dma_tile<T>(Q, p.q_rs, qb * 64, p.s_q, base + L::Q, wave, lane);
+    dma_tile<T>(DO, p.do_rs, qb * 64, p.s_q, base + L::DO, wave, lane);
+    dma_stat(KB ? RK : LSE, qb * 64, p.s_q, base + L::LSE, lane);      // KB: plane 1 holds -LSE * log2(e) (dQ kernel)
+    dma_stat(DV, qb * 64, p.s_q, base + L::D, lane);
+    if (KB) dma_stat(reinterpret_cast<const float*>(KWS), qb * 64, p.s_q, base + L::KW + wave * L::KW_PITCH, lane);
+    else dma_stat(RK, qb * 64, p.s_q, base + L::RK, lane);
   };
+  static_assert(L::DMAS == 2 * DMA_TILE + 3, "issue(): Q tile, dO tile, LSE row, D row, row keys or the wave's keep-word segment");
   // the lane's key inside its 64-key block: half (wave & 1 -- the wave's 32 keys), key half fg' = bit 2, element 4 (r >> 3) + (r & 3)
   const int kr = mykey & 31;
-  const uint32_t kw_seg = (uint32_t)(((wave >> 1) * 2 + ((kr >> 2) & 1)) * (KWP / 4));        // word offset of the lane's segment
+  const uint32_t kw_seg = (uint32_t)(((wave >> 1) * 2 + ((kr >> 2) & 1)) * (L::KW_PITCH / 4));        // word offset of the lane's segment
   const uint32_t kw_bit = 31u - (uint32_t)((wave & 1) * 16 + 4 * (kr >> 3) + (kr & 3));
   if (qb0 < nqb) { issue(qb0, 0); if (NSTG > 2) issue(min(qb0 + 1, nqb - 1), 1); }
   int st = 0;
   ATS(4);
   for (int qb = qb0; qb < nqb; ++qb) {
-    wait_vmcnt<(NSTG - 2) * LPT>();
+    wait_vmcnt<(NSTG - 2) * L::DMAS>();
     __builtin_amdgcn_s_barrier();
     ATS(0);
     issue(min(qb + NSTG - 1, nqb - 1), st == 0 ? NSTG - 1 : st - 1);
@@ -896,9 +908,12 @@ __global__ __launch_bounds__(NT, (!IDX && DROP == 2) ? COGV_DKDV_WAVES : 2) void
     ats[6] += 1;
 #endif
     if (wave_active && qb * 64 + 63 >= qbeg_w) {
-      const char* lq = smem + st * STAGE; const char* ldo = lq + TILE;
-      const uint32_t lqt = smem_addr + st * STAGE, ldot = lqt + TILE;
-      const float* stat = reinterpret_cast<const float*>(lq + 2 * TILE);
+      const char* lq = smem + st * L::SIZE + L::Q; const char* ldo = smem + st * L::SIZE + L::DO;
+      const uint32_t lqt = smem_addr + st * L::SIZE + L::Q, ldot = smem_addr + st * L::SIZE + L::DO;
+      const float* lse_row = reinterpret_cast<const float*>(smem + st * L::SIZE + L::LSE);
+      const float* d_row = reinterpret_cast<const float*>(smem + st * L::SIZE + L::D);
+      const uint32_t* rk_row = reinterpret_cast<const uint32_t*>(smem + st * L::SIZE + L::RK);      // !KB: the queries' dropout row keys
+      const uint32_t* kw_segs = reinterpret_cast<const uint32_t*>(smem + st * L::SIZE + L::KW);     // KB: the four keep-word segments
       auto half = [&](auto SBc) {
         constexpr int sb = decltype(SBc)::value;
         f32x16 sacc, pacc;
@@ -908,11 +923,11 @@ __global__ __launch_bounds__(NT, (!IDX && DROP == 2) ? COGV_DKDV_WAVES : 2) void
         // requested NOW and land behind the S / dP products and the element-wise chain; the regenerating form (register
         // pressure at the limit) reads them synchronously where they are used -- two exposed LDS round trips per half
         TrRaw dor_a[2][2], qr_a[2][2];
-        if (KB && COGV_DKDV_AHEAD) { tr_frags_issue<T, sb>(ldot, loff, dor_a); tr_frags_issue<T, sb>(lqt, loff, qr_a); }
+        if (KB) { tr_frags_issue<T, sb>(ldot, loff, dor_a); tr_frags_issue<T, sb>(lqt, loff, qr_a); }
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
           sacc = HT<T>::mfma32(nat_frag<T>(lq, sb * 32 + fr, 2 * t + fg), kf[t], sacc);     // S = Q K^T
-          pacc = HT<T>::mfma32(nat_frag<T>(ldo, sb * 32 + fr, 2 * t + fg), VLDS ? own_v[t * 64] : vf[t], pacc);    // dPd = dO V^T
+          pacc = HT<T>::mfma32(nat_frag<T>(ldo, sb * 32 + fr, 2 * t + fg), vf[t], pacc);    // dPd = dO V^T
         }
         // element e <-> query qfirst + 4fg + (e&3) + 8(e>>2); key fixed per lane
         const int qfirst = qb * 64 + sb * 32;
@@ -927,7 +942,7 @@ __global__ __launch_bounds__(NT, (!IDX && DROP == 2) ? COGV_DKDV_WAVES : 2) void
         if (!all_visible || tail) {
 #pragma unroll
           for (int e = 0; e < 16; ++e) {
-            const int q = qfirst + 4 * fg + (e & 3) + 8 * (e >> 2);
+            const int q = qfirst + 4 * fg + elem_idx(e);
             float a = sacc[e];
             if (!visible(q, mykey, off, p.sep_k)) a = masked_raw;
             if (q >= p.s_q) a = -INFINITY;
@@ -943,7 +958,7 @@ __global__ __launch_bounds__(NT, (!IDX && DROP == 2) ? COGV_DKDV_WAVES : 2) void
           const T* mcol = reinterpret_cast<const T*>(p.mask) + (long long)b * p.mask_bs + min(mykey, p.s_k - 1);
 #pragma unroll
           for (int e = 0; e < 16; ++e) {
-            const int q = qfirst + 4 * fg + (e & 3) + 8 * (e >> 2);
+            const int q = qfirst + 4 * fg + elem_idx(e);
             mq[e] = HT<T>::to_f(mcol[(long long)min(q, p.s_q - 1) * p.s_k]);
             if (q < p.s_q) sacc[e] = fmaf(sacc[e], mq[e], masked_raw * (1.f - mq[e]));
           }
@@ -955,7 +970,7 @@ __global__ __launch_bounds__(NT, (!IDX && DROP == 2) ? COGV_DKDV_WAVES : 2) void
           for (int gq = 0; gq < 4; ++gq) {
             // row q = qb * 64 + sb * 32 + 8 gq + 4 fg + c of this (batch, head): its key comes from the stage's third
             // statistics row; group = the lane's keys
-            const uint32_t rkq = reinterpret_cast<const uint32_t*>(stat)[128 + sb * 32 + 8 * gq + 4 * fg + c];
+            const uint32_t rkq = rk_row[sb * 32 + 8 * gq + 4 * fg + c];
             const u32x2 r = attn_bits_w(rkq + gweyl);
             uint32_t m4 = 0;
 #pragma unroll
@@ -968,11 +983,11 @@ __global__ __launch_bounds__(NT, (!IDX && DROP == 2) ? COGV_DKDV_WAVES : 2) void
 #pragma unroll
         for (int gq = 0; gq < 4; ++gq) {
           const int ql = sb * 32 + 8 * gq + 4 * fg;                // local query of element i = 0
-          const f32x4 l4 = *reinterpret_cast<const f32x4*>(stat + ql);
-          const f32x4 d4 = *reinterpret_cast<const f32x4*>(stat + 64 + ql);
+          const f32x4 l4 = *reinterpret_cast<const f32x4*>(lse_row + ql);
+          const f32x4 d4 = *reinterpret_cast<const f32x4*>(d_row + ql);
           uint32_t km[4];
           if (KB) {                                             // the words of the 4 queries of this group: one b128 read
-            const u32x4 w4 = *reinterpret_cast<const u32x4*>(reinterpret_cast<const uint32_t*>(stat) + 128 + kw_seg + ql);
+            const u32x4 w4 = *reinterpret_cast<const u32x4*>(kw_segs + kw_seg + ql);
             km[0] = w4[0]; km[1] = w4[1]; km[2] = w4[2]; km[3] = w4[3];
           } else if (drop) {                                    // quad_perm(i,i,i,i): value held by quad lane i
             km[0] = (uint32_t)__builtin_amdgcn_mov_dpp((int)kmask[gq], 0x00, 0xf, 0xf, true);
@@ -1003,7 +1018,7 @@ __global__ __launch_bounds__(NT, (!IDX && DROP == 2) ? COGV_DKDV_WAVES : 2) void
         typename HT<T>::v8 pb[2], dsb[2];
 #pragma unroll
         for (int t = 0; t < 2; ++t) { pb[t] = cvt8<T>(pd + 8 * t); dsb[t] = cvt8<T>(ds + 8 * t); }
-        if (KB && COGV_DKDV_AHEAD) {
+        if (KB) {
           tr_wait(dor_a[0][0], dor_a[0][1]); tr_wait(dor_a[1][0], dor_a[1][1]);
           tr_wait(qr_a[0][0], qr_a[0][1]); tr_wait(qr_a[1][0], qr_a[1][1]);
 #pragma unroll
@@ -1259,7 +1274,42 @@ __global__ __launch_bounds__(256) void sparse_slot_reduce_kernel(const T* __rest
 
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
-int fill_args(const cogv_attn_desc* d, AttnArgs& a) {
+// Which instantiation runs.  The dense kernels have dropout off / on / on with stored keep bits as separate instantiations (no
+// wave-uniform branches and register copies at their joins inside the softmax); the flexible one (gathered / sparse keys,
+// arbitrary mask tensors: IDX = true) decides about dropout at run time.
+enum AttnForm { ATTN_DENSE = 0, ATTN_DENSE_DROP = 1, ATTN_DENSE_BITS = 2, ATTN_FLEXIBLE = 3 };
+
+// Everything a call of cogv_attention_fwd / _bwd decides before it launches: the argument checks, the kernel arguments, the form,
+// and grid + dynamic LDS of each launch.  Host-only (no device call, no pointer of the descriptor is dereferenced);
+// cogv_attention_plan reports it.
+struct AttnPlan {
+  int form;
+  AttnArgs a;
+  unsigned grid_q, grid_k;     // forward or dQ launch; dK.dV launch (backward only).  One-dimensional XCD-aware grids (xcd_block_id):
+  int lds_q, lds_k;            // 8 x ceil(units / 8) x blocks, units = H * B (dK.dV: H * planes)
+  // sparse training form: dK / dV are slot-space buffers, one [s_k] plane per (batch, query block): dk_bs / dv_bs is the plane
+  // stride and the dK.dV grid runs over B * (s_q / sparse_window) planes; B otherwise
+  int planes;
+};
+
+// gathered keys (kv_index) and the sparse training form's slot attributes
+int index_args(const cogv_attn_desc* d, AttnArgs& a) {
+  if (d->kv_index) {
+    if (a.s_k > 4096) return COGV_ERR_UNSUPPORTED;
+    a.kv_index = d->kv_index; a.kv_index_bs = d->kv_index_bs;
+    if (d->sparse_window > 0) {          // training form: s_k = slots per query block, queries in blocks of sparse_window
+      if ((d->sparse_window % 128) || (a.s_q % d->sparse_window) || d->sparse_pivots < 0 || d->sparse_pivots > a.s_k ||
+          a.s_k < d->sparse_window || a.sep_k != 0) return COGV_ERR_ARG;
+      a.kv_index_gs = d->kv_index_gs; a.sp_w = d->sparse_window; a.sp_npiv = d->sparse_pivots; a.sp_bias = d->sparse_pivot_bias;
+    }
+  } else if (d->sparse_window > 0) {
+    return COGV_ERR_ARG;
+  }
+  return COGV_OK;
+}
+
+int attn_plan(const cogv_attn_desc* d, bool backward, AttnPlan& pl) {
+  AttnArgs& a = pl.a;
   if (!d) return COGV_ERR_ARG;
   if (d->dtype != COGV_F16 && d->dtype != COGV_BF16) return COGV_ERR_UNSUPPORTED;
   if (d->head_dim != HD) return COGV_ERR_UNSUPPORTED;
@@ -1286,139 +1336,96 @@ int fill_args(const cogv_attn_desc* d, AttnArgs& a) {
   a.thr16 = (uint32_t)(d->dropout_p * 65536.0f + 0.5f);
   a.keep_scale = 65536.0f / (65536.0f - (float)a.thr16);
   a.rng_key = rng_key(d->seed, d->stream_id);
-  return COGV_OK;
-}
 
-// gathered keys (kv_index) and the sparse training form's slot attributes
-int index_args(const cogv_attn_desc* d, AttnArgs& a) {
-  if (d->kv_index) {
-    if (a.s_k > 4096) return COGV_ERR_UNSUPPORTED;
-    a.kv_index = d->kv_index; a.kv_index_bs = d->kv_index_bs;
-    if (d->sparse_window > 0) {          // training form: s_k = slots per query block, queries in blocks of sparse_window
-      if ((d->sparse_window % 128) || (a.s_q % d->sparse_window) || d->sparse_pivots < 0 || d->sparse_pivots > a.s_k ||
-          a.s_k < d->sparse_window || a.sep_k != 0) return COGV_ERR_ARG;
-      a.kv_index_gs = d->kv_index_gs; a.sp_w = d->sparse_window; a.sp_npiv = d->sparse_pivots; a.sp_bias = d->sparse_pivot_bias;
+  // (the two directions check pointers, index and strides in different orders; an input that fails two checks can tell, so both stay)
+  int rc;
+  if (!a.q || !a.k || !a.v || !a.o) return COGV_ERR_ARG;
+  if (!backward) {
+    if (!aligned16(a.q) || !aligned16(a.k) || !aligned16(a.v) || !aligned16(a.o)) return COGV_ERR_ARG;
+    if ((a.q_rs | a.k_rs | a.v_rs | a.o_rs) & 7) return COGV_ERR_ARG;
+    if ((a.q_bs | a.k_bs | a.v_bs | a.o_bs) & 7) return COGV_ERR_ARG;
+    if ((rc = index_args(d, a))) return rc;
+  } else {
+    if (!a.dout || !a.dq || !a.dk || !a.dv || !a.lse || !a.dvec) return COGV_ERR_ARG;
+    if (d->kv_index && d->sparse_window <= 0) return COGV_ERR_UNSUPPORTED;      // the plain gathered form is inference only
+    if ((rc = index_args(d, a))) return rc;
+    if (a.sp_w > 0 && d->colsum_partial) return COGV_ERR_UNSUPPORTED;
+    if (d->colsum_partial) {
+      if (d->s_q != d->s_k || ((uintptr_t)d->colsum_partial & 15)) return COGV_ERR_ARG;
+      a.colsum_ws = d->colsum_partial;
     }
-  } else if (d->sparse_window > 0) {
-    return COGV_ERR_ARG;
+    if (!aligned16(a.q) || !aligned16(a.k) || !aligned16(a.v) || !aligned16(a.o) || !aligned16(a.dout) ||
+        !aligned16(a.dq) || !aligned16(a.dk) || !aligned16(a.dv)) return COGV_ERR_ARG;
+    if ((a.q_rs | a.k_rs | a.v_rs | a.o_rs | a.do_rs | a.dq_rs | a.dk_rs | a.dv_rs) & 7) return COGV_ERR_ARG;
+    if ((a.q_bs | a.k_bs | a.v_bs | a.o_bs | a.do_bs | a.dq_bs | a.dk_bs | a.dv_bs) & 7) return COGV_ERR_ARG;
+  }
+  const int slots = a.kv_index ? a.s_k : 0;       // the index table behind the ring of the lane = query kernels
+  pl.planes = a.sp_w > 0 && backward ? a.B * (a.s_q / a.sp_w) : a.B;
+  pl.grid_q = 8u * (unsigned)((a.H * a.B + 7) / 8) * (unsigned)((a.s_q + 127) / 128);
+  pl.grid_k = backward ? 8u * (unsigned)((a.H * pl.planes + 7) / 8) * (unsigned)((a.s_k + 127) / 128) : 0u;
+  pl.lds_q = backward ? DqStage<false>::dynamic_lds(slots) : FwdStage::dynamic_lds(slots);
+  pl.lds_k = backward ? DkdvStage<false>::dynamic_lds(0) : 0;
+  if (pl.lds_q > 160 * 1024) return COGV_ERR_UNSUPPORTED;
+  const bool drop = a.thr16 != 0u;
+  pl.form = (a.kv_index || a.mask) ? ATTN_FLEXIBLE : drop ? ATTN_DENSE_DROP : ATTN_DENSE;
+  if (d->keep_bits && drop && !a.kv_index) {      // dense, dropout on: forward stores its keep bits there, backward reads them
+    if ((uintptr_t)d->keep_bits & 3) return COGV_ERR_ARG;       // (same dropout_p / seed / stream in both calls)
+    a.keepbits = reinterpret_cast<uint32_t*>(d->keep_bits);
+    pl.form = ATTN_DENSE_BITS;
+    if (backward) { pl.lds_q = DqStage<true>::dynamic_lds(0); pl.lds_k = DkdvStage<true>::dynamic_lds(0); }
   }
   return COGV_OK;
 }
 
-template <typename K>
-void set_smem(K kernel, int bytes) {
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+// One launch: the kernel's dynamic-LDS attribute is raised first when this launch needs more than any before it (remembered per
+// instantiation and process; never lowered: a smaller later request must not lower it under a launch that still needs more)
+// The forward kernels go through it too: their ring plus the largest index table is 64 KiB at most, so for them it is a formality.
+template <void (*KERNEL)(const AttnArgs)>
+void attn_launch(unsigned grid, int lds, hipStream_t st, const AttnArgs& a) {
+  static int raised = 0;
+  if (lds > raised) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    raised = lds;
+  }
+  hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(NT), lds, st, a);
+}
+template <typename T, bool IDX, int DROP>
+void attn_launch_form(const AttnPlan& pl, bool backward, hipStream_t st) {
+  if (!backward) return attn_launch<attn_fwd_kernel<T, IDX, DROP>>(pl.grid_q, pl.lds_q, st, pl.a);
+  attn_launch<attn_bwd_dq_kernel<T, IDX, DROP>>(pl.grid_q, pl.lds_q, st, pl.a);
+  attn_launch<attn_bwd_dkdv_kernel<T, IDX, DROP>>(pl.grid_k, pl.lds_k, st, pl.a);
+}
+template <typename T>
+void attn_launch_dtype(const AttnPlan& pl, bool backward, hipStream_t st) {
+  switch (pl.form) {
+    case ATTN_DENSE: return attn_launch_form<T, false, 0>(pl, backward, st);
+    case ATTN_DENSE_DROP: return attn_launch_form<T, false, 1>(pl, backward, st);
+    case ATTN_DENSE_BITS: return attn_launch_form<T, false, 2>(pl, backward, st);
+    default: return attn_launch_form<T, true, -1>(pl, backward, st);
+  }
+}
+int attn_run(const cogv_attn_desc* d, bool backward, void* stream) {
+  AttnPlan pl;
+  const int rc = attn_plan(d, backward, pl);
+  if (rc) return rc;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (d->dtype == COGV_F16) attn_launch_dtype<f16_t>(pl, backward, st);
+  else attn_launch_dtype<bf16_t>(pl, backward, st);
+  return cogv_check_launch();
 }
 
 }  // namespace
 
-extern "C" int cogv_attention_fwd(const cogv_attn_desc* d, void* stream) {
-  AttnArgs a;
-  int rc = fill_args(d, a);
-  if (rc) return rc;
-  if (!a.q || !a.k || !a.v || !a.o) return COGV_ERR_ARG;
-  if (!aligned16(a.q) || !aligned16(a.k) || !aligned16(a.v) || !aligned16(a.o)) return COGV_ERR_ARG;
-  if ((a.q_rs | a.k_rs | a.v_rs | a.o_rs) & 7) return COGV_ERR_ARG;
-  if ((a.q_bs | a.k_bs | a.v_bs | a.o_bs) & 7) return COGV_ERR_ARG;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  // one-dimensional XCD-aware grid (xcd_block_id): 8 x ceil(units / 8) x blocks, units = H * B
-  dim3 grid(8u * (unsigned)((a.H * a.B + 7) / 8) * (unsigned)((a.s_q + 127) / 128));
-  int sh = NSTG * 2 * TILE;
-  if ((rc = index_args(d, a))) return rc;
-  if (a.kv_index) sh += ((a.s_k * 4 + 15) / 16) * 16;
-  // dense kernels: dropout on / off are separate instantiations (no wave-uniform branches and register copies at their
-  // joins inside the softmax); the gathered / sparse forms decide at run time
-  const bool drop = a.thr16 != 0u;
-  if (d->keep_bits && drop && !a.kv_index) {      // dense, dropout on, the caller keeps the bits for the backward pass
-    if ((uintptr_t)d->keep_bits & 3) return COGV_ERR_ARG;
-    a.keepbits = reinterpret_cast<uint32_t*>(d->keep_bits);
-    if (d->dtype == COGV_F16) hipLaunchKernelGGL((attn_fwd_kernel<f16_t, false, 2>), grid, dim3(NT), sh, st, a);
-    else hipLaunchKernelGGL((attn_fwd_kernel<bf16_t, false, 2>), grid, dim3(NT), sh, st, a);
-    return cogv_check_launch();
-  }
-  if (a.kv_index || a.mask) {         // the flexible instantiation: gathered / sparse forms, arbitrary mask tensors
-    if (d->dtype == COGV_F16) hipLaunchKernelGGL((attn_fwd_kernel<f16_t, true, -1>), grid, dim3(NT), sh, st, a);
-    else hipLaunchKernelGGL((attn_fwd_kernel<bf16_t, true, -1>), grid, dim3(NT), sh, st, a);
-  } else if (d->dtype == COGV_F16) {
-    if (drop) hipLaunchKernelGGL((attn_fwd_kernel<f16_t, false, 1>), grid, dim3(NT), sh, st, a);
-    else hipLaunchKernelGGL((attn_fwd_kernel<f16_t, false, 0>), grid, dim3(NT), sh, st, a);
-  } else {
-    if (drop) hipLaunchKernelGGL((attn_fwd_kernel<bf16_t, false, 1>), grid, dim3(NT), sh, st, a);
-    else hipLaunchKernelGGL((attn_fwd_kernel<bf16_t, false, 0>), grid, dim3(NT), sh, st, a);
-  }
-  return cogv_check_launch();
-}
+extern "C" int cogv_attention_fwd(const cogv_attn_desc* d, void* stream) { return attn_run(d, false, stream); }
+extern "C" int cogv_attention_bwd(const cogv_attn_desc* d, void* stream) { return attn_run(d, true, stream); }
 
-extern "C" int cogv_attention_bwd(const cogv_attn_desc* d, void* stream) {
-  AttnArgs a;
-  int rc = fill_args(d, a);
-  if (rc) return rc;
-  if (!a.q || !a.k || !a.v || !a.o || !a.dout || !a.dq || !a.dk || !a.dv || !a.lse || !a.dvec) return COGV_ERR_ARG;
-  if (d->kv_index && d->sparse_window <= 0) return COGV_ERR_UNSUPPORTED;      // the plain gathered form is inference only
-  if ((rc = index_args(d, a))) return rc;
-  if (a.sp_w > 0 && d->colsum_partial) return COGV_ERR_UNSUPPORTED;
-  if (d->colsum_partial) {
-    if (d->s_q != d->s_k || ((uintptr_t)d->colsum_partial & 15)) return COGV_ERR_ARG;
-    a.colsum_ws = d->colsum_partial;
-  }
-  if (!aligned16(a.q) || !aligned16(a.k) || !aligned16(a.v) || !aligned16(a.o) || !aligned16(a.dout) ||
-      !aligned16(a.dq) || !aligned16(a.dk) || !aligned16(a.dv)) return COGV_ERR_ARG;
-  if ((a.q_rs | a.k_rs | a.v_rs | a.o_rs | a.do_rs | a.dq_rs | a.dk_rs | a.dv_rs) & 7) return COGV_ERR_ARG;
-  if ((a.q_bs | a.k_bs | a.v_bs | a.o_bs | a.do_bs | a.dq_bs | a.dk_bs | a.dv_bs) & 7) return COGV_ERR_ARG;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  // sparse training form: dK / dV are slot-space buffers, one [s_k] plane per (batch, query block): dk_bs / dv_bs is
-  // the plane stride and grid z runs over B * (s_q / sparse_window) planes
-  const int planes = a.sp_w > 0 ? a.B * (a.s_q / a.sp_w) : a.B;
-  dim3 gq(8u * (unsigned)((a.H * a.B + 7) / 8) * (unsigned)((a.s_q + 127) / 128));
-  dim3 gk(8u * (unsigned)((a.H * planes + 7) / 8) * (unsigned)((a.s_k + 127) / 128));
-  const int sh_q = ring_bytes(2 * TILE, true) + (a.kv_index ? ((a.s_k * 4 + 15) / 16) * 16 : 0), sh_k = ring_bytes(2 * TILE + 768, true);
-  if (sh_q > 160 * 1024) return COGV_ERR_UNSUPPORTED;
-  static int attr_q = 0;
-  static bool attr = false;
-  if (!attr) {
-    set_smem(&attn_bwd_dkdv_kernel<f16_t, false, 0>, sh_k); set_smem(&attn_bwd_dkdv_kernel<bf16_t, false, 0>, sh_k);
-    set_smem(&attn_bwd_dkdv_kernel<f16_t, false, 1>, sh_k); set_smem(&attn_bwd_dkdv_kernel<bf16_t, false, 1>, sh_k);
-    set_smem(&attn_bwd_dkdv_kernel<f16_t, true, -1>, sh_k); set_smem(&attn_bwd_dkdv_kernel<bf16_t, true, -1>, sh_k);
-    set_smem(&attn_bwd_dq_kernel<f16_t, false, 0>, ring_bytes(2 * TILE, true)); set_smem(&attn_bwd_dq_kernel<bf16_t, false, 0>, ring_bytes(2 * TILE, true));
-    set_smem(&attn_bwd_dq_kernel<f16_t, false, 1>, ring_bytes(2 * TILE, true)); set_smem(&attn_bwd_dq_kernel<bf16_t, false, 1>, ring_bytes(2 * TILE, true));
-    set_smem(&attn_bwd_dq_kernel<f16_t, false, 2>, ring_bytes(2 * TILE + 1024, true)); set_smem(&attn_bwd_dq_kernel<bf16_t, false, 2>, ring_bytes(2 * TILE + 1024, true));
-    set_smem(&attn_bwd_dkdv_kernel<f16_t, false, 2>, ring_bytes(2 * TILE + 512 + 4 * COGV_DKDV_KW_PITCH, true) + DKDV_OWN_V); set_smem(&attn_bwd_dkdv_kernel<bf16_t, false, 2>, ring_bytes(2 * TILE + 512 + 4 * COGV_DKDV_KW_PITCH, true) + DKDV_OWN_V);
-    attr = true;
-  }
-  // the flexible dQ instantiation (gathered / sparse keys: ring + index table; arbitrary mask tensors: ring only) shares ONE
-  // attribute, which only ever grows (a smaller later request must not lower it under a launch that still needs more)
-  if ((a.kv_index || a.mask) && sh_q > attr_q) {
-    set_smem(&attn_bwd_dq_kernel<f16_t, true, -1>, sh_q); set_smem(&attn_bwd_dq_kernel<bf16_t, true, -1>, sh_q);
-    attr_q = sh_q;
-  }
-  const bool drop = a.thr16 != 0u;
-  if (d->keep_bits && drop && !a.kv_index) {      // the keep bits the forward call stored (same dropout_p / seed / stream)
-    if ((uintptr_t)d->keep_bits & 3) return COGV_ERR_ARG;
-    a.keepbits = reinterpret_cast<uint32_t*>(d->keep_bits);
-    const int shq2 = ring_bytes(2 * TILE + 1024, true), shk2 = ring_bytes(2 * TILE + 512 + 4 * COGV_DKDV_KW_PITCH, true) + DKDV_OWN_V;
-    if (d->dtype == COGV_F16) {
-      hipLaunchKernelGGL((attn_bwd_dq_kernel<f16_t, false, 2>), gq, dim3(NT), shq2, st, a);
-      hipLaunchKernelGGL((attn_bwd_dkdv_kernel<f16_t, false, 2>), gk, dim3(NT), shk2, st, a);
-    } else {
-      hipLaunchKernelGGL((attn_bwd_dq_kernel<bf16_t, false, 2>), gq, dim3(NT), shq2, st, a);
-      hipLaunchKernelGGL((attn_bwd_dkdv_kernel<bf16_t, false, 2>), gk, dim3(NT), shk2, st, a);
-    }
-    return cogv_check_launch();
-  }
-#define ATTN_BWD_LAUNCH(T_, IDX_, DROP_)                                                             \
-  do {                                                                                               \
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<T_, IDX_, DROP_>), gq, dim3(NT), sh_q, st, a);            \
-    hipLaunchKernelGGL((attn_bwd_dkdv_kernel<T_, IDX_, DROP_>), gk, dim3(NT), sh_k, st, a);          \
-  } while (0)
-  if (a.kv_index || a.mask) {   // sparse training form / arbitrary mask tensor: the instantiation with the gather, the slot attributes, the mask
-    if (d->dtype == COGV_F16) ATTN_BWD_LAUNCH(f16_t, true, -1); else ATTN_BWD_LAUNCH(bf16_t, true, -1);
-  } else if (d->dtype == COGV_F16) {
-    if (drop) ATTN_BWD_LAUNCH(f16_t, false, 1); else ATTN_BWD_LAUNCH(f16_t, false, 0);
-  } else {
-    if (drop) ATTN_BWD_LAUNCH(bf16_t, false, 1); else ATTN_BWD_LAUNCH(bf16_t, false, 0);
-  }
-#undef ATTN_BWD_LAUNCH
-  return cogv_check_launch();
+extern "C" int cogv_attention_plan(const cogv_attn_desc* d, int backward, int out[8]) {
+  AttnPlan pl;
+  const int rc = attn_plan(d, backward != 0, pl);
+  if (rc || !out) return rc ? rc : COGV_ERR_ARG;
+  out[0] = pl.form; out[1] = NT; out[2] = (int)pl.grid_q; out[3] = pl.lds_q; out[4] = (int)pl.grid_k; out[5] = pl.lds_k;
+  out[6] = pl.planes; out[7] = pl.a.sep_k;
+  return COGV_OK;
 }
 
 extern "C" size_t cogv_attention_keep_bits_bytes(int B, int H, int s_q, int s_k) {

@@ -239,6 +239,14 @@ typedef struct cogv_attn_desc {
 } cogv_attn_desc;
 int cogv_attention_fwd(const cogv_attn_desc* d, void* stream);
 int cogv_attention_bwd(const cogv_attn_desc* d, void* stream);
+/* Host-only query (no device is touched, none of the descriptor's pointers is dereferenced): what cogv_attention_fwd (backward = 0)
+ * or cogv_attention_bwd (backward = 1) would launch for this descriptor, from the function the launch itself uses, and the argument
+ * errors of those entry points (out is left untouched then).  out = { form (0 dense without dropout, 1 dense regenerating the
+ * dropout draws, 2 dense with stored keep bits, 3 flexible: gathered / sparse keys, mask tensor), threads per workgroup,
+ * workgroups and dynamic LDS bytes of the forward or dQ launch, workgroups and dynamic LDS bytes of the dK.dV launch (0 forward),
+ * planes of the dK.dV grid (B; sparse training form backward: B * s_q / sparse_window), sep_k: keys [0, sep_k) are visible to
+ * every query (a mask tensor: s_k) }. */
+int cogv_attention_plan(const cogv_attn_desc* d, int backward, int out[8]);
 size_t cogv_attention_keep_bits_bytes(int B, int H, int s_q, int s_k);
 /* Decode step (generation/sampling.py:139-148: one model call per generated token; mems mpu/sparse_transformer.py:526-546):
  * ONE query token per batch row against a fixed-capacity key/value cache.  qkv: the QKV projection of the new token,

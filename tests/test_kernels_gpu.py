@@ -889,3 +889,53 @@ def test_gemv_with_layernorm_prologue(ops, dtype, M, K, N, post, gelu):
     if gelu:
         ref = O.gelu(ref.to(dtype).float())
     assert rel(out, ref) < TOL[dtype]
+
+
+def test_attention_launch_order_independence(ops):
+    """Every attention instantiation raises its own dynamic-LDS attribute at its first launch (attention.hip: attn_launch), so no
+    result may depend on which form ran first: forward and backward of the four forms (dense without dropout, regenerating, stored
+    keep bits, flexible: mask tensor and sparse training form) in both dtypes, in one order and then in the reverse order in the
+    same process, bit-identical.  B = 1, H = 3 (fewer units than XCDs: idle workgroups), s = 192 (a full and a half query block:
+    inactive waves); the sparse form at window 128, s = 256, 24 pivots + 2 windows = 280 slots."""
+    from cogview_amd import functional as F_
+    g = torch.Generator().manual_seed(192)
+    drop = (0.1, 77, 5)
+    s, w, times, n_piv = 192, 128, 2, 24
+    data = {}
+    for dtype in DTYPES:
+        q, k, v, dout = [dev(rnd((1, s, 3, 64), dtype, g)) for _ in range(4)]
+        mask = dev((torch.rand((1, s, s), generator=g) < 0.7).to(dtype))
+        sq, sk, sv, sdout = [dev(rnd((1, 2 * w, 3, 64), dtype, g)) for _ in range(4)]
+        pivot_idx = dev(torch.stack([torch.randperm(2 * w, generator=g)[:n_piv]]))
+        tab, inv = F_.sparse_pivot_plan(pivot_idx, 2 * w, w, times)
+        data[dtype] = (q, k, v, dout, mask, sq, sk, sv, sdout, tab, inv)
+
+    def run(form, dtype):
+        q, k, v, dout, mask, sq, sk, sv, sdout, tab, inv = data[dtype]
+        if form == "dense":
+            o, lse = ops.attention_fwd(q, k, v)
+            return (o, lse) + tuple(ops.attention_bwd(dout, q, k, v, o, lse))
+        if form == "regenerating":
+            o, lse = ops.attention_fwd(q, k, v, dropout=drop)
+            return (o, lse) + tuple(ops.attention_bwd(dout, q, k, v, o, lse, dropout=drop))
+        if form == "stored bits":
+            o, lse, bits = ops.attention_fwd(q, k, v, dropout=drop, keep_bits=True)
+            # the keep words the forward pass wrote: query q's words of key blocks 0 .. q // 64 (those of blocks above its wave's
+            # diagonal are never written and stay whatever the allocator handed out)
+            words = bits.view(torch.int32).view(1, 3, (s + 63) // 64, 2, s)
+            wrote = dev(torch.arange((s + 63) // 64).view(-1, 1, 1) <= (torch.arange(s) // 64).view(1, 1, -1)).expand_as(words)
+            return (o, lse, words[wrote]) + tuple(ops.attention_bwd(dout, q, k, v, o, lse, dropout=drop, keep_bits=bits))
+        if form == "mask tensor":
+            o, lse = ops.attention_fwd(q, k, v, mask=mask)
+            return (o, lse) + tuple(ops.attention_bwd(dout, q, k, v, o, lse, mask=mask))
+        sp = (w, n_piv, math.log(2 * w // n_piv))
+        o, lse = ops.attention_fwd(sq, sk, sv, kv_index=tab, sparse=sp, dropout=drop)
+        return (o, lse) + tuple(ops.sparse_attention_bwd(sdout, sq, sk, sv, o, lse, tab, sp, inv, times, dropout=drop))
+
+    order = [(f, d) for f in ("dense", "regenerating", "stored bits", "mask tensor", "sparse training") for d in DTYPES]
+    first = {key: [t.clone() for t in run(*key)] for key in order}
+    for key in reversed(order):
+        again = run(*key)
+        assert len(again) == len(first[key])
+        for i, (a, b) in enumerate(zip(again, first[key])):
+            assert torch.equal(a, b), (key, i)

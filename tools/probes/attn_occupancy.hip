@@ -16,8 +16,8 @@ template <typename K> static void report(const char* name, K kernel, int dyn) {
 }
 
 int main() {
-  report("attn_fwd<f16, dense, bits>", &attn_fwd_kernel<f16_t, false, 2>, NSTG * 2 * TILE);
-  report("attn_bwd_dq<f16, dense, bits>", &attn_bwd_dq_kernel<f16_t, false, 2>, ring_bytes(2 * TILE + 1024, true));
-  report("attn_bwd_dkdv<f16, dense, bits>", &attn_bwd_dkdv_kernel<f16_t, false, 2>, ring_bytes(2 * TILE + 1536, true));
+  report("attn_fwd<f16, dense, bits>", &attn_fwd_kernel<f16_t, false, 2>, FwdStage::dynamic_lds(0));
+  report("attn_bwd_dq<f16, dense, bits>", &attn_bwd_dq_kernel<f16_t, false, 2>, DqStage<true>::dynamic_lds(0));
+  report("attn_bwd_dkdv<f16, dense, bits>", &attn_bwd_dkdv_kernel<f16_t, false, 2>, DkdvStage<true>::dynamic_lds(0));
   return 0;
 }
