@@ -119,6 +119,17 @@ class SampleDesc(C.Structure):
     ]
 
 
+class ScoreDesc(C.Structure):
+    _fields_ = [
+        ("dtype", C.c_int), ("rows", C.c_int), ("vocab", C.c_int), ("row_stride", C.c_int64),
+        ("logits", C.c_void_p), ("target", C.c_void_p),
+        ("allow_lo", C.c_int), ("allow_hi", C.c_int),
+        ("group", C.c_int),
+        ("logp", C.c_void_p),
+        ("scores", C.c_void_p),
+    ]
+
+
 CONV_4X4_S2, CONV_1X1, CONVT_4X4_S2, CONV_3X3_S1 = 0, 1, 2, 3
 
 _vp, _i, _f, _u64, _i64, _sz = C.c_void_p, C.c_int, C.c_float, C.c_uint64, C.c_int64, C.c_size_t
@@ -180,6 +191,7 @@ SIGNATURES = {
     "cogv_nchw3_to_nhwc4_f32": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "cogv_embed_code_f32": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp]),
     "cogv_sample_logits": (_i, [C.POINTER(SampleDesc), _vp]),
+    "cogv_score_targets": (_i, [C.POINTER(ScoreDesc), _vp]),
     "cogv_conv1x1_to_rgb_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), _vp]),
 }
 

@@ -2,5 +2,5 @@
 from .decoder import GraphDecoder, SamplingDecoder                                        # noqa: F401
 from .id_space import IdSpace                                                              # noqa: F401
 from .sampling import (DeviceFiller, add_interlacing_beam_marks, filling_sequence, generate_on_device,  # noqa: F401
-                       get_batch, inverse_prompt_score, magnify, plan_device_fill, plan_device_generation, shrink_beams,
-                       top_k_logits)
+                       get_batch, inverse_prompt_score, inverse_prompt_score_on_device, magnify, plan_device_fill,
+                       plan_device_generation, post_selection_rows, rerank_generated, shrink_beams, top_k_logits)

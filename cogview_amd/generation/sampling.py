@@ -180,6 +180,87 @@ def inverse_prompt_score(model, seq, args, tokenizer=None):
         return torch.gather(log_probs, 2, tokens[:, first_text + 1:].unsqueeze(-1)).squeeze(-1).sum(dim=-1)
 
 
+def _score_chunks(num, max_rows):
+    """The row blocks one scoring forward takes each, by the rule of the reference's post_selection loop
+    (generate_samples.py:254-259): `num < mbz or num % mbz == 0`, then max(num // mbz, 1) blocks of mbz rows."""
+    if max_rows is None:
+        return [(0, num)]
+    mbz = int(max_rows)
+    if mbz <= 0:
+        raise ValueError(f"max_rows = {max_rows} must be positive")
+    if not (num < mbz or num % mbz == 0):
+        raise ValueError(f"{num} rows are neither fewer than max_rows = {mbz} nor a multiple of it (the reference's post_selection rule)")
+    return [(i * mbz, min((i + 1) * mbz, num)) for i in range(max(num // mbz, 1))]
+
+
+def inverse_prompt_score_on_device(model, seq, args, tokenizer=None, image_tokens=1024, max_rows=None):
+    """inverse_prompt_score with the softmax tail on the device (ops.score_targets, cogv_score_targets): same rows
+    ([BASE] [BOI1] image_tokens codes [EOI1] [ROI1] text...), same meaning, same result ([rows] fp32).  Embedding and
+    transformer run as in GPT2Model.forward; the hidden states are cut to the T text-predicting positions ([ROI1] .. L - 2)
+    BEFORE the tied output projection, so the logits are [rows, T, vocab] in the storage type -- no product over the image
+    positions, no fp32 copy -- and one launch scores them with the image codes excluded.  [ROI1] is checked in every row
+    (one comparison, one read-back).  max_rows: rows per forward (default: args.max_inference_batch_size when present, else
+    all), by the reference's post_selection rule.  Dense attention and one model-parallel partition; sparse (is_sparse = 2)
+    and model parallelism > 1 are inverse_prompt_score's."""
+    from .. import functional as F_
+    from .. import ops
+    tokenizer = tokenizer if tokenizer is not None else IdSpace()
+    _refuse_unsupported(args, use="inverse_prompt_score")
+    assert seq.dim() == 2
+    first_text = 2 + image_tokens + 1                            # index of [ROI1]: the text it scores starts right after
+    n_text = seq.shape[1] - 1 - first_text
+    if n_text < 1:
+        raise ValueError(f"rows of {seq.shape[1]} ids hold no text after [ROI1] (index {first_text}): nothing to score")
+    if bool((seq[:, first_text] != tokenizer['[ROI1]']).any()):
+        raise ValueError(f"[ROI1] is not at index {first_text} of every row")
+    if max_rows is None:
+        max_rows = getattr(args, "max_inference_batch_size", None)
+    gpt = _unwrap(model)
+    vocab = gpt.word_embeddings.weight.shape[0]
+    scores = torch.empty(seq.shape[0], dtype=torch.float32, device=seq.device)
+    with torch.no_grad():
+        for lo, hi in _score_chunks(seq.shape[0], max_rows):
+            tokens, attention_mask, position_ids = get_batch(seq[lo:hi], seq.device, args)
+            h0 = gpt.transformer.embed(tokens, position_ids, gpt.word_embeddings)
+            hL, *_ = gpt.transformer(h0, position_ids, attention_mask, None, None, 0, embedded=True)
+            logits = F_.tied_logits(hL[:, first_text:-1], gpt.word_embeddings.weight)
+            ops.score_targets(logits, tokens[:, first_text + 1:], allow=(tokenizer.img_tokenizer.num_tokens, vocab),
+                              group=n_text, scores=scores[lo:hi])
+    return scores
+
+
+def post_selection_rows(tokens, tokenizer, image_tokens=1024):
+    """Completed text-to-image rows [nb, L] laid out [ROI1] text... [BASE] [BOI1] codes... (what generate_on_device and
+    filling_sequence return) -> the rows inverse_prompt_score reads, [nb, 2 + image_tokens + 1 + 1 + len(text)] laid out
+    [BASE] [BOI1] codes [EOI1] [ROI1] text... (the reference's '[BASE] [BOI1] [Image]{} [EOI1] [ROI1] {}' template).  Tensor
+    ops on the rows' device, one read-back for the layout check."""
+    if tokens.dim() != 2 or tokens.shape[1] < image_tokens + 3:
+        raise ValueError(f"want rows [nb, 1 + len(text) + 2 + {image_tokens}], got {tuple(tokens.shape)}")
+    n = tokens.shape[1] - image_tokens                          # [ROI1] text [BASE] [BOI1]
+    head, codes = tokens[:, :n], tokens[:, n:]
+    ok = (head[:, 0] == tokenizer['[ROI1]']) & (head[:, n - 2] == tokenizer['[BASE]']) & (head[:, n - 1] == tokenizer['[BOI1]'])
+    ok = ok.all() & (codes >= 0).all() & (codes < tokenizer.img_tokenizer.num_tokens).all()
+    if not bool(ok):
+        raise ValueError(f"rows are not [ROI1] text [BASE] [BOI1] followed by {image_tokens} image codes")
+    mid = torch.tensor([tokenizer['[EOI1]'], tokenizer['[ROI1]']], dtype=tokens.dtype, device=tokens.device)
+    return torch.cat((head[:, n - 2:], codes, mid.expand(tokens.shape[0], 2), head[:, 1:n - 2]), dim=1)
+
+
+def rerank_generated(model, tokens, args, tokenizer=None, image_tokens=1024, keep=None, max_rows=None):
+    """Post-selection of generated candidates: the text-to-image rows of generate_on_device / filling_sequence, best first
+    by how well each image predicts its caption (inverse_prompt_score_on_device of post_selection_rows).  Returns
+    (tokens[order][:keep], scores[order][:keep], order[:keep]); `order` is a stable descending sort (-inf rows last),
+    everything stays on the device.  A returned row feeds magnify as it is: row[-image_tokens:] are the codes,
+    row[1:n - 2] (n = len(row) - image_tokens) the text."""
+    tokenizer = tokenizer if tokenizer is not None else IdSpace()
+    scores = inverse_prompt_score_on_device(model, post_selection_rows(tokens, tokenizer, image_tokens), args, tokenizer=tokenizer,
+                                            image_tokens=image_tokens, max_rows=max_rows)
+    order = torch.sort(scores, descending=True, stable=True)[1]
+    if keep is not None:
+        order = order[:int(keep)]
+    return tokens[order], scores[order], order
+
+
 # (row block, column block, lines to fill) of the nine overlapping 16 x 16 -> 32 x 32 windows, in generation order
 _MAGNIFY_WINDOWS = ((0, 0, 18), (0, 1, 30), (0, 2, 30), (1, 1, 30), (1, 0, 30), (1, 2, 30), (2, 0, 32), (2, 1, 32), (2, 2, 32))
 
@@ -293,15 +374,15 @@ def plan_device_fill(seq_l, tokenizer, vocab):
                 capacity=_plan_capacity(len(seq_l)))
 
 
-def _refuse_unsupported(args):
-    """What only filling_sequence does, refused before the model is touched."""
+def _refuse_unsupported(args, use="filling_sequence"):
+    """What only the host form (`use`) does, refused before the model is touched."""
     from ..mpu.initialize import mp_world_size_or_1
     if args.is_sparse == 2:
-        raise NotImplementedError("sparse generation (is_sparse = 2): use filling_sequence")
+        raise NotImplementedError(f"sparse generation (is_sparse = 2): use {use}")
     if args.is_sparse != 0:
         raise ValueError('set is_sparse==2 for inference.')
     if mp_world_size_or_1() > 1:
-        raise NotImplementedError("model parallelism > 1: use filling_sequence")
+        raise NotImplementedError(f"model parallelism > 1: use {use}")
 
 
 def _unwrap(model):

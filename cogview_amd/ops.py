@@ -1029,6 +1029,61 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
+# ------------------------------------------------------------------------------------------ candidate scoring
+def score_targets(logits, targets, allow=None, group=1, logp=None, scores=None):
+    """log p(target) per row of `logits` ([rows, vocab] or [b, t, vocab]; fp16 / bf16 / fp32; last dim contiguous) under a
+    softmax over the ids of `allow` = (lo, hi) only (default: all), and its sum over every `group` consecutive rows -- the
+    tail of the reference's inverse_prompt_score (generation/sampling.py:214-230) without the fp32 copy of the logits.
+    A target outside `allow` scores -inf.  The row stride is read from the tensor, so a slice of a larger logits tensor is
+    scored where it lies; a 3-D slice whose batch stride is not t row strides takes one launch per batch entry (t % group
+    must be 0 then).  targets: int64, one per row.  logp / scores: optional contiguous fp32 outputs ([rows] / [rows / group]).
+    Returns (logp [rows], scores [rows / group])."""
+    _need_gpu(logits, targets, logp, scores)
+    if logits.dim() not in (2, 3):
+        raise ValueError("logits: want [rows, vocab] or [b, t, vocab]")
+    assert logits.stride(-1) == 1, "logits: the vocabulary dimension must be contiguous"
+    v, group = logits.shape[-1], int(group)
+    # The kernel takes rows ONE stride apart.  Fold the tensor into (nb batch entries sb apart) x (nt rows st apart):
+    if logits.dim() == 2:
+        nb, nt, sb, st = 1, logits.shape[0], 0, logits.stride(0)
+    else:
+        (nb, nt), (sb, st) = logits.shape[:2], logits.stride()[:2]
+    if nt == 1:
+        nb, nt, st = 1, nb, sb                            # [b, 1, vocab]: the batch entries are the rows
+    n = nb * nt
+    if n == 1:
+        st = v                                            # one row: torch reports any stride for a dimension of size 1
+    if nb == 1 or sb == nt * st:
+        launches = [(0, 0, n)]                            # uniform stride (2-D, contiguous 3-D): one launch for all rows
+    elif group > 0 and nt % group == 0:
+        launches = [(i * sb, i * nt, nt) for i in range(nb)]    # a slice like big[:, 5:9, :]: one launch per batch entry, whose
+    else:                                                       # nt rows hold whole groups; (element offset, first row, rows)
+        raise ValueError(f"logits: a batch stride of {sb} with {nt} rows {st} apart needs t % group == 0 (or a copy)")
+    dev = logits.device
+    tgt = targets.reshape(-1).to(torch.int64).contiguous()
+    if tgt.numel() != n:
+        raise ValueError(f"targets: want {n} ids, one per row")
+    ng = n // group if group > 0 else 0
+    if logp is None:
+        logp = torch.empty(n, dtype=torch.float32, device=dev)
+    if scores is None:
+        scores = torch.empty(ng, dtype=torch.float32, device=dev)
+    for name, t, cnt in (("logp", logp, n), ("scores", scores, ng)):
+        if t.dtype != torch.float32 or t.numel() != cnt or not t.is_contiguous():
+            raise ValueError(f"{name}: want a contiguous fp32 tensor of {cnt} elements")
+    lo, hi = (0, v) if allow is None else (int(allow[0]), int(allow[1]))
+    d = L.ScoreDesc()
+    d.dtype, d.vocab, d.row_stride, d.allow_lo, d.allow_hi, d.group = dt_code(logits), v, st, lo, hi, group
+    for off, row0, rows in launches:
+        d.rows = rows
+        d.logits = logits.data_ptr() + off * logits.element_size()
+        d.target = tgt.data_ptr() + row0 * 8
+        d.logp = logp.data_ptr() + row0 * 4
+        d.scores = scores.data_ptr() + (row0 // group) * 4 if group > 0 else scores.data_ptr()
+        L.check(L.lib().cogv_score_targets(C.byref(d), _stream()), "cogv_score_targets")
+    return logp, scores
+
+
 _COUNTERS = {}
 
 

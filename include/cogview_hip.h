@@ -396,6 +396,27 @@ typedef struct cogv_sample_desc {
 } cogv_sample_desc;
 int cogv_sample_logits(const cogv_sample_desc* d, void* stream);
 
+/* ------------------------------------------------------------------ candidate scoring
+ * replaces the host tail of the post-selection score, generation/sampling.py:214-230 (logits.float(), -inf over the image
+ * codes, log_softmax, gather of the next token, sum over the text positions).  Per row of logits[rows][vocab]:
+ *   x_i = float(logit_i) for i in [allow_lo, allow_hi) (raw logits: no temperature); ids outside the range are excluded;
+ *   logp[row] = x_target - max - log(sum exp(x_i - max)) in fp32; a target outside the range gives -inf.
+ * scores[g] = logp[g * group] + ... + logp[g * group + group - 1], added in that order by one thread (a second launch on the
+ * same stream); it is formed from the stored per-row values, so scores != NULL needs logp != NULL.  The row is streamed, never
+ * held in registers: any vocab >= 1.  16-byte loads when `logits` and row_stride * sizeof(element) are multiples of 16, scalar
+ * loads otherwise.  Every sum has a fixed order and there are no floating-point atomics: same input, same bits.
+ * 1: null logits / target, rows <= 0, group <= 0, rows % group != 0, an empty or out-of-vocabulary allow range,
+ * row_stride < vocab;  3: rows > 65535. */
+typedef struct cogv_score_desc {
+  int dtype; int rows; int vocab; int64_t row_stride;   /* logits[rows][vocab], F16 | BF16 | F32, rows row_stride elements apart */
+  const void* logits; const int64_t* target;            /* target[rows]: the id whose log-probability is wanted */
+  int allow_lo; int allow_hi;                           /* ids outside [allow_lo, allow_hi) are excluded from the softmax (-inf) */
+  int group;                                            /* rows per scored sequence; rows % group == 0 */
+  float* logp;                                          /* [rows] (may be NULL when scores is NULL too) */
+  float* scores;                                        /* [rows / group] (may be NULL): sum of the group's logp */
+} cogv_score_desc;
+int cogv_score_targets(const cogv_score_desc* d, void* stream);
+
 /* ------------------------------------------------------------------ VQ-VAE tokenizer (fp32, exact-fp32 MFMA)
  * replaces the conv stacks of vqvae/vqvae_zc.py:121-129,159-164 (Encoder) and :172-192 (Decoder), the
  * nearest-code search :41-54 and embed_code :95-96 for the production config of vqvae/api.py:12-20.

@@ -4,7 +4,10 @@ one eager model call and host sampling per token), for one 1024-code image at ba
 scripts/text2image.sh).  `--sampler-only`: just the sampler kernel, 8 rows of 58 240 bf16 logits (for a rocprofv3 kernel
 trace of its own).  `--super-resolution`: one generation.magnify of a random 32 x 32 code map (nine windows, top_k 200,
 temperature 1.02, as the reference's scripts/super_resolution.sh) with fill=DeviceFiller and with filling_sequence
-(kv_cache=True), wall seconds per image for each and the split of the device form's decode replays."""
+(kv_cache=True), wall seconds per image for each and the split of the device form's decode replays.  `--post-selection`: the
+reference's three stages joined on the device -- eight candidates from generate_on_device, scored with inverse_prompt_score
+(the host tail: full logits in fp32) and with inverse_prompt_score_on_device in the same run (ms per candidate, largest score
+difference, peak allocated memory of each), ranked by rerank_generated, the best one magnified with fill=DeviceFiller."""
 import os, sys, time, types
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -27,7 +30,8 @@ dist.init_process_group("nccl", init_method="env://", world_size=1, rank=0)
 from cogview_amd import mpu
 from cogview_amd.fp16 import FP16_Module
 from cogview_amd.generation import (DeviceFiller, IdSpace, add_interlacing_beam_marks, filling_sequence, generate_on_device,
-                                    magnify, plan_device_fill)
+                                    inverse_prompt_score, inverse_prompt_score_on_device, magnify, plan_device_fill,
+                                    post_selection_rows, rerank_generated)
 from cogview_amd.model import GPT2Model
 mpu.initialize_model_parallel(1); torch.manual_seed(1); mpu.model_parallel_cuda_manual_seed(1)
 L, h, heads, V = 48, 2560, 40, 58240
@@ -67,6 +71,40 @@ if SR:
           f"{t_dev / (replays + len(plans)) * 1e3:.2f} ms per model call", flush=True)
     sys.exit(0)
 args = types.SimpleNamespace(temperature=1.0, top_k=200, top_p=0.0, is_sparse=0)
+
+if "--post-selection" in sys.argv:
+    nb, reps = 8, 3
+    seq = [ids["[ROI1]"]] + text + [ids["[BASE]"], ids["[BOI1]"]] + [-1] * 1024
+    add_interlacing_beam_marks(seq, nb=nb, period=3000)
+    out, _ = generate_on_device(model, torch.tensor(seq, device="cuda"), args, seed=1)
+    rows = post_selection_rows(out, ids)
+
+    def measure(fn):
+        fn()                                                                   # warm-up (first-use allocations)
+        torch.cuda.synchronize(); base = torch.cuda.memory_allocated(); torch.cuda.reset_peak_memory_stats()
+        t0 = time.time()
+        for _ in range(reps):
+            scores = fn()
+        torch.cuda.synchronize()
+        return scores, (time.time() - t0) / reps / nb * 1e3, (torch.cuda.max_memory_allocated() - base) / 2 ** 20
+
+    s_host, ms_host, mb_host = measure(lambda: inverse_prompt_score(model, rows, args))
+    s_dev, ms_dev, mb_dev = measure(lambda: inverse_prompt_score_on_device(model, rows, args))
+    print(f"post-selection, {nb} candidates of {rows.shape[1]} ids ({rows.shape[1] - 1028} scored text positions): "
+          f"inverse_prompt_score {ms_host:.2f} ms/candidate, peak {mb_host:.0f} MiB above the model; "
+          f"inverse_prompt_score_on_device {ms_dev:.2f} ms/candidate, peak {mb_dev:.0f} MiB; "
+          f"largest |score difference| {(s_host - s_dev).abs().max().item():.3e} (scores {s_dev.min().item():.2f} .. {s_dev.max().item():.2f})")
+    best, sc, order = rerank_generated(model, out, args, keep=1)
+    n = best.shape[1] - 1024
+    sr_args = types.SimpleNamespace(temperature=1.02, top_k=200, top_p=0.0, is_sparse=0)
+    torch.cuda.synchronize(); t0 = time.time()
+    big = magnify(model, ids, best[0, -1024:], best[0, 1:n - 2], sr_args, fill=DeviceFiller(model, sr_args, seed=1))
+    torch.cuda.synchronize()
+    assert big.shape == (1, 4096) and int(big.max()) < 8192 and int(order[0]) == int(s_dev.argmax())
+    print(f"generate_on_device -> rerank_generated (kept candidate {int(order[0])}, score {sc[0].item():.2f}) -> magnify with "
+          f"DeviceFiller: {time.time() - t0:.2f} s for the 64 x 64 codes", flush=True)
+    sys.exit(0)
+
 for nb in (1, 8):
     seq = text + [ids["[BASE]"], ids["[BOI1]"]] + [-1] * 1024
     add_interlacing_beam_marks(seq, nb=nb, period=3000)
