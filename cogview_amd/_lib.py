@@ -68,6 +68,10 @@ class LnPrologue(C.Structure):
     ]
 
 
+class W8Weight(C.Structure):
+    _fields_ = [("q", C.c_void_p), ("ldq", C.c_int), ("scale", C.c_void_p)]
+
+
 class AttnDecodeDesc(C.Structure):
     _fields_ = [
         ("dtype", C.c_int), ("B", C.c_int), ("H", C.c_int), ("capacity", C.c_int), ("head_dim", C.c_int),
@@ -163,6 +167,10 @@ SIGNATURES = {
     "cogv_gemv_ln": (_i, [C.POINTER(GemmDesc), C.POINTER(LnPrologue), _vp]),
     "cogv_gemv_attn": (_i, [C.POINTER(GemmDesc), _vp, _i, _i, _vp]),
     "cogv_attention_decode": (_i, [C.POINTER(AttnDecodeDesc), _vp]),
+    "cogv_quantize_rows_e4m3": (_i, [_i, _vp, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "cogv_gemm_w8": (_i, [C.POINTER(GemmDesc), C.POINTER(W8Weight), _vp]),
+    "cogv_gemv_ln_w8": (_i, [C.POINTER(GemmDesc), C.POINTER(LnPrologue), C.POINTER(W8Weight), _vp]),
+    "cogv_gemv_attn_w8": (_i, [C.POINTER(GemmDesc), C.POINTER(W8Weight), _vp, _i, _i, _vp]),
     "cogv_attention_decode_workspace_bytes": (_sz, [_i, _i, _i]),
     "cogv_attention_keep_bits_bytes": (_sz, [_i, _i, _i, _i]),
     "cogv_sparse_slot_reduce": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i64, _i, _i, _i, _i, _i, _i, _i, _vp]),

@@ -44,6 +44,8 @@ def sources():
 EXTRA_UNITS = [("gemm.hip", f"gemm_w4_{k}.o", [f"-DCOGV_W4_TU={k}"]) for k in range(8)]
 # the skinny-M kernels of the decode step, one unit per dtype (gemv.hip is empty without the macro)
 EXTRA_UNITS += [("gemv.hip", f"gemv_{k}.o", [f"-DCOGV_GEMV_TU={k}"]) for k in range(2)]
+# the same kernels on 8-bit (E4M3) weights: units of their own, so that the 16-bit units compile what they always did
+EXTRA_UNITS += [("gemv.hip", f"gemv_w8_{k}.o", [f"-DCOGV_GEMV_TU={k}", "-DCOGV_GEMV_W8=1"]) for k in range(2)]
 
 
 def units():

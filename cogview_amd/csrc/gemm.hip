@@ -479,6 +479,70 @@ extern "C" int cogv_gemv_attn(const cogv_gemm_desc* d, const void* partials, int
   return cogv_check_launch();
 }
 
+// ---- the three skinny-M products on an 8-bit weight operand (gemv.hip, FormV8 / FormM8; units gemv_w8_<dtype>.o).  The operand
+//      travels in the argument block as B / ldb / wscale.  No first-generation kernel stands behind these: what the launchers
+//      do not take is COGV_ERR_UNSUPPORTED.
+extern "C" __attribute__((visibility("hidden"))) int cogv_gemv2_w8_launch_0(const void* args, void* stream);
+extern "C" __attribute__((visibility("hidden"))) int cogv_gemv2_w8_launch_1(const void* args, void* stream);
+extern "C" __attribute__((visibility("hidden"))) int cogv_gemv2_w8_attn_launch_0(const void* args, const float* partials, int heads, int nsplit, void* stream);
+extern "C" __attribute__((visibility("hidden"))) int cogv_gemv2_w8_attn_launch_1(const void* args, const float* partials, int heads, int nsplit, void* stream);
+extern "C" __attribute__((visibility("hidden"))) int cogv_gemv2_w8_ln_launch_0(const void* args, int stream_f32, void* stream);
+extern "C" __attribute__((visibility("hidden"))) int cogv_gemv2_w8_ln_launch_1(const void* args, int stream_f32, void* stream);
+
+// the descriptor with the 8-bit operand in B's place -> argument block; `allowed`: the epilogue flags the product takes
+static int build_w8_args(const cogv_gemm_desc* d, const cogv_w8_weight* w, int allowed, bool has_a, GemmArgs& a) {
+  if (!d || !w || !w->q || !w->scale) return COGV_ERR_ARG;
+  if (d->M > GEMV_MAX_M || (d->N & 7) || (d->K & 511) || d->trans_a || d->trans_b || (d->flags & ~allowed) || d->out_f32 || d->splitk > 1)
+    return COGV_ERR_UNSUPPORTED;
+  if ((w->ldq & 15) || (((uintptr_t)w->q | (uintptr_t)w->scale) & 15)) return COGV_ERR_ARG;
+  cogv_gemm_desc dd = *d;
+  dd.B = w->q; dd.ldb = w->ldq;
+  if (!has_a) { dd.A = dd.B; dd.lda = dd.K; }          // (no A operand: keep build_gemm_args' pointer checks happy)
+  const int rc = build_gemm_args(&dd, a);
+  if (rc != COGV_OK) return rc;
+  a.splitk = 1;
+  a.wscale = w->scale;
+  return COGV_OK;
+}
+
+extern "C" int cogv_gemm_w8(const cogv_gemm_desc* d, const cogv_w8_weight* w, void* stream) {
+  GemmArgs a;
+  const int rc = build_w8_args(d, w, COGV_EPI_BIAS | COGV_EPI_GELU | COGV_EPI_ABSMAX, true, a);
+  if (rc != COGV_OK) return rc;
+  if (d->aux) return COGV_ERR_UNSUPPORTED;
+  const int rc2 = d->dtype == COGV_F16 ? cogv_gemv2_w8_launch_1(&a, stream) : cogv_gemv2_w8_launch_0(&a, stream);
+  return rc2 != COGV_OK ? rc2 : cogv_check_launch();
+}
+
+extern "C" int cogv_gemv_ln_w8(const cogv_gemm_desc* d, const cogv_ln_prologue* ln, const cogv_w8_weight* w, void* stream) {
+  if (!ln) return COGV_ERR_ARG;
+  GemvLnArgs a;
+  const int rc = build_w8_args(d, w, COGV_EPI_BIAS | COGV_EPI_GELU | COGV_EPI_ABSMAX, false, a.g);
+  if (rc != COGV_OK) return rc;
+  if (d->aux || a.g.K > 4096) return COGV_ERR_UNSUPPORTED;
+  if (!ln->z || !ln->gamma || !ln->beta) return COGV_ERR_ARG;
+  if (ln->gamma_post && (!ln->beta_post || !ln->residual)) return COGV_ERR_ARG;
+  if (((uintptr_t)ln->z | (uintptr_t)ln->gamma | (uintptr_t)ln->beta | (uintptr_t)ln->gamma_post | (uintptr_t)ln->beta_post |
+       (uintptr_t)ln->residual | (uintptr_t)ln->t_out) & 15) return COGV_ERR_ARG;
+  a.z = ln->z; a.z_absmax = ln->z_absmax; a.gamma_p = ln->gamma_post; a.beta_p = ln->beta_post; a.res = ln->residual;
+  a.t_out = ln->t_out; a.gamma = ln->gamma; a.beta = ln->beta; a.eps = ln->eps;
+  const int sf = ln->stream_f32 != 0;
+  const int rc2 = d->dtype == COGV_F16 ? cogv_gemv2_w8_ln_launch_1(&a, sf, stream) : cogv_gemv2_w8_ln_launch_0(&a, sf, stream);
+  return rc2 != COGV_OK ? rc2 : cogv_check_launch();
+}
+
+extern "C" int cogv_gemv_attn_w8(const cogv_gemm_desc* d, const cogv_w8_weight* w, const void* partials, int heads, int capacity, void* stream) {
+  if (!partials || heads <= 0 || capacity <= 0 || capacity > 4096 || ((uintptr_t)partials & 15)) return COGV_ERR_ARG;
+  GemmArgs a;
+  const int rc = build_w8_args(d, w, COGV_EPI_BIAS | COGV_EPI_ABSMAX, false, a);
+  if (rc != COGV_OK) return rc;
+  if (a.K != heads * 64) return COGV_ERR_UNSUPPORTED;
+  const int nsplit = (capacity + 127) / 128;
+  const float* pw = reinterpret_cast<const float*>(partials);
+  const int rc2 = d->dtype == COGV_F16 ? cogv_gemv2_w8_attn_launch_1(&a, pw, heads, nsplit, stream) : cogv_gemv2_w8_attn_launch_0(&a, pw, heads, nsplit, stream);
+  return rc2 != COGV_OK ? rc2 : cogv_check_launch();
+}
+
 // Several GEMMs of the same dtype and layout in one persistent launch of the generation-3 kernel (see GroupArgs).
 // Every problem must satisfy that kernel's requirements (M, N >= 256, K % 64 == 0, operands < 4 GiB); otherwise
 // COGV_ERR_UNSUPPORTED and the caller issues them one by one.

@@ -23,7 +23,10 @@ struct GemmArgs {
   uint32_t thr16;       // dropout threshold (0 => keep all)
   float keep_scale;
   float* colsum_ws;     // COGV_EPI_COLSUM partial sums [2 * tiles_m(256)][N] fp32
-  float* ws;            // split-K slabs [S][M][N] fp32
+  union {               // (one slot: the skinny-M products never split K, so the layout of the block stays what it was)
+    float* ws;            // split-K slabs [S][M][N] fp32
+    const float* wscale;  // 8-bit weight operand (gemv.hip, FormV8 / FormM8): B is uint8 E4M3 [N][ldb], wscale [N] its row scales
+  };
   int splitk;
   int ktiles_per_split;
   int tiles_m, tiles_n;

@@ -27,7 +27,16 @@
 // The three kernels use the same association for the same K, so the combine-prologue form and the two-launch form of the
 // attention-output projection still agree bit for bit (tests/test_kernels_gpu.py).
 //
-// Compiled as two translation units (-DCOGV_GEMV_TU=0: bf16, 1: fp16; build.py); without the macro this file is empty.
+// 8-BIT WEIGHTS (FormV8 / FormM8: B as OCP E4M3 bytes with one fp32 scale per row, cogv_quantize_rows_e4m3).  The decode step is
+// a weight stream, so half the bytes is the lever that is left: the same three kernels, instantiated on two more forms -- the
+// prologues do not know what a weight is.  The bytes are converted in registers (v_cvt_pk_f32_fp8, exact), the arithmetic and
+// every rounding point stay those of the 16-bit form, and the fp32 sum of column n is multiplied by scale[n] once, in front
+// of the shared epilogue.  A slot of the same shape holds half the bytes, so the class table changes to keep 16-20 KB in flight
+// per wave: FormV8 gives a wave twice the columns (8-byte slots: a lane keeps FormV's 8 contraction elements), FormM8 gives a
+// 16-column tile half the waves (a 16-byte load is two MFMA fragments).  The table stands in front of the launchers below.
+//
+// Compiled as two translation units (-DCOGV_GEMV_TU=0: bf16, 1: fp16; build.py) for the 16-bit forms and two more with
+// -DCOGV_GEMV_W8 for the 8-bit forms; without the macro this file is empty.
 #include "gemm_shared.cuh"
 
 #include <cstdlib>
@@ -223,6 +232,205 @@ struct FormM {
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     accumulate<0, LMAX>(r, xs, XS, K, 0, wave, lane, acc);
     finish(acc, p, sh, n0, wave, lane, bias_pre);
+  }
+};
+
+// =====================================================================================================================
+// 8-bit weight operand (FormV8 / FormM8, see the file header): B is uint8 OCP E4M3 [N][ldb], p.wscale [N] fp32.
+// 8 E4M3 bytes -> 8 floats, exact (v_cvt_pk_f32_fp8: two bytes of the selected 16-bit half per instruction)
+__device__ __forceinline__ void unpack8_e4m3(uint32_t lo, uint32_t hi, float* f) {
+  const f32x2_t a = __builtin_amdgcn_cvt_pk_f32_fp8((int)lo, false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)lo, true);
+  const f32x2_t c = __builtin_amdgcn_cvt_pk_f32_fp8((int)hi, false), d = __builtin_amdgcn_cvt_pk_f32_fp8((int)hi, true);
+  f[0] = a[0]; f[1] = a[1]; f[2] = b[0]; f[3] = b[1]; f[4] = c[0]; f[5] = c[1]; f[6] = d[0]; f[7] = d[1];
+}
+__device__ __forceinline__ u32x2 gload8_stream(const void* q) {
+#if COGV_DECODE_NT
+  return __builtin_nontemporal_load((const COGV_GLOBAL u32x2*)q);
+#else
+  return *(const COGV_GLOBAL u32x2*)q;
+#endif
+}
+// the row scales of the 8 columns n .. n + 7 a finishing lane multiplies its sums by: requested BEHIND the weights (the memory
+// counter retires in order: they arrive right after the last weight, long before the sums are complete).  Unconditional, with a
+// clamped column, for gv2_bias's reason.
+struct Scale8 { f32x4 a, b; };
+__device__ __forceinline__ Scale8 gv2_scale(const GemmArgs& p, int n) {
+  const float* s = p.wscale + (n < p.N ? n : p.N - 8) + gv2_vzero();
+  return Scale8{*(const COGV_GLOBAL f32x4*)s, *(const COGV_GLOBAL f32x4*)(s + 4)};
+}
+
+// FormV8: FormV on 8-bit weights.  A lane's load is 8 BYTES = the same 8 contraction elements c * 512 + 8 lane .. + 7 of a
+// column as in FormV, so the x side, the fmaf chain and its order are FormV's; a slot is half as many bytes, so a wave owns
+// twice as many columns (J).  NW * J / 8 groups of 8 columns are finished by lanes 0 .. GPW - 1 of every wave.
+template <typename T, int J, int KCMAX, bool GUARD_, int MT, int NW_>
+struct FormV8 {
+  static constexpr int NW = NW_, COLS = NW_ * J, XPAD = 0, NS = KCMAX * J, XCHUNKS = KCMAX;
+  static constexpr int NG = (NW_ * J) / 8, GPW = (NG + NW_ - 1) / NW_;
+  static constexpr bool GUARD = GUARD_;
+  struct Regs { u32x2 w[NS]; };
+  struct Shared { float outp[MT][NW_ * J]; };
+  template <int S0, int S1>
+  static __device__ __forceinline__ void issue(Regs& r, const GemmArgs& p, int n0, int K, int wave, int lane) {
+    const uint8_t* B = reinterpret_cast<const uint8_t*>(p.B);
+    const int nw = n0 + wave * J, kc = K >> 9;
+#pragma unroll
+    for (int s = S0; s < S1; ++s) {
+      const int c = s / J, j = s % J;
+      const int n = nw + j < p.N ? nw + j : p.N - 1;
+      if (!GUARD || c < kc) r.w[s] = gload8_stream(B + (size_t)n * p.ldb + c * 512 + lane * 8);
+    }
+  }
+  static __device__ __forceinline__ u32x4 bias(const GemmArgs& p, int n0, int wave, int lane) {
+    return gv2_bias<T>(p, n0 + (wave * GPW + (lane < GPW ? lane : 0)) * 8);
+  }
+  static __device__ __forceinline__ void product(const Regs& r, const GemmArgs& p, const T* xs, int XS, int K, Shared& sh, int n0, int wave,
+                                                 int lane, const u32x4& bias_pre) {
+    const int kc = K >> 9;
+    const int g = wave * GPW + (lane < GPW ? lane : 0);           // the group of 8 columns this lane finishes (lanes < GPW)
+    const Scale8 sc = gv2_scale(p, n0 + g * 8);
+    float acc[MT][J];
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+      for (int j = 0; j < J; ++j) acc[m][j] = 0.f;
+#pragma unroll
+    for (int c = 0; c < KCMAX; ++c) {
+      if (!GUARD || c < kc) {
+        float x[MT][8];
+#pragma unroll
+        for (int m = 0; m < MT; ++m) unpack8<T>(*reinterpret_cast<const u32x4*>(xs + (size_t)m * XS + c * 512 + lane * 8), x[m]);
+#pragma unroll
+        for (int j = 0; j < J; ++j) {
+          float wf[8];
+          unpack8_e4m3(r.w[c * J + j][0], r.w[c * J + j][1], wf);
+#pragma unroll
+          for (int m = 0; m < MT; ++m) {
+            float t = acc[m][j];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) t = fmaf(x[m][e], wf[e], t);
+            acc[m][j] = t;
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+      for (int j = 0; j < J; ++j) {
+        const float t = wave_sum_uniform(acc[m][j]);
+        if (lane == 0) sh.outp[m][wave * J + j] = t;
+      }
+    __syncthreads();
+    if (lane < GPW && g < NG) {
+      const int n = n0 + g * 8;
+      if (n < p.N) {
+        const float s8[8] = {sc.a[0], sc.a[1], sc.a[2], sc.a[3], sc.b[0], sc.b[1], sc.b[2], sc.b[3]};
+        uint32_t am = 0u;
+        for (int m = 0; m < p.M && m < MT; ++m) {
+          float v[8];
+#pragma unroll
+          for (int i = 0; i < 8; ++i) v[i] = sh.outp[m][g * 8 + i] * s8[i];      // the row scale, once, in front of the shared epilogue
+          am = absmax_pk(am, epilogue8<T>(p, m, n, v, &bias_pre));
+        }
+        if (p.flags & COGV_EPI_ABSMAX) {
+          const uint32_t wv = max(am & 0xffffu, am >> 16);
+          atomic_max_nonneg(p.absmax, bits_to_f<T>((uint16_t)wv));
+        }
+      }
+    }
+  }
+};
+
+// FormM8: FormM on 8-bit weights.  A lane's 16-byte load holds 16 contraction elements of its row: TWO fragments.  Load i of
+// a wave covers the 64-element block kblock(kw, i) of the tile's 16 rows (blocks in pairs: one 128-byte line of a row); lane l
+// supplies row (l & 15), elements 16 (l >> 4) .. + 15 of the block -- the first 8 to one v_mfma_f32_16x16x32 and the last 8
+// to the next, and the x operand of each takes the same 8 elements of its row from LDS (a contraction is a sum over all slots:
+// any slot-to-lane mapping serves as long as both operands use it).  E4M3 -> T is exact (fp16 and bf16 hold every E4M3 value),
+// through fp32 in registers.  Everything behind the accumulator is FormM's, with the row scale in front of the epilogue.
+template <typename T, int NWK, int TW, int LMAX, bool GUARD_, int MT>
+struct FormM8 {
+  static constexpr int NW = NWK * TW, COLS = 16 * TW, XPAD = 8, NS = LMAX, XCHUNKS = (LMAX * NWK * 64 + 511) / 512;
+  static constexpr bool GUARD = GUARD_;
+  struct Regs { u32x4 w[LMAX]; };
+  struct Shared { f32x4 red[NW][64]; float outp[TW][16][16]; };
+  static __device__ __forceinline__ int kblock(int kw, int i) { return 2 * (kw + NWK * (i >> 1)) + (i & 1); }
+  template <int S0, int S1>
+  static __device__ __forceinline__ void issue(Regs& r, const GemmArgs& p, int n0, int K, int wave, int lane) {
+    const int L = K / (64 * NWK), kw = wave % NWK, nt = n0 + (wave / NWK) * 16 + (lane & 15);
+    const int n = nt < p.N ? nt : p.N - 1;
+    const uint8_t* row = reinterpret_cast<const uint8_t*>(p.B) + (size_t)n * p.ldb + (lane >> 4) * 16;
+#pragma unroll
+    for (int i = S0; i < S1; ++i)
+      if (!GUARD || i < L) r.w[i] = gload16(row + 64 * kblock(kw, i));
+  }
+  static __device__ __forceinline__ u32x4 bias(const GemmArgs& p, int n0, int wave, int lane) {
+    return gv2_bias<T>(p, n0 + (wave / NWK) * 16 + (lane & 1) * 8);
+  }
+  static __device__ __forceinline__ typename HT<T>::v8 frag(uint32_t lo, uint32_t hi) {
+    float f[8];
+    unpack8_e4m3(lo, hi, f);
+    return __builtin_bit_cast(typename HT<T>::v8, pack8<T>(f));
+  }
+  template <int I0, int I1>
+  static __device__ __forceinline__ void accumulate(const Regs& r, const T* xs, int XS, int K, int kofs, int wave, int lane, f32x4& acc) {
+    typedef typename HT<T>::v8 v8;
+    const int L = K / (64 * NWK), kw = wave % NWK;
+    const int mrow = (lane & 15) < MT ? (lane & 15) : MT - 1;
+    const T* xrow = xs + (size_t)mrow * XS + (lane >> 4) * 16 - kofs;
+#pragma unroll
+    for (int i = I0; i < I1; ++i) {
+      if (!GUARD || i < L) {
+        const T* xb = xrow + 64 * kblock(kw, i);
+        const v8 b0 = *reinterpret_cast<const v8*>(xb), b1 = *reinterpret_cast<const v8*>(xb + 8);
+        acc = HT<T>::mfma16(frag(r.w[i][0], r.w[i][1]), b0, acc);
+        acc = HT<T>::mfma16(frag(r.w[i][2], r.w[i][3]), b1, acc);
+      }
+    }
+  }
+  static __device__ __forceinline__ Scale8 scale(const GemmArgs& p, int n0, int wave, int lane) {
+    return gv2_scale(p, n0 + (wave / NWK) * 16 + (lane & 1) * 8);
+  }
+  // (the two-halves kernel calls this form: its scales are requested here, in the tail)
+  static __device__ __forceinline__ void finish(f32x4 acc, const GemmArgs& p, Shared& sh, int n0, int wave, int lane, const u32x4& bias_pre) {
+    finish(acc, p, sh, n0, wave, lane, bias_pre, scale(p, n0, wave, lane));
+  }
+  static __device__ __forceinline__ void finish(f32x4 acc, const GemmArgs& p, Shared& sh, int n0, int wave, int lane, const u32x4& bias_pre,
+                                                const Scale8& sc) {
+    const int tile = wave / NWK, kw = wave % NWK;
+    sh.red[wave][lane] = acc;
+    __syncthreads();
+    if (kw == 0) {
+      f32x4 s = sh.red[tile * NWK][lane];
+#pragma unroll
+      for (int w = 1; w < NWK; ++w) s += sh.red[tile * NWK + w][lane];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) sh.outp[tile][lane & 15][(lane >> 4) * 4 + i] = s[i];
+    }
+    __syncthreads();
+    if (kw == 0) {
+      const int m = lane >> 1, n = n0 + tile * 16 + (lane & 1) * 8;
+      uint32_t am = 0u;
+      if (m < p.M && m < MT && n < p.N) {
+        const float s8[8] = {sc.a[0], sc.a[1], sc.a[2], sc.a[3], sc.b[0], sc.b[1], sc.b[2], sc.b[3]};
+        float v[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = sh.outp[tile][m][(lane & 1) * 8 + i] * s8[i];
+        am = epilogue8<T>(p, m, n, v, &bias_pre);
+      }
+      if (p.flags & COGV_EPI_ABSMAX) {
+        uint32_t wv = max(am & 0xffffu, am >> 16);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) wv = max(wv, (uint32_t)__shfl_xor((int)wv, o, 64));
+        if (lane == 0) atomic_max_nonneg(p.absmax, bits_to_f<T>((uint16_t)wv));
+      }
+    }
+  }
+  static __device__ __forceinline__ void product(const Regs& r, const GemmArgs& p, const T* xs, int XS, int K, Shared& sh, int n0, int wave,
+                                                 int lane, const u32x4& bias_pre) {
+    const Scale8 sc = scale(p, n0, wave, lane);
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    accumulate<0, LMAX>(r, xs, XS, K, 0, wave, lane, acc);
+    finish(acc, p, sh, n0, wave, lane, bias_pre, sc);
   }
 };
 
@@ -631,6 +839,7 @@ template <int NWK, int LMAX, bool G, int MT, int TW = 1> using FM = FormM<TT, NW
 #define GV2_CAT(a, b) GV2_CAT2(a, b)
 #define GV2_UNWRAP(...) __VA_ARGS__
 
+#ifndef COGV_GEMV_W8
 // C = epilogue(A B^T), M <= 8.  COGV_ERR_UNSUPPORTED: the caller falls back to the first-generation kernel.
 extern "C" __attribute__((visibility("hidden"))) int GV2_CAT(cogv_gemv2_launch_, COGV_GEMV_TU)(const void* args, void* stream) {
   const GemmArgs& a = *reinterpret_cast<const GemmArgs*>(args);
@@ -742,5 +951,146 @@ extern "C" __attribute__((visibility("hidden"))) int GV2_CAT(cogv_gemv2_ln_launc
 #undef GV2_LN
   return COGV_OK;
 }
+
+#else  // COGV_GEMV_W8: the same three kernels on the 8-bit forms (units gemv_w8_<dtype>.o; nothing above is instantiated here,
+       // and nothing below in the 16-bit units: their code is what it was)
+// Classes.  Bytes in flight per wave as in the 16-bit table; what halves is the number of waves that share a column block:
+//   one row   (FormV8, 4 waves, 8-byte slots):   K = 1024: J = 16 (32 slots, 16 KB)   2560: J = 8 (40, 20 KB)   4096: J = 4 (32, 16 KB)
+//                                                10240: J = 4 (80, 40 KB)   other K % 512 == 0: J = 4 guarded (<= 80; LN prologue: <= 32)
+//   2..8 rows (FormM8, 16-byte loads, NWK waves per 16 columns):   K = 1024: NWK = 2, L = 8   2560: NWK = 2, L = 20   4096: NWK = 4, L = 16
+//                                                10240: NWK = 8, L = 20   guarded: K <= 2560: NWK = 2, K <= 5120: NWK = 4 (L <= 20)
+//   x rows of more than 56 KB are staged in two halves (K = 10240 with 3 .. 8 rows, K = 4096 with 5 .. 8); the guarded classes and
+//   the prologue forms have no such kernel: COGV_ERR_UNSUPPORTED there (5 .. 8 rows above K = 3072).  There is no other kernel
+//   to fall back to: every shape outside this table is COGV_ERR_UNSUPPORTED.
+namespace {
+template <int J, int KCMAX, bool G> using FV8 = FormV8<TT, J, KCMAX, G, 1, 4>;
+template <int NWK, int LMAX, bool G, int MT, int TW = 1> using FM8 = FormM8<TT, NWK, TW, LMAX, G, MT>;
+// CALL(F, MT) for 2 / 4 / 8 rows with FormM8<NWK, TW, LMAX, G, MT>: TW2 / TW4 = tiles per workgroup at 2 and at 4 / 8 rows
+#define GV2_M8_SWITCH(mt, CALL, NWK_, LMAX_, G_, TW2_, TW4_)                \
+  do {                                                                      \
+    if ((mt) == 2) { CALL((FM8<NWK_, LMAX_, G_, 2, TW2_>), 2); }            \
+    else if ((mt) == 4) { CALL((FM8<NWK_, LMAX_, G_, 4, TW4_>), 4); }       \
+    else { CALL((FM8<NWK_, LMAX_, G_, 8, TW4_>), 8); }                      \
+  } while (0)
+inline bool gv2_w8_args_ok(const GemmArgs& a, int kmax) {
+  return a.M >= 1 && a.M <= GEMV_MAX_M && (a.K & 511) == 0 && a.K <= kmax && (a.N & 7) == 0 && (a.ldb & 15) == 0 && a.ldb >= a.K &&
+         a.wscale && (((uintptr_t)a.B | (uintptr_t)a.wscale) & 15) == 0;
+}
+}  // namespace
+
+extern "C" __attribute__((visibility("hidden"))) int GV2_CAT(cogv_gemv2_w8_launch_, COGV_GEMV_TU)(const void* args, void* stream) {
+  const GemmArgs& a = *reinterpret_cast<const GemmArgs*>(args);
+  const int mt = gv2_mt(a.M), kc = a.K >> 9;
+  if (!gv2_w8_args_ok(a, 10240)) return COGV_ERR_UNSUPPORTED;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+#define GV2_PLAIN(F_, MT_)                                                                                                   \
+  do {                                                                                                                       \
+    typedef GV2_UNWRAP F_ FF;                                                                                                \
+    const size_t shmem = (size_t)MT_ * (a.K + FF::XPAD) * 2;                                                                 \
+    if (shmem > GV2_MAX_SHMEM) return COGV_ERR_UNSUPPORTED;                                                                  \
+    hipLaunchKernelGGL((gemv2_kernel<TT, FF, MT_>), dim3((a.N + FF::COLS - 1) / FF::COLS), dim3(FF::NW * 64), shmem, st, a); \
+  } while (0)
+#define GV2_PLAIN_K2(F_, MT_)                                                                                                \
+  do {                                                                                                                       \
+    typedef GV2_UNWRAP F_ FF;                                                                                                \
+    const size_t shmem = (size_t)MT_ * (a.K / 2 + FF::XPAD) * 2;                                                             \
+    static bool attr = false;                                                                                                \
+    if (!attr) {                                                                                                             \
+      if (shmem > GV2_MAX_SHMEM &&                                                                                           \
+          hipFuncSetAttribute(reinterpret_cast<const void*>(&gemv2_k2_kernel<TT, FF, MT_>), hipFuncAttributeMaxDynamicSharedMemorySize, \
+                              (int)shmem) != hipSuccess)                                                                    \
+        return COGV_ERR_UNSUPPORTED;                                                                                         \
+      attr = true;                                                                                                           \
+    }                                                                                                                        \
+    hipLaunchKernelGGL((gemv2_k2_kernel<TT, FF, MT_>), dim3((a.N + FF::COLS - 1) / FF::COLS), dim3(FF::NW * 64), shmem, st, a); \
+  } while (0)
+  if (mt == 1) {
+    if (a.K == 1024) GV2_PLAIN((FV8<16, 2, false>), 1);
+    else if (a.K == 2560) GV2_PLAIN((FV8<8, 5, false>), 1);
+    else if (a.K == 4096) GV2_PLAIN((FV8<4, 8, false>), 1);
+    else if (a.K == 10240) GV2_PLAIN((FV8<4, 20, false>), 1);
+    else GV2_PLAIN((FV8<4, 20, true>), 1);
+  } else {
+    if (a.K == 1024) GV2_M8_SWITCH(mt, GV2_PLAIN, 2, 8, false, 1, 1);
+    else if (a.K == 2560) GV2_M8_SWITCH(mt, GV2_PLAIN, 2, 20, false, 1, 1);
+    else if (a.K == 4096) {
+      if (mt == 2) GV2_PLAIN((FM8<4, 16, false, 2>), 2);
+      else if (mt == 4) GV2_PLAIN((FM8<4, 16, false, 4>), 4);
+      else GV2_PLAIN_K2((FM8<4, 16, false, 8>), 8);
+    }
+    else if (a.K == 10240) {
+      if (mt == 2) GV2_PLAIN((FM8<8, 20, false, 2>), 2);
+      else if (mt == 4) GV2_PLAIN_K2((FM8<8, 20, false, 4>), 4);
+      else GV2_PLAIN_K2((FM8<8, 20, false, 8>), 8);
+    }
+    else if (kc <= 5) GV2_M8_SWITCH(mt, GV2_PLAIN, 2, 20, true, 1, 1);
+    else if (kc <= 10) GV2_M8_SWITCH(mt, GV2_PLAIN, 4, 20, true, 1, 1);
+    else return COGV_ERR_UNSUPPORTED;
+  }
+#undef GV2_PLAIN
+#undef GV2_PLAIN_K2
+  return COGV_OK;
+}
+
+extern "C" __attribute__((visibility("hidden"))) int GV2_CAT(cogv_gemv2_w8_attn_launch_, COGV_GEMV_TU)(const void* args, const float* partials, int heads,
+                                                                                                     int nsplit, void* stream) {
+  const GemmArgs& a = *reinterpret_cast<const GemmArgs*>(args);
+  const int mt = gv2_mt(a.M), kc = a.K >> 9;
+  if (!gv2_w8_args_ok(a, 10240) || nsplit > 32) return COGV_ERR_UNSUPPORTED;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+#define GV2_ATTN(F_, MT_)                                                                                                         \
+  do {                                                                                                                            \
+    typedef GV2_UNWRAP F_ FF;                                                                                                     \
+    const size_t shmem = (size_t)MT_ * (a.K + FF::XPAD) * 2;                                                                      \
+    if (shmem > GV2_MAX_SHMEM) return COGV_ERR_UNSUPPORTED;                                                                       \
+    hipLaunchKernelGGL((gemv2_attn_kernel<TT, FF, MT_>), dim3((a.N + FF::COLS - 1) / FF::COLS), dim3(FF::NW * 64), shmem, st, a,  \
+                       partials, heads, nsplit);                                                                                  \
+  } while (0)
+  // (for every (K, M) the association of cogv_gemv2_w8_launch: the combine-prologue form and the two-launch form of the projection
+  //  agree bit for bit -- a FormM8 class's arithmetic depends on NWK only, so the guarded NWK = 4 class stands in for K = 4096)
+  if (mt == 1) {
+    if (a.K == 1024) GV2_ATTN((FV8<16, 2, false>), 1);
+    else if (a.K == 2560) GV2_ATTN((FV8<8, 5, false>), 1);
+    else GV2_ATTN((FV8<4, 20, true>), 1);
+  } else {
+    if (a.K == 1024) GV2_M8_SWITCH(mt, GV2_ATTN, 2, 8, false, 1, 1);
+    else if (a.K == 2560) GV2_M8_SWITCH(mt, GV2_ATTN, 2, 20, false, 1, 1);
+    else if (kc <= 5) GV2_M8_SWITCH(mt, GV2_ATTN, 2, 20, true, 1, 1);
+    else if (kc <= 10) GV2_M8_SWITCH(mt, GV2_ATTN, 4, 20, true, 1, 1);
+    else return COGV_ERR_UNSUPPORTED;
+  }
+#undef GV2_ATTN
+  return COGV_OK;
+}
+
+extern "C" __attribute__((visibility("hidden"))) int GV2_CAT(cogv_gemv2_w8_ln_launch_, COGV_GEMV_TU)(const void* args, int stream_f32, void* stream) {
+  const GemvLnArgs& a = *reinterpret_cast<const GemvLnArgs*>(args);
+  const int mt = gv2_mt(a.g.M), kc = a.g.K >> 9;
+  if (!gv2_w8_args_ok(a.g, 4096)) return COGV_ERR_UNSUPPORTED;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+#define GV2_LN(F_, MT_)                                                                                                          \
+  do {                                                                                                                           \
+    typedef GV2_UNWRAP F_ FF;                                                                                                    \
+    const size_t shmem = (size_t)MT_ * (a.g.K + FF::XPAD) * 2;                                                                   \
+    if (shmem > GV2_MAX_SHMEM) return COGV_ERR_UNSUPPORTED;                                                                      \
+    const dim3 grid((a.g.N + FF::COLS - 1) / FF::COLS), block(FF::NW * 64);                                                      \
+    if (stream_f32) hipLaunchKernelGGL((gemv2_ln_kernel<TT, FF, MT_, true>), grid, block, shmem, st, a);                         \
+    else hipLaunchKernelGGL((gemv2_ln_kernel<TT, FF, MT_, false>), grid, block, shmem, st, a);                                   \
+  } while (0)
+  // (the prologue wants 4 or 8 waves: 2 tiles per workgroup at 2 rows, 4 at 4 and 8 rows -- the thread counts of the 16-bit table)
+  if (mt == 1) {
+    if (a.g.K == 1024) GV2_LN((FV8<16, 2, false>), 1);
+    else if (a.g.K == 2560) GV2_LN((FV8<8, 5, false>), 1);
+    else GV2_LN((FormV8<TT, 4, 8, true, 1, 4>), 1);
+  } else {
+    if (a.g.K == 1024) GV2_M8_SWITCH(mt, GV2_LN, 2, 8, false, 2, 4);
+    else if (a.g.K == 2560) GV2_M8_SWITCH(mt, GV2_LN, 2, 20, false, 2, 4);
+    else if (kc <= 5) GV2_M8_SWITCH(mt, GV2_LN, 2, 20, true, 2, 4);
+    else GV2_M8_SWITCH(mt, GV2_LN, 4, 20, true, 2, 2);
+  }
+#undef GV2_LN
+  return COGV_OK;
+}
+#endif  // COGV_GEMV_W8
 
 #endif  // COGV_GEMV_TU

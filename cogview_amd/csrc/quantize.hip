@@ -1,0 +1,55 @@
+// Row-wise 8-bit weight quantizer of the decode step's weight stream (cogv_quantize_rows_e4m3; consumed by the 8-bit forms of
+// gemv.hip).  W[N][K] in the 16-bit storage type -> q[N][K] as OCP E4M3 bytes ("e4m3fn": no infinities, largest value 448) and
+// one fp32 scale per row:
+//     scale[n] = max_k |W[n][k]| / 448   (fp32 division; 1.0 for an all-zero row)
+//     q[n][k]  = rne_e4m3( float(W[n][k]) / scale[n] )          (a true fp32 division, not a reciprocal multiply: a CPU reproduces
+//                                                                the bytes with the same two operations)
+// |w| / scale exceeds 448 by fp32 rounding error at most, which still rounds to 448: no value leaves the representable range.
+// One workgroup per row, two passes over it (the second is served by L2); the row maximum is taken on the bit patterns and
+// reduced through LDS in a fixed order -- no atomics.  Runs once per weight matrix when a decoder is built: not a hot path.
+#include "common.cuh"
+#include "cogview_hip.h"
+
+namespace {
+
+template <typename T>
+__global__ __launch_bounds__(256) void quantize_rows_e4m3_kernel(const T* __restrict__ w, int ldw, int K, uint8_t* __restrict__ q, int ldq,
+                                                                 float* __restrict__ scale) {
+  __shared__ uint32_t redm[16];
+  const int n = blockIdx.x, nvec = K >> 3;
+  const T* row = w + (size_t)n * ldw;
+  uint32_t m = 0u;
+  for (int v = threadIdx.x; v < nvec; v += 256) m = absmax_pk8(m, *reinterpret_cast<const u32x4*>(row + v * 8));
+  const float amax = absmax_pk_block<T>(m, redm);
+  const float s = amax == 0.f ? 1.0f : amax / 448.0f;
+  if (threadIdx.x == 0) scale[n] = s;
+  uint8_t* qrow = q + (size_t)n * ldq;
+  for (int v = threadIdx.x; v < nvec; v += 256) {
+    float f[8];
+    unpack8<T>(*reinterpret_cast<const u32x4*>(row + v * 8), f);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) f[i] = f[i] / s;
+    int lo = 0, hi = 0;
+    lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], lo, false);
+    lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], lo, true);
+    hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], hi, false);
+    hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], hi, true);
+    *reinterpret_cast<u32x2*>(qrow + v * 8) = u32x2{(uint32_t)lo, (uint32_t)hi};
+  }
+}
+
+}  // namespace
+
+extern "C" int cogv_quantize_rows_e4m3(int dtype, const void* w, int ldw, int N, int K, void* q, int ldq, float* scale, void* stream) {
+  if (!w || !q || !scale || N <= 0 || K <= 0) return COGV_ERR_ARG;
+  if ((K & 7) || (ldw & 7) || (ldq & 7) || ldw < K || ldq < K || ((uintptr_t)w & 15) || ((uintptr_t)q & 7) || ((uintptr_t)scale & 3)) return COGV_ERR_ARG;
+  if (dtype != COGV_F16 && dtype != COGV_BF16) return COGV_ERR_UNSUPPORTED;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (dtype == COGV_F16)
+    hipLaunchKernelGGL((quantize_rows_e4m3_kernel<f16_t>), dim3(N), dim3(256), 0, st, reinterpret_cast<const f16_t*>(w), ldw, K,
+                       reinterpret_cast<uint8_t*>(q), ldq, scale);
+  else
+    hipLaunchKernelGGL((quantize_rows_e4m3_kernel<bf16_t>), dim3(N), dim3(256), 0, st, reinterpret_cast<const bf16_t*>(w), ldw, K,
+                       reinterpret_cast<uint8_t*>(q), ldq, scale);
+  return cogv_check_launch();
+}

@@ -984,14 +984,46 @@ def decode_chain_supported(tr, batch):
             and tr.layers[0].input_layernorm.weight.dtype in (torch.float16, torch.bfloat16))
 
 
-def decode_chain(tr, h0, absmax0, slots, emb_weight):
+class W8Weights:
+    """The 8-bit copies a decode step streams instead of the 16-bit weights (ops.quantize_rows_e4m3; GraphDecoder(weights="e4m3")):
+    per layer the (q, scale) pairs of the four Linear weights, and one of the word-embedding matrix for the tied-logits product.
+    Biases, LayerNorm parameters and the embedding LOOKUP stay what they are."""
+
+    def __init__(self, tr, emb_weight):
+        quant = ops.quantize_rows_e4m3
+        self.layers = [(quant(l.attention.query_key_value.weight), quant(l.attention.dense.weight),
+                        quant(l.mlp.dense_h_to_4h.weight), quant(l.mlp.dense_4h_to_h.weight)) for l in tr.layers]
+        self.emb = quant(emb_weight)
+        self.dtype = emb_weight.dtype
+
+    def tensors(self):
+        return [t for lw in self.layers for qs in lw for t in qs] + list(self.emb)
+
+
+def w8_decode_supported(tr, batch):
+    """What the 8-bit skinny-M kernels cover (include/cogview_hip.h, cogv_gemm_w8): both contraction lengths of the model, h and
+    4h, at this row count.  Returns None, or the reason as a string."""
+    h = tr.layers[0].input_layernorm.weight.shape[0]
+    f = tr.layers[0].mlp.dense_h_to_4h.weight.shape[0]
+    if batch > 8:
+        return f"batch {batch} > 8 rows"
+    for k in (h, f):
+        if k % 512 or k > 10240 or (batch > 1 and k > 5120 and k not in (10240,)) or (batch > 4 and k > 3072 and k not in (4096, 10240)):
+            return f"contraction length {k} at {batch} row(s) is outside the 8-bit kernels' classes"
+    return None
+
+
+def decode_chain(tr, h0, absmax0, slots, emb_weight, w8=None):
     """One decode step through all layers with FIVE launches per layer (round 3: the split-combine of the decode attention
     rides in the dense GEMV's prologue): QKV GEMV with [previous layer's
     LN4 + residual, LN1] as prologue | decode attention, key splits (cache append fused) | dense GEMV with the combine as prologue | h->4h GEMV with [LN3 +
     residual, LN2] as prologue and GeLU epilogue | 4h->h GEMV; the last LN4 + residual and the final LayerNorm are the
     prologue of the tied-logits GEMV.  Same arithmetic and rounding points as the layer-by-layer path
     (mpu/sparse_transformer.py:314-342, 612; model/gpt2_modeling.py:115-118).  h0 [b, 1, h]; slots: StaticKVSlot per
-    layer.  Returns logits [b, 1, V]."""
+    layer.  Returns logits [b, 1, V].
+    w8 (W8Weights): the same five launches on the 8-bit copies of the weights (_decode_chain_w8)."""
+    if w8 is not None:
+        return _decode_chain_w8(tr, h0, absmax0, slots, w8)
     b, s, h = h0.shape
     assert s == 1
     dev = h0.device
@@ -1025,6 +1057,73 @@ def decode_chain(tr, h0, absmax0, slots, emb_weight):
     fl = tr.final_layernorm
     logits, _ = ops.gemv_ln(z, emb_weight, None, fl.weight, fl.bias, fl.eps, z_absmax, post, res)
     return logits.view(b, 1, emb_weight.shape[0])
+
+
+def _decode_chain_w8(tr, h0, absmax0, slots, w8):
+    """decode_chain on the 8-bit weights w8 (W8Weights): launch for launch the same chain, each product reading (q, scale) in
+    place of the 16-bit matrix."""
+    b, s, h = h0.shape
+    assert s == 1
+    z, z_absmax, post, res = h0.view(b, h), absmax0, None, None
+    for layer, slot, (w_qkv, w_dense, w_h4h, w_4hh) in zip(tr.layers, slots, w8.layers):
+        att_m, mlp_m = layer.attention, layer.mlp
+        eps = layer.input_layernorm.eps
+        npp = att_m.num_attention_heads_per_partition
+        hp = npp * 64
+        qkv, x = ops.gemv_ln_w8(z, w_qkv, att_m.query_key_value.bias, layer.input_layernorm.weight, layer.input_layernorm.bias, eps,
+                                z_absmax, post, res, want_t=post is not None)
+        if x is None:
+            x = z
+        if hp % 512 == 0 and _decode_fuse_combine():
+            parts = ops.attention_decode(qkv.view(b, 1, 3 * hp), slot.cache, slot.pos_index, npp, combine=False)
+            ao = ops.gemv_attn_w8(parts, b, npp, slot.cache.shape[1], w_dense, w8.dtype, bias=att_m.dense.bias)
+        else:
+            att = ops.attention_decode(qkv.view(b, 1, 3 * hp), slot.cache, slot.pos_index, npp)
+            ao = ops.gemm_w8(att.view(b, hp), w_dense, bias=att_m.dense.bias)
+        slot.out = slot.cache
+        g, y = ops.gemv_ln_w8(ao, w_h4h, mlp_m.dense_h_to_4h.bias, layer.post_attention_layernorm.weight,
+                              layer.post_attention_layernorm.bias, eps, None,
+                              (layer.third_layernorm.weight, layer.third_layernorm.bias), x, want_t=True, gelu=True)
+        mo = ops.gemm_w8(g, w_4hh, bias=mlp_m.dense_4h_to_h.bias)
+        z, z_absmax, post, res = mo, None, (layer.fourth_layernorm.weight, layer.fourth_layernorm.bias), y
+    fl = tr.final_layernorm
+    logits, _ = ops.gemv_ln_w8(z, w8.emb, None, fl.weight, fl.bias, fl.eps, z_absmax, post, res)
+    return logits.view(b, 1, w8.emb[0].shape[0])
+
+
+def decode_layers_w8(tr, h0, absmax0, slots, w8):
+    """One decode step layer by layer on the 8-bit weights: _layer_forward's inference chain for one token per row (every
+    Sandwich-LN its own launch, decode attention with its combine, four plain 8-bit products per layer), the final LayerNorm and
+    the tied-logits product.  What the 8-bit decoder runs above COGV_DECODE_CHAIN_MAX_ROWS, and the comparison path of the chain."""
+    b, s, h = h0.shape
+    assert s == 1
+    dev = h0.device
+    x, absmax_x = (h0 if h0.is_contiguous() else h0.contiguous()), absmax0
+    for layer, slot, (w_qkv, w_dense, w_h4h, w_4hh) in zip(tr.layers, slots, w8.layers):
+        att_m, mlp_m = layer.attention, layer.mlp
+        eps = layer.input_layernorm.eps
+        npp = att_m.num_attention_heads_per_partition
+        hp = npp * 64
+        a, _, _ = ops.sandwich_ln_fwd(x, layer.input_layernorm.weight, layer.input_layernorm.bias, eps, absmax_x, save_stats=False)
+        qkv = ops.gemm_w8(a.view(b, h), w_qkv, bias=att_m.query_key_value.bias).view(b, 1, 3 * hp)
+        att = ops.attention_decode(qkv, slot.cache, slot.pos_index, npp)
+        slot.out = slot.cache
+        slot_ao = ops.new_absmax_slot(dev)
+        ao = ops.gemm_w8(att.view(b, hp), w_dense, bias=att_m.dense.bias, absmax=slot_ao)
+        slot_y = ops.new_absmax_slot(dev)
+        y, _, _ = ops.sandwich_ln_fwd(ao.view(b, 1, h), layer.third_layernorm.weight, layer.third_layernorm.bias, eps, slot_ao,
+                                      residual=x, absmax_out=slot_y, save_stats=False)
+        c, _, _ = ops.sandwich_ln_fwd(y, layer.post_attention_layernorm.weight, layer.post_attention_layernorm.bias, eps, slot_y,
+                                      save_stats=False)
+        g = ops.gemm_w8(c.view(b, h), w_h4h, bias=mlp_m.dense_h_to_4h.bias, gelu=True)
+        slot_mo = ops.new_absmax_slot(dev)
+        mo = ops.gemm_w8(g, w_4hh, bias=mlp_m.dense_4h_to_h.bias, absmax=slot_mo)
+        absmax_x = ops.new_absmax_slot(dev)
+        x, _, _ = ops.sandwich_ln_fwd(mo.view(b, 1, h), layer.fourth_layernorm.weight, layer.fourth_layernorm.bias, eps, slot_mo,
+                                      residual=y, absmax_out=absmax_x, save_stats=False)
+    fl = tr.final_layernorm
+    out, _, _ = ops.sandwich_ln_fwd(x, fl.weight, fl.bias, fl.eps, absmax_x, save_stats=False)
+    return ops.gemm_w8(out.view(b, h), w8.emb).view(b, 1, w8.emb[0].shape[0])
 
 
 def transformer_layer_kv(layer, x, absmax_x, sep, kv_slot):

@@ -16,15 +16,47 @@ from .. import ops
 from ..mpu.transformer import StaticKVSlot
 
 
+WEIGHT_FORMATS = ("e4m3",)
+
+
+def refuse_w8_unsupported(weights, tr, batch):
+    """weights= of the decoders: what the 8-bit decode step does not cover, refused before anything is quantized."""
+    from ..mpu.initialize import mp_world_size_or_1
+    if weights not in WEIGHT_FORMATS:
+        raise ValueError(f"weights={weights!r}: None (16-bit) or one of {WEIGHT_FORMATS}")
+    if mp_world_size_or_1() > 1:
+        raise NotImplementedError(f"weights={weights!r} with model parallelism > 1: use the 16-bit decoder (weights=None)")
+    dt = tr.layers[0].attention.query_key_value.weight.dtype
+    if dt not in (torch.float16, torch.bfloat16):
+        raise NotImplementedError(f"weights={weights!r} on a {dt} model: the 8-bit step computes in fp16 / bf16")
+    why = F_.w8_decode_supported(tr, batch)
+    if why is not None:
+        raise NotImplementedError(f"weights={weights!r}: {why}")
+
+
 class GraphDecoder:
-    def __init__(self, model, batch=1, capacity=1152):
+    def __init__(self, model, batch=1, capacity=1152, weights=None):
         """model: GPT2Model (optionally inside FP16_Module) in eval mode, dense attention; capacity: slots per cache
-        (<= 4096, the gathered form's limit)."""
+        (<= 4096, the gathered form's limit).
+        weights="e4m3": the decode step streams 8-bit copies of the weights (OCP E4M3 bytes with one fp32 scale per row,
+        ops.quantize_rows_e4m3), made here, once: the four Linear weights of every layer and a copy of the word-embedding
+        matrix for the tied-logits product -- half the bytes a step reads.  The embedding lookup keeps the 16-bit table and
+        the prefill runs on the 16-bit weights (a GEMM, not a stream), so those stay resident: the copies ADD half the
+        model's size in device memory (about 4 GB at 4B).  Logits differ from the 16-bit step's by the quantization of the
+        weights.  One model-parallel partition, dense attention, fp16 / bf16, hidden sizes whose h and 4h the 8-bit kernels
+        cover (the model family's: 1024 and 2560).  None (default): nothing is allocated, the step is what it was."""
         m = model
         while hasattr(m, "module"):
             m = m.module
         self.gpt, tr = m, m.transformer
         assert capacity <= 4096
+        self.w8 = None
+        if weights is not None:
+            refuse_w8_unsupported(weights, tr, batch)
+            if m.word_embeddings.weight.shape[0] % 8:
+                raise NotImplementedError(f"weights={weights!r}: a vocabulary of {m.word_embeddings.weight.shape[0]} rows (not a multiple of 8)")
+            with torch.no_grad():
+                self.w8 = F_.W8Weights(tr, m.word_embeddings.weight)
         p0 = tr.layers[0].attention.query_key_value.weight
         hp = tr.layers[0].attention.hidden_size_per_partition
         dev, dt = p0.device, p0.dtype
@@ -47,6 +79,11 @@ class GraphDecoder:
         self.slab.zero_()
         with ops.scalar_slab(self.slab):
             h = tr.embed(self.tok, self.pos, self.gpt.word_embeddings)
+            if self.w8 is not None:
+                # the same two paths on the 8-bit copies of the weights
+                if self.fused and F_.decode_chain_supported(tr, self.batch):
+                    return F_.decode_chain(tr, h, h._cogv_absmax, self.slots, self.gpt.word_embeddings.weight, w8=self.w8)
+                return F_.decode_layers_w8(tr, h, h._cogv_absmax, self.slots, self.w8)
             if self.fused and F_.decode_chain_supported(tr, self.batch):
                 # five launches per layer: the LayerNorms ride as prologues of the GEMVs, the cache append inside the
                 # decode attention kernel (functional.decode_chain)
@@ -120,8 +157,8 @@ class SamplingDecoder(GraphDecoder):
     and a run of them needs no host work.  Reference path: generation/sampling.py:139-186 (model call, filter, multinomial,
     beam score) once per token.  Use start() + generate() (step() feeds tokens from the host and is not for this mode)."""
 
-    def __init__(self, model, batch=1, capacity=1152):
-        super().__init__(model, batch, capacity)
+    def __init__(self, model, batch=1, capacity=1152, weights=None):
+        super().__init__(model, batch, capacity, weights=weights)
         self.sampling = None
 
     def enable_sampling(self, temperature=1.0, top_k=0, top_p=0.0, allow=None, seed=0, out_tokens=None, out_base=0,

@@ -374,9 +374,17 @@ def plan_device_fill(seq_l, tokenizer, vocab):
                 capacity=_plan_capacity(len(seq_l)))
 
 
-def _refuse_unsupported(args, use="filling_sequence"):
+def _refuse_unsupported(args, use="filling_sequence", weights=None):
     """What only the host form (`use`) does, refused before the model is touched."""
     from ..mpu.initialize import mp_world_size_or_1
+    if weights is not None:
+        from .decoder import WEIGHT_FORMATS
+        if weights not in WEIGHT_FORMATS:
+            raise ValueError(f"weights={weights!r}: None (16-bit) or one of {WEIGHT_FORMATS}")
+        if args.is_sparse == 2:
+            raise NotImplementedError(f"sparse generation (is_sparse = 2) with weights={weights!r}: use {use}")
+        if mp_world_size_or_1() > 1:
+            raise NotImplementedError(f"model parallelism > 1 with weights={weights!r}: use {use}")
     if args.is_sparse == 2:
         raise NotImplementedError(f"sparse generation (is_sparse = 2): use {use}")
     if args.is_sparse != 0:
@@ -391,7 +399,7 @@ def _unwrap(model):
     return model
 
 
-def generate_on_device(model, seq, args, tokenizer=None, seed=0, capture=True):
+def generate_on_device(model, seq, args, tokenizer=None, seed=0, capture=True, weights=None):
     """filling_sequence for one run of generated tokens with the sampling on the device: prefill of the context (one row,
     its keys / values broadcast into the nb cache rows), nb independent first draws from its last logits, then one
     captured decode graph per token (generation/decoder.py SamplingDecoder) whose last launch filters, draws, and feeds
@@ -399,16 +407,17 @@ def generate_on_device(model, seq, args, tokenizer=None, seed=0, capture=True):
     row); the draws come from the package's counter-based generator keyed (seed, step, row), not torch.multinomial.
     Supported: dense attention (args.is_sparse == 0), one model-parallel partition, fp16 / bf16, <= 4096 positions.
     Returns (tokens [nb, len(seq)], scores [nb] fp32: the summed log-probabilities of the drawn ids), on seq's device.
-    capture=False runs the same launches eagerly (the reference for the captured form)."""
+    capture=False runs the same launches eagerly (the reference for the captured form).
+    weights="e4m3": the decode steps stream 8-bit copies of the weights (GraphDecoder's `weights`; the prefill stays 16-bit)."""
     from .decoder import SamplingDecoder
     tokenizer = tokenizer if tokenizer is not None else IdSpace()
-    _refuse_unsupported(args)
+    _refuse_unsupported(args, weights=weights)
     assert seq.dim() == 1
     plan = plan_device_generation(seq.tolist(), tokenizer, _unwrap(model).word_embeddings.weight.shape[0])
     n, run, nb = plan["context"], plan["run"], plan["nb"]
     tokens, attention_mask, position_ids = get_batch(seq[:n], seq.device, args)
     position_ids[position_ids > plan["offset"]] -= plan["offset"]
-    dec = SamplingDecoder(model, batch=nb, capacity=plan["capacity"])
+    dec = SamplingDecoder(model, batch=nb, capacity=plan["capacity"], weights=weights)
     out = torch.empty((nb, run), dtype=torch.long, device=tokens.device)
     dec.enable_sampling(args.temperature, args.top_k, args.top_p, plan["allow"], seed, out_tokens=out, out_base=n)
     with torch.no_grad():
@@ -433,19 +442,21 @@ class DeviceFiller:
     Same filter as filling_sequence; draws from the package's counter-based generator keyed (seed, step, row).  Dense
     attention, one model-parallel partition, <= capacity positions (1408: the reference's MAXSEQLEN 1345 rounded up to 64).
     capture=False runs the same launches eagerly.  After a call, .scores is [1] fp32: the summed log-probability of the
-    drawn ids (given ids add nothing)."""
+    drawn ids (given ids add nothing).  weights="e4m3": the decode steps stream 8-bit copies of the weights (GraphDecoder's
+    `weights`), made when the first call builds the decoder."""
 
-    def __init__(self, model, args, seed=0, capacity=1408, capture=True):
-        _refuse_unsupported(args)
+    def __init__(self, model, args, seed=0, capacity=1408, capture=True, weights=None):
+        _refuse_unsupported(args, weights=weights)
         if not 0 < capacity <= 4096:
             raise ValueError(f"capacity {capacity} outside (0, 4096]: the decode cache's limit")
         self.model, self.seed, self.capacity, self.capture = model, int(seed), int(capacity), capture
+        self.weights = weights
         self.dec, self.key, self.scores = None, None, None
 
     def _decoder(self, args, allow):
         from .decoder import SamplingDecoder
         if self.dec is None:
-            self.dec = SamplingDecoder(self.model, batch=1, capacity=self.capacity)
+            self.dec = SamplingDecoder(self.model, batch=1, capacity=self.capacity, weights=self.weights)
             dev = self.dec.tok.device
             self.out = torch.empty((1, self.capacity), dtype=torch.long, device=dev)
             self.given = torch.full((self.capacity,), -1, dtype=torch.long, device=dev)

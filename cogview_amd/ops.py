@@ -669,6 +669,97 @@ def gemv_attn(partials, batch, heads, capacity, w, bias=None, absmax=None):
     return out
 
 
+# ------------------------------------------------------------------------------------------ 8-bit weights (decode step)
+def quantize_rows_e4m3(w):
+    """cogv_quantize_rows_e4m3: w [N, K] fp16 / bf16 (rows may be strided) -> (q [N, K] uint8: OCP E4M3 bytes, scale [N] fp32)
+    with scale = row abs-max / 448 (1.0 for a zero row) and q = rne_e4m3(w.float() / scale) -- the weight operand of gemm_w8,
+    gemv_ln_w8 and gemv_attn_w8.  View q as torch.float8_e4m3fn to read the values."""
+    _need_gpu(w)
+    assert w.dim() == 2 and w.stride(1) == 1
+    N, K = w.shape
+    q = torch.empty((N, K), dtype=torch.uint8, device=w.device)
+    scale = torch.empty(N, dtype=torch.float32, device=w.device)
+    L.check(L.lib().cogv_quantize_rows_e4m3(dt_code(w), _p(w), w.stride(0), N, K, _p(q), K, _p(scale), _stream()),
+            "cogv_quantize_rows_e4m3")
+    return q, scale
+
+
+def _w8_call(x_dtype, M, K, qs, bias, gelu, absmax):
+    """(descriptor, operand, out) of a skinny-M product on the 8-bit weight qs = (q, scale)."""
+    q, scale = qs
+    _need_gpu(q, scale)
+    assert q.dim() == 2 and q.dtype == torch.uint8 and q.stride(1) == 1 and q.shape[1] == K, "q [N, K] uint8 with K matching the input"
+    assert scale.dtype == torch.float32 and scale.is_contiguous() and scale.numel() == q.shape[0]
+    N = q.shape[0]
+    out = torch.empty((M, N), dtype=x_dtype, device=q.device)
+    d = L.GemmDesc()
+    d.dtype = dt_code(x_dtype)
+    d.M, d.N, d.K = M, N, K
+    d.A, d.lda = None, K
+    d.C, d.ldc = out.data_ptr(), N
+    flags = 0
+    if bias is not None:
+        assert bias.dtype == x_dtype
+        flags |= L.EPI_BIAS
+        d.bias = bias.data_ptr()
+    if gelu:
+        flags |= L.EPI_GELU
+    if absmax is not None:
+        flags |= L.EPI_ABSMAX
+        d.absmax = absmax.data_ptr()
+    d.flags, d.splitk = flags, 1
+    w = L.W8Weight()
+    w.q, w.ldq, w.scale = q.data_ptr(), q.stride(0), scale.data_ptr()
+    return d, w, out
+
+
+def gemm_w8(a, qs, bias=None, gelu=False, absmax=None):
+    """gemm's skinny case (a [M, K], M <= 8) on an 8-bit weight qs = (q [N, K] uint8, scale [N]) from quantize_rows_e4m3
+    (cogv_gemm_w8): out [M, N] = epilogue(scale * (a . e4m3(q)^T) + bias) in a's dtype.  Shapes outside the kernels' classes raise:
+    there is no other kernel behind this one."""
+    _need_gpu(a)
+    assert a.dim() == 2 and a.stride(1) == 1
+    M, K = a.shape
+    d, w, out = _w8_call(a.dtype, M, K, qs, bias, gelu, absmax)
+    d.A, d.lda = a.data_ptr(), a.stride(0)
+    L.check(L.lib().cogv_gemm_w8(C.byref(d), C.byref(w), _stream()), "cogv_gemm_w8")
+    return out
+
+
+def gemv_ln_w8(z, qs, bias, gamma, beta, eps, z_absmax=None, post=None, residual=None, want_t=False, gelu=False, absmax=None):
+    """gemv_ln on an 8-bit weight qs = (q, scale) (cogv_gemv_ln_w8); everything else as there.  The output takes gamma's dtype."""
+    _need_gpu(z, gamma)
+    assert z.dim() == 2 and z.is_contiguous()
+    M, K = z.shape
+    stream32 = (residual.dtype == torch.float32) if post is not None else (z.dtype == torch.float32)
+    if post is not None:
+        assert z.dtype == gamma.dtype
+    d, w, out = _w8_call(gamma.dtype, M, K, qs, bias, gelu, absmax)
+    ln = L.LnPrologue()
+    ln.z = z.data_ptr()
+    ln.z_absmax = None if z_absmax is None else z_absmax.data_ptr()
+    t = None
+    if post is not None:
+        assert residual is not None and residual.is_contiguous() and residual.shape == z.shape
+        ln.gamma_post, ln.beta_post, ln.residual = post[0].data_ptr(), post[1].data_ptr(), residual.data_ptr()
+        if want_t:
+            t = torch.empty_like(residual)
+            ln.t_out = t.data_ptr()
+    ln.gamma, ln.beta, ln.eps = gamma.data_ptr(), beta.data_ptr(), float(eps)
+    ln.stream_f32 = int(stream32)
+    L.check(L.lib().cogv_gemv_ln_w8(C.byref(d), C.byref(ln), C.byref(w), _stream()), "cogv_gemv_ln_w8")
+    return out, t
+
+
+def gemv_attn_w8(partials, batch, heads, capacity, qs, dtype, bias=None, absmax=None):
+    """gemv_attn on an 8-bit weight qs = (q, scale) (cogv_gemv_attn_w8); `dtype`: the 16-bit type of the output (and bias)."""
+    _need_gpu(partials)
+    assert batch <= 8
+    d, w, out = _w8_call(dtype, batch, heads * 64, qs, bias, False, absmax)
+    L.check(L.lib().cogv_gemv_attn_w8(C.byref(d), C.byref(w), _p(partials), int(heads), int(capacity), _stream()), "cogv_gemv_attn_w8")
+    return out
+
+
 def _sparse_desc(d, kv_index, sparse, b, s_q):
     """Sparse training form in slot space: kv_index [b, s_q // w, n_slots] int32 (bit 31 = masked slot),
     sparse = (w, n_pivots, pivot_bias)."""

@@ -132,6 +132,36 @@ int cogv_gemv_ln(const cogv_gemm_desc* d, const cogv_ln_prologue* ln, void* stre
  * per layer less than combine + GEMV.  d->A is ignored; K = heads * 64, K % 512 == 0; flags BIAS | ABSMAX only. */
 int cogv_gemv_attn(const cogv_gemm_desc* d, const void* partials, int heads, int capacity, void* stream);
 
+/* ------------------------------------------------------------------ 8-bit weights for the decode step (OCP E4M3, one scale per row)
+ * A decode step (generation/sampling.py:139-148: one model call per generated token) reads every Linear weight once per
+ * token: it is a weight stream, and its cost is the weights' bytes.  cogv_quantize_rows_e4m3 stores a weight matrix
+ * W[N][K] (F16 | BF16, rows ldw elements apart) as q[N][K] uint8 in OCP E4M3 ("e4m3fn": no infinities, largest value 448;
+ * rows ldq bytes apart) with one fp32 scale per row:
+ *     scale[n] = max_k |W[n][k]| / 448 in fp32 (1.0 for an all-zero row);  q[n][k] = rne_e4m3(float(W[n][k]) / scale[n])
+ * -- a true fp32 division, so torch's float8_e4m3fn conversion of w.float() / scale reproduces the bytes.  Deterministic, no
+ * atomics.  K % 8 == 0, ldw % 8 == 0, ldq % 8 == 0 (the products below want ldq % 16 == 0 and q, scale 16-byte aligned).
+ * Replaces nothing in the reference (it keeps fp16 weights: mpu/layers.py:243,319); it prepares the operand of the three
+ * products below. */
+int cogv_quantize_rows_e4m3(int dtype, const void* w, int ldw, int N, int K, void* q, int ldq, float* scale, void* stream);
+/* The 8-bit weight operand: it takes the place of d->B / d->ldb (ignored) in the three calls below.  C[m][n] =
+ * epilogue(scale[n] * sum_k X[m][k] * e4m3(q[n][k])): the bytes are converted exactly, the sum is the fp32 sum of the 16-bit
+ * kernels, the scale multiplies it once, then the same fused epilogue (bias, GeLU, rounding to T, abs-max). */
+typedef struct cogv_w8_weight {
+  const void* q; int ldq;      /* [N][ldq] uint8 E4M3 */
+  const float* scale;          /* [N] fp32 */
+} cogv_w8_weight;
+/* cogv_gemm's skinny case (M <= 8: F.linear at mpu/layers.py:243,319 and the tied logits model/gpt2_modeling.py:117 inside a
+ * decode step) on an 8-bit weight; trans_a = trans_b = 0, flags BIAS | GELU | ABSMAX.  3 (unsupported) outside the kernels'
+ * classes -- there is no other kernel to fall back to: M > 8, N % 8, K % 512, K > 10240, K not in {4096, 10240} above 5120
+ * with M >= 2, more than 4 rows in a guarded class above K = 3072. */
+int cogv_gemm_w8(const cogv_gemm_desc* d, const cogv_w8_weight* w, void* stream);
+/* cogv_gemv_ln (mpu/sparse_transformer.py:326-341 fused into the consuming product) on an 8-bit weight; same arguments and
+ * limits (K <= 4096; more than 4 rows: K <= 3072). */
+int cogv_gemv_ln_w8(const cogv_gemm_desc* d, const cogv_ln_prologue* ln, const cogv_w8_weight* w, void* stream);
+/* cogv_gemv_attn (the attention-output projection mpu/sparse_transformer.py:163-166 with the split combine as prologue) on
+ * an 8-bit weight; bit-identical to the combine launch followed by cogv_gemm_w8. */
+int cogv_gemv_attn_w8(const cogv_gemm_desc* d, const cogv_w8_weight* w, const void* partials, int heads, int capacity, void* stream);
+
 /* ------------------------------------------------------------------ Sandwich-LN
  * y = [residual +] LayerNorm_{eps*(amax/8)^2}(x) * gamma + beta ; amax = *absmax_in (NULL: plain LN).
  * replaces mpu/sparse_transformer.py:40-44 (LayerNorm = FusedLayerNorm(x / (x.abs().max()/8))) and the

@@ -1,6 +1,8 @@
 """Single-token decode latency of the 4B model with a 1024-position memory: the captured HIP-graph decode step
 (generation.GraphDecoder), eager K/V-cache memories (kv_cache=True) and the reference-style layer-input memories (every
-step re-projects K and V of the whole memory)."""
+step re-projects K and V of the whole memory).  `--weights e4m3`: in the same run, the captured step on the 8-bit copies of the
+weights (GraphDecoder(weights="e4m3")) next to the 16-bit one -- ms per token of each, and the relative L2 / largest difference
+of their logits on the step that was timed."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 os.environ.setdefault("MASTER_ADDR", "127.0.0.1"); os.environ.setdefault("MASTER_PORT", "29589")
@@ -32,6 +34,35 @@ with torch.no_grad():
             nxt = lg[:, -1].float().argmax(-1)                   # consume the logits on the device, as a sampler would
         torch.cuda.synchronize(); dt = (time.time() - t0) / 20
         print(f"GraphDecoder {mode}: decode {dt*1e3:.2f} ms/token at memory length ~{pre}" + (f" (batch {B})" if B > 1 else ""), flush=True)
+if "--weights" in sys.argv:
+    fmt = sys.argv[sys.argv.index("--weights") + 1]
+    dec8 = GraphDecoder(model, batch=B, capacity=1152, weights=fmt)
+    with torch.no_grad():
+        dec8.prefill(tokens[:, :pre], pos[:, :pre])
+        dec8.capture()
+        while dec8.length < dec.length:                          # the same history (and memory length) as the 16-bit decoder
+            dec8.step(tokens[:, pre:pre + 1], pos[:, pre:pre + 1])
+        ms, last = {}, {}
+        for rep in range(2):                                     # 16-bit, 8-bit, and once more each: the order must not matter
+            for name, d in (("16-bit", dec), (fmt, dec8)):
+                d.length -= 24
+                for t in range(4):
+                    d.step(tokens[:, pre:pre + 1], pos[:, pre:pre + 1])
+                torch.cuda.synchronize(); t0 = time.time()
+                for t in range(20):
+                    lg = d.step(tokens[:, pre:pre + 1], pos[:, pre:pre + 1])
+                    nxt = lg[:, -1].float().argmax(-1)
+                torch.cuda.synchronize()
+                ms.setdefault(name, []).append((time.time() - t0) / 20 * 1e3)
+                last[name] = lg.float().clone()
+        lg16, lg8 = last["16-bit"], last[fmt]
+    w8_bytes = sum(t.numel() * t.element_size() for t in dec8.w8.tensors())
+    print(f"captured graph, 16-bit weights: {min(ms['16-bit']):.2f} ms/token; {fmt} weights: {min(ms[fmt]):.2f} ms/token "
+          f"({min(ms['16-bit']) / min(ms[fmt]):.2f}x; runs {['%.2f' % v for v in ms['16-bit']]} / {['%.2f' % v for v in ms[fmt]]})"
+          + (f" (batch {B})" if B > 1 else "") + f"; 8-bit copies {w8_bytes / 2 ** 30:.2f} GiB", flush=True)
+    print(f"logits {fmt} vs 16-bit on the timed step: rel-L2 {((lg8 - lg16).norm() / lg16.norm()).item():.3e}, "
+          f"max |difference| {(lg8 - lg16).abs().max().item():.3e} (max |logit| {lg16.abs().max().item():.3f})", flush=True)
+    del dec8
 del model, dec
 torch.cuda.empty_cache()
 if os.environ.get("MB_DECODE_GRAPH_ONLY") == "1":
