@@ -84,6 +84,19 @@ class AttnDecodeDesc(C.Structure):
     ]
 
 
+class AttnDecodeKv8Desc(C.Structure):
+    _fields_ = [
+        ("dtype", C.c_int), ("B", C.c_int), ("H", C.c_int), ("capacity", C.c_int), ("head_dim", C.c_int),
+        ("scale", C.c_float),
+        ("qkv", C.c_void_p), ("qkv_bs", C.c_longlong),
+        ("kv_q", C.c_void_p), ("kv_q_bs", C.c_longlong),
+        ("kv_scale", C.c_void_p), ("kv_scale_bs", C.c_longlong),
+        ("out", C.c_void_p), ("out_bs", C.c_longlong),
+        ("pos", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("skip_combine", C.c_int),
+    ]
+
+
 class AdamDesc(C.Structure):
     _fields_ = [
         ("dtype", C.c_int),
@@ -171,6 +184,8 @@ SIGNATURES = {
     "cogv_gemm_w8": (_i, [C.POINTER(GemmDesc), C.POINTER(W8Weight), _vp]),
     "cogv_gemv_ln_w8": (_i, [C.POINTER(GemmDesc), C.POINTER(LnPrologue), C.POINTER(W8Weight), _vp]),
     "cogv_gemv_attn_w8": (_i, [C.POINTER(GemmDesc), C.POINTER(W8Weight), _vp, _i, _i, _vp]),
+    "cogv_kv_quantize_e4m3": (_i, [_i, _vp, _i64, _i64, _i, _i, _i, _vp, _i64, _vp, _i64, _i, _i, _vp]),
+    "cogv_attention_decode_kv8": (_i, [C.POINTER(AttnDecodeKv8Desc), _vp]),
     "cogv_attention_decode_workspace_bytes": (_sz, [_i, _i, _i]),
     "cogv_attention_keep_bits_bytes": (_sz, [_i, _i, _i, _i]),
     "cogv_sparse_slot_reduce": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i64, _i, _i, _i, _i, _i, _i, _i, _vp]),

@@ -1465,6 +1465,19 @@ extern "C" int cogv_attention_decode(const cogv_attn_decode_desc* d, void* strea
   return cogv_check_launch();
 }
 
+// the combine launch alone, for the decode attention on the 8-bit cache (attention_kv8.hip: a unit of its own that leaves the
+// same partials): host code only, the kernels above are instantiated as they were
+extern "C" __attribute__((visibility("hidden"))) int cogv_attn_decode_combine_launch(int dtype, const void* ws, void* out, long long out_bs,
+                                                                                     int B, int H, int nsplit, void* stream) {
+  DecodeArgs a = {};
+  a.out = out; a.ws = const_cast<float*>(reinterpret_cast<const float*>(ws));
+  a.out_bs = out_bs; a.B = B; a.H = H; a.nsplit = nsplit;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (dtype == COGV_F16) hipLaunchKernelGGL((attn_decode_combine_kernel<f16_t>), dim3(H, B), dim3(64), 0, st, a);
+  else hipLaunchKernelGGL((attn_decode_combine_kernel<bf16_t>), dim3(H, B), dim3(64), 0, st, a);
+  return cogv_check_launch();
+}
+
 extern "C" int cogv_sparse_slot_reduce(int dtype, const void* dk_slots, const void* dv_slots, const int* pivot_inv,
                                        void* dk, void* dv, long long dk_bs, int dk_rs, long long dv_bs, int dv_rs,
                                        int B, int s, int H, int window, int times, int n_pivots, void* stream) {

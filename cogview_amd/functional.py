@@ -588,8 +588,7 @@ def _layer_forward(layer, x, absmax_x, sep, drops, keep, kv_slot=None):
         att, lse, kbits = res[0], res[1], (res[2] if len(res) > 2 else None)
     elif s == 1 and getattr(kv_slot, "pos_index", None) is not None:
         # captured decode step (StaticKVSlot): keys split over workgroups, cache append fused, length read on the device
-        att, lse = ops.attention_decode(qkv, kv_slot.cache, kv_slot.pos_index, npp).view(b, 1, npp, 64), None
-        kv_slot.out = kv_slot.cache
+        att, lse = decode_attention(qkv, kv_slot, npp).view(b, 1, npp, 64), None
     else:
         _, kc, vc = kv_slot.append(qkv[:, :, hp:2 * hp], qkv[:, :, 2 * hp:])
         kc, vc = kc.view(b, kc.shape[1], npp, 64), vc.view(b, vc.shape[1], npp, 64)
@@ -972,6 +971,25 @@ def _decode_fuse_combine():
     return not torch.cuda.is_current_stream_capturing()
 
 
+def decode_attention(qkv, slot, heads, combine=True):
+    """The decode attention of one layer, chosen by the slot's type: a 16-bit StaticKVSlot (ops.attention_decode on its cache)
+    or an 8-bit StaticKV8Slot (ops.attention_decode_kv8 on its bytes and scales); both write the new token's key / value into
+    the slot at pos_index.  combine=False: the split partials for gemv_attn / gemv_attn_w8."""
+    if getattr(slot, "scale", None) is not None:
+        res = (ops.attention_decode_kv8(qkv, slot, slot.pos_index, heads) if combine else
+               ops.attention_decode_kv8(qkv, slot, slot.pos_index, heads, combine=False))
+        slot.out = slot.q
+        return res
+    res = (ops.attention_decode(qkv, slot.cache, slot.pos_index, heads) if combine else
+           ops.attention_decode(qkv, slot.cache, slot.pos_index, heads, combine=False))
+    slot.out = slot.cache
+    return res
+
+
+def _slot_capacity(slot):
+    return slot.capacity if getattr(slot, "scale", None) is not None else slot.cache.shape[1]
+
+
 def decode_chain_supported(tr, batch):
     """The fused decode chain (decode_chain) covers the dense, single-partition model in a 16-bit type at one token per
     row: what a captured decode step runs."""
@@ -1043,12 +1061,11 @@ def decode_chain(tr, h0, absmax0, slots, emb_weight, w8=None):
         # burst of same-address atomics
         if hp % 512 == 0 and _decode_fuse_combine():
             # the key splits' partials are combined in the prologue of the attention-output GEMV (one launch less)
-            parts = ops.attention_decode(qkv.view(b, 1, 3 * hp), slot.cache, slot.pos_index, npp, combine=False)
-            ao = ops.gemv_attn(parts, b, npp, slot.cache.shape[1], att_m.dense.weight, bias=att_m.dense.bias)
+            parts = decode_attention(qkv.view(b, 1, 3 * hp), slot, npp, combine=False)
+            ao = ops.gemv_attn(parts, b, npp, _slot_capacity(slot), att_m.dense.weight, bias=att_m.dense.bias)
         else:
-            att = ops.attention_decode(qkv.view(b, 1, 3 * hp), slot.cache, slot.pos_index, npp)
+            att = decode_attention(qkv.view(b, 1, 3 * hp), slot, npp)
             ao = ops.gemm(att.view(b, hp), att_m.dense.weight, bias=att_m.dense.bias)
-        slot.out = slot.cache
         g, y = ops.gemv_ln(ao, mlp_m.dense_h_to_4h.weight, mlp_m.dense_h_to_4h.bias, layer.post_attention_layernorm.weight,
                            layer.post_attention_layernorm.bias, eps, None,
                            (layer.third_layernorm.weight, layer.third_layernorm.bias), x, want_t=True, gelu=True)
@@ -1075,12 +1092,11 @@ def _decode_chain_w8(tr, h0, absmax0, slots, w8):
         if x is None:
             x = z
         if hp % 512 == 0 and _decode_fuse_combine():
-            parts = ops.attention_decode(qkv.view(b, 1, 3 * hp), slot.cache, slot.pos_index, npp, combine=False)
-            ao = ops.gemv_attn_w8(parts, b, npp, slot.cache.shape[1], w_dense, w8.dtype, bias=att_m.dense.bias)
+            parts = decode_attention(qkv.view(b, 1, 3 * hp), slot, npp, combine=False)
+            ao = ops.gemv_attn_w8(parts, b, npp, _slot_capacity(slot), w_dense, w8.dtype, bias=att_m.dense.bias)
         else:
-            att = ops.attention_decode(qkv.view(b, 1, 3 * hp), slot.cache, slot.pos_index, npp)
+            att = decode_attention(qkv.view(b, 1, 3 * hp), slot, npp)
             ao = ops.gemm_w8(att.view(b, hp), w_dense, bias=att_m.dense.bias)
-        slot.out = slot.cache
         g, y = ops.gemv_ln_w8(ao, w_h4h, mlp_m.dense_h_to_4h.bias, layer.post_attention_layernorm.weight,
                               layer.post_attention_layernorm.bias, eps, None,
                               (layer.third_layernorm.weight, layer.third_layernorm.bias), x, want_t=True, gelu=True)
@@ -1106,8 +1122,7 @@ def decode_layers_w8(tr, h0, absmax0, slots, w8):
         hp = npp * 64
         a, _, _ = ops.sandwich_ln_fwd(x, layer.input_layernorm.weight, layer.input_layernorm.bias, eps, absmax_x, save_stats=False)
         qkv = ops.gemm_w8(a.view(b, h), w_qkv, bias=att_m.query_key_value.bias).view(b, 1, 3 * hp)
-        att = ops.attention_decode(qkv, slot.cache, slot.pos_index, npp)
-        slot.out = slot.cache
+        att = decode_attention(qkv, slot, npp)
         slot_ao = ops.new_absmax_slot(dev)
         ao = ops.gemm_w8(att.view(b, hp), w_dense, bias=att_m.dense.bias, absmax=slot_ao)
         slot_y = ops.new_absmax_slot(dev)

@@ -13,7 +13,7 @@ import torch
 
 from .. import functional as F_
 from .. import ops
-from ..mpu.transformer import StaticKVSlot
+from ..mpu.transformer import KV8Cache, StaticKVSlot
 
 
 WEIGHT_FORMATS = ("e4m3",)
@@ -34,8 +34,24 @@ def refuse_w8_unsupported(weights, tr, batch):
         raise NotImplementedError(f"weights={weights!r}: {why}")
 
 
+KV_FORMATS = ("e4m3",)
+
+
+def refuse_kv8_unsupported(kv, tr):
+    """kv= of the decoders: what the 8-bit key/value cache does not cover, refused before anything is allocated."""
+    from ..mpu.initialize import mp_world_size_or_1
+    if kv not in KV_FORMATS:
+        raise ValueError(f"kv={kv!r}: None (16-bit cache) or one of {KV_FORMATS}")
+    if mp_world_size_or_1() > 1:
+        raise NotImplementedError(f"kv={kv!r} with model parallelism > 1: use the 16-bit cache (kv=None)")
+    dt = tr.layers[0].attention.query_key_value.weight.dtype
+    if dt not in (torch.float16, torch.bfloat16):
+        raise NotImplementedError(f"kv={kv!r} on a {dt} model: the 8-bit cache is read by the fp16 / bf16 decode step (kv=None: "
+                                  f"the 16-bit cache)")
+
+
 class GraphDecoder:
-    def __init__(self, model, batch=1, capacity=1152, weights=None):
+    def __init__(self, model, batch=1, capacity=1152, weights=None, kv=None):
         """model: GPT2Model (optionally inside FP16_Module) in eval mode, dense attention; capacity: slots per cache
         (<= 4096, the gathered form's limit).
         weights="e4m3": the decode step streams 8-bit copies of the weights (OCP E4M3 bytes with one fp32 scale per row,
@@ -44,13 +60,20 @@ class GraphDecoder:
         the prefill runs on the 16-bit weights (a GEMM, not a stream), so those stay resident: the copies ADD half the
         model's size in device memory (about 4 GB at 4B).  Logits differ from the 16-bit step's by the quantization of the
         weights.  One model-parallel partition, dense attention, fp16 / bf16, hidden sizes whose h and 4h the 8-bit kernels
-        cover (the model family's: 1024 and 2560).  None (default): nothing is allocated, the step is what it was."""
+        cover (the model family's: 1024 and 2560).  None (default): nothing is allocated, the step is what it was.
+        kv="e4m3": the key/value caches hold OCP E4M3 bytes with one fp32 scale per (slot, head, K | V) (mpu.transformer.KV8Cache,
+        ops.kv_quantize_e4m3 / ops.attention_decode_kv8) INSTEAD of the 16-bit caches: 0.53 of the bytes a step streams from them
+        and of their resident memory.  The prefill stays 16-bit; its memories are quantized into the cache.  Logits differ from
+        the 16-bit cache's by the quantization of keys and values.  Composes with weights="e4m3".  One model-parallel partition,
+        dense attention, fp16 / bf16.  None (default): the 16-bit caches, the step is what it was."""
         m = model
         while hasattr(m, "module"):
             m = m.module
         self.gpt, tr = m, m.transformer
         assert capacity <= 4096
-        self.w8 = None
+        self.w8, self.kv = None, kv
+        if kv is not None:
+            refuse_kv8_unsupported(kv, tr)
         if weights is not None:
             refuse_w8_unsupported(weights, tr, batch)
             if m.word_embeddings.weight.shape[0] % 8:
@@ -67,8 +90,13 @@ class GraphDecoder:
         self.table = torch.arange(capacity, dtype=torch.int64, device=dev)
         self.masked = ((self.table | (1 << 31)) - (1 << 32)).to(torch.int32)       # every slot flagged: nothing visible
         self.table = self.masked.unsqueeze(0).repeat(batch, 1).contiguous()
-        self.caches = [torch.zeros((batch, capacity, 2 * hp), dtype=dt, device=dev) for _ in tr.layers]
-        self.slots = [StaticKVSlot(c, self.pos_index, self.table) for c in self.caches]
+        if kv is None:
+            self.kv8 = None
+            self.caches = [torch.zeros((batch, capacity, 2 * hp), dtype=dt, device=dev) for _ in tr.layers]
+            self.slots = [StaticKVSlot(c, self.pos_index, self.table) for c in self.caches]
+        else:
+            self.kv8 = KV8Cache(len(tr.layers), batch, hp // 64, capacity, self.pos_index, dev)
+            self.caches, self.slots = None, self.kv8.slots
         self.slab = torch.zeros(8 * len(tr.layers) + 16, dtype=torch.float32, device=dev)
         self.graph, self.logits = None, None
         self.fused = True            # False: layer-by-layer path (every LayerNorm its own launch) -- kept for comparison
@@ -125,8 +153,12 @@ class GraphDecoder:
         finally:
             tr.kv_cache, tr.max_memory_length = kv_flag, max_mem
         n = tokens.shape[1]
-        for c, mem in zip(self.caches, mems):
-            c[:, :n].copy_(mem)
+        if self.kv8 is not None:
+            for slot, mem in zip(self.slots, mems):       # 1 or B rows of 16-bit keys | values -> bytes + scales of all B rows
+                slot.load(mem)
+        else:
+            for c, mem in zip(self.caches, mems):
+                c[:, :n].copy_(mem)
         self.table[:, :n] = torch.arange(n, dtype=torch.int32, device=self.table.device)
         self.table[:, n:] = self.masked[n:]           # a longer earlier run left these visible (the op-by-op step reads them)
         self.length = n
@@ -157,8 +189,8 @@ class SamplingDecoder(GraphDecoder):
     and a run of them needs no host work.  Reference path: generation/sampling.py:139-186 (model call, filter, multinomial,
     beam score) once per token.  Use start() + generate() (step() feeds tokens from the host and is not for this mode)."""
 
-    def __init__(self, model, batch=1, capacity=1152, weights=None):
-        super().__init__(model, batch, capacity, weights=weights)
+    def __init__(self, model, batch=1, capacity=1152, weights=None, kv=None):
+        super().__init__(model, batch, capacity, weights=weights, kv=kv)
         self.sampling = None
 
     def enable_sampling(self, temperature=1.0, top_k=0, top_p=0.0, allow=None, seed=0, out_tokens=None, out_base=0,

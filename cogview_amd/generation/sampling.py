@@ -374,9 +374,17 @@ def plan_device_fill(seq_l, tokenizer, vocab):
                 capacity=_plan_capacity(len(seq_l)))
 
 
-def _refuse_unsupported(args, use="filling_sequence", weights=None):
+def _refuse_unsupported(args, use="filling_sequence", weights=None, kv=None):
     """What only the host form (`use`) does, refused before the model is touched."""
     from ..mpu.initialize import mp_world_size_or_1
+    if kv is not None:
+        from .decoder import KV_FORMATS
+        if kv not in KV_FORMATS:
+            raise ValueError(f"kv={kv!r}: None (16-bit cache) or one of {KV_FORMATS}")
+        if args.is_sparse == 2:
+            raise NotImplementedError(f"sparse generation (is_sparse = 2) with kv={kv!r}: use {use}")
+        if mp_world_size_or_1() > 1:
+            raise NotImplementedError(f"model parallelism > 1 with kv={kv!r}: use {use}")
     if weights is not None:
         from .decoder import WEIGHT_FORMATS
         if weights not in WEIGHT_FORMATS:
@@ -399,7 +407,20 @@ def _unwrap(model):
     return model
 
 
-def generate_on_device(model, seq, args, tokenizer=None, seed=0, capture=True, weights=None):
+def _decoder_formats(weights, kv):
+    """The format keywords a decoder is built with: only those that are set (a default build issues the call it always did)."""
+    kw = {"weights": weights}
+    if kv is not None:
+        kw["kv"] = kv
+    return kw
+
+
+def _refuse_fp32_kv8(model, kv, use="filling_sequence"):
+    if kv is not None and model is not None and _unwrap(model).word_embeddings.weight.dtype == torch.float32:
+        raise NotImplementedError(f"kv={kv!r} on a float32 model: use {use} (or the 16-bit cache of an fp16 / bf16 model)")
+
+
+def generate_on_device(model, seq, args, tokenizer=None, seed=0, capture=True, weights=None, kv=None):
     """filling_sequence for one run of generated tokens with the sampling on the device: prefill of the context (one row,
     its keys / values broadcast into the nb cache rows), nb independent first draws from its last logits, then one
     captured decode graph per token (generation/decoder.py SamplingDecoder) whose last launch filters, draws, and feeds
@@ -408,16 +429,18 @@ def generate_on_device(model, seq, args, tokenizer=None, seed=0, capture=True, w
     Supported: dense attention (args.is_sparse == 0), one model-parallel partition, fp16 / bf16, <= 4096 positions.
     Returns (tokens [nb, len(seq)], scores [nb] fp32: the summed log-probabilities of the drawn ids), on seq's device.
     capture=False runs the same launches eagerly (the reference for the captured form).
-    weights="e4m3": the decode steps stream 8-bit copies of the weights (GraphDecoder's `weights`; the prefill stays 16-bit)."""
+    weights="e4m3": the decode steps stream 8-bit copies of the weights (GraphDecoder's `weights`; the prefill stays 16-bit).
+    kv="e4m3": the key/value caches hold 8-bit keys and values (GraphDecoder's `kv`); composes with `weights`."""
     from .decoder import SamplingDecoder
     tokenizer = tokenizer if tokenizer is not None else IdSpace()
-    _refuse_unsupported(args, weights=weights)
+    _refuse_unsupported(args, weights=weights, kv=kv)
+    _refuse_fp32_kv8(model, kv)
     assert seq.dim() == 1
     plan = plan_device_generation(seq.tolist(), tokenizer, _unwrap(model).word_embeddings.weight.shape[0])
     n, run, nb = plan["context"], plan["run"], plan["nb"]
     tokens, attention_mask, position_ids = get_batch(seq[:n], seq.device, args)
     position_ids[position_ids > plan["offset"]] -= plan["offset"]
-    dec = SamplingDecoder(model, batch=nb, capacity=plan["capacity"], weights=weights)
+    dec = SamplingDecoder(model, batch=nb, capacity=plan["capacity"], **_decoder_formats(weights, kv))
     out = torch.empty((nb, run), dtype=torch.long, device=tokens.device)
     dec.enable_sampling(args.temperature, args.top_k, args.top_p, plan["allow"], seed, out_tokens=out, out_base=n)
     with torch.no_grad():
@@ -443,20 +466,21 @@ class DeviceFiller:
     attention, one model-parallel partition, <= capacity positions (1408: the reference's MAXSEQLEN 1345 rounded up to 64).
     capture=False runs the same launches eagerly.  After a call, .scores is [1] fp32: the summed log-probability of the
     drawn ids (given ids add nothing).  weights="e4m3": the decode steps stream 8-bit copies of the weights (GraphDecoder's
-    `weights`), made when the first call builds the decoder."""
+    `weights`), made when the first call builds the decoder.  kv="e4m3": 8-bit key/value caches (GraphDecoder's `kv`)."""
 
-    def __init__(self, model, args, seed=0, capacity=1408, capture=True, weights=None):
-        _refuse_unsupported(args, weights=weights)
+    def __init__(self, model, args, seed=0, capacity=1408, capture=True, weights=None, kv=None):
+        _refuse_unsupported(args, weights=weights, kv=kv)
+        _refuse_fp32_kv8(model, kv)
         if not 0 < capacity <= 4096:
             raise ValueError(f"capacity {capacity} outside (0, 4096]: the decode cache's limit")
         self.model, self.seed, self.capacity, self.capture = model, int(seed), int(capacity), capture
-        self.weights = weights
+        self.weights, self.kv = weights, kv
         self.dec, self.key, self.scores = None, None, None
 
     def _decoder(self, args, allow):
         from .decoder import SamplingDecoder
         if self.dec is None:
-            self.dec = SamplingDecoder(self.model, batch=1, capacity=self.capacity, weights=self.weights)
+            self.dec = SamplingDecoder(self.model, batch=1, capacity=self.capacity, **_decoder_formats(self.weights, self.kv))
             dev = self.dec.tok.device
             self.out = torch.empty((1, self.capacity), dtype=torch.long, device=dev)
             self.given = torch.full((self.capacity,), -1, dtype=torch.long, device=dev)

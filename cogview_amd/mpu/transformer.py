@@ -119,6 +119,58 @@ class StaticKVSlot(KVCacheSlot):
         return self.cache, self.cache[:, :, :hp], self.cache[:, :, hp:]
 
 
+class StaticKV8Slot(KVCacheSlot):
+    """A layer's fixed-capacity key/value cache in 8 bits for captured decode steps (generation/decoder.py, kv="e4m3"):
+    q [b, 2, heads, capacity, 64] uint8 -- OCP E4M3 bytes, plane 0 keys, plane 1 values -- and scale [b, 2, heads, capacity]
+    fp32, one per (slot, head, K | V) (ops.kv_quantize_e4m3).  The decode attention on it (ops.attention_decode_kv8) quantizes
+    the new token's key / value and writes them at the device-side position `pos_index`.  It travels through
+    `mem=` like the other slots, but there is no 16-bit memory to append to or to gather from: whatever asks for one raises."""
+
+    def __init__(self, q, scale, pos_index):
+        super().__init__(None, 0)
+        self.q, self.scale, self.pos_index = q, scale, pos_index
+
+    @property
+    def capacity(self):
+        return self.q.shape[3]
+
+    def load(self, kv, slot0=0):
+        """kv [1 or b, n, 2 * hp] (16-bit keys | values of a prefill) -> slots [slot0, slot0 + n) of every cache row."""
+        rows, n = kv.shape[0], kv.shape[1]
+        assert rows in (1, self.q.shape[0])
+        ops.kv_quantize_e4m3(kv, self.q[:rows], self.scale[:rows], slot0)
+        if rows < self.q.shape[0]:
+            self.q[rows:, :, :, slot0:slot0 + n].copy_(self.q[:1, :, :, slot0:slot0 + n])
+            self.scale[rows:, :, :, slot0:slot0 + n].copy_(self.scale[:1, :, :, slot0:slot0 + n])
+
+    def dequantize(self):
+        """[b, capacity, 2 * hp] fp32, keys | values: the 16-bit cache's layout (tests and tools)."""
+        b, _, heads, cap, _ = self.q.shape
+        x = self.q.view(torch.float8_e4m3fn).float() * self.scale.unsqueeze(-1)
+        return x.permute(0, 3, 1, 2, 4).reshape(b, cap, 2 * heads * 64)
+
+    def append(self, k_new, v_new):
+        raise NotImplementedError("the 8-bit key/value cache serves one-token decode steps (ops.attention_decode_kv8) only: "
+                                  "use the 16-bit cache (kv=None) for the gathered multi-token form")
+
+
+class KV8Cache:
+    """The 8-bit key/value caches of a decoder: one StaticKV8Slot per layer on shared allocations."""
+
+    def __init__(self, layers, batch, heads, capacity, pos_index, device):
+        self.q = torch.zeros((layers, batch, 2, heads, capacity, 64), dtype=torch.uint8, device=device)
+        self.scale = torch.ones((layers, batch, 2, heads, capacity), dtype=torch.float32, device=device)
+        self.pos_index = pos_index
+        self.slots = [StaticKV8Slot(self.q[i], self.scale[i], pos_index) for i in range(layers)]
+
+    def dequantize(self):
+        """Per layer [b, capacity, 2 * hp] fp32 (keys | values)."""
+        return [s.dequantize() for s in self.slots]
+
+    def tensors(self):
+        return [self.q, self.scale]
+
+
 class GPT2ParallelSelfAttention(torch.nn.Module):
     """mpu/sparse_transformer.py:46-169."""
 
@@ -147,6 +199,9 @@ class GPT2ParallelSelfAttention(torch.nn.Module):
 
     def forward(self, hidden_states, ltor_mask, pivot_idx=None, is_sparse=0, mem=None):
         query_length = hidden_states.size(1)
+        if isinstance(mem, StaticKV8Slot):
+            raise NotImplementedError("the 8-bit key/value cache serves the fused decode step only (functional.decode_attention): "
+                                      "sparse generation, model parallelism and the gathered multi-token form need kv=None")
         if isinstance(mem, KVCacheSlot):
             # K/V-cache mode: project only the new positions, append their keys / values to the layer's cache and
             # attend over the cache (strided views: the attention kernels take any row stride)

@@ -643,6 +643,54 @@ def attention_decode(qkv, cache, pos_index, heads, combine=True):
     return out if combine else ws
 
 
+def kv_quantize_e4m3(kv, q, scale, slot0=0):
+    """cogv_kv_quantize_e4m3: the 16-bit K | V rows a prefill leaves, kv [b, n, 2 * heads * 64] (batch and row strides free),
+    into slots [slot0, slot0 + n) of an 8-bit cache: q [b, 2, heads, capacity, 64] uint8 (OCP E4M3 bytes; plane 0 keys, plane 1
+    values) and scale [b, 2, heads, capacity] fp32, one scale per (slot, head, K | V) = abs-max of its 64 elements / 448 (1.0
+    when they are all zero), q = rne_e4m3(x.float() / scale).  q / scale may be the leading rows of a larger cache."""
+    _need_gpu(kv, q, scale)
+    assert kv.dim() == 3 and kv.stride(2) == 1 and q.dim() == 5 and scale.dim() == 4
+    b, n, w = kv.shape
+    heads, cap = q.shape[2], q.shape[3]
+    assert w == 2 * heads * 64 and q.shape == (b, 2, heads, cap, 64) and scale.shape == (b, 2, heads, cap)
+    assert q.dtype == torch.uint8 and scale.dtype == torch.float32 and q[0].is_contiguous() and scale[0].is_contiguous()
+    assert 0 <= slot0 and slot0 + n <= cap
+    L.check(L.lib().cogv_kv_quantize_e4m3(dt_code(kv), _p(kv), kv.stride(0), kv.stride(1), b, n, heads, _p(q), q.stride(0), _p(scale),
+                                          scale.stride(0), cap, int(slot0), _stream()), "cogv_kv_quantize_e4m3")
+
+
+def attention_decode_kv8(qkv, cache8, pos_index, heads, combine=True):
+    """attention_decode on an 8-bit cache (cogv_attention_decode_kv8): cache8 = (q [b, 2, heads, capacity, 64] uint8,
+    scale [b, 2, heads, capacity] fp32) as kv_quantize_e4m3 fills it, or an object with these as .q / .scale (StaticKV8Slot).  The new token's key / value are quantized, written into
+    slot pos as bytes + scale, and attended in their dequantized form.  Result, partials (combine=False) and the workspace
+    cache (keyed as attention_decode's: the same buffers) as there."""
+    q, scale = (cache8.q, cache8.scale) if hasattr(cache8, "scale") else cache8
+    _need_gpu(qkv, q, scale, pos_index)
+    b, cap = q.shape[0], q.shape[3]
+    hp = heads * 64
+    assert qkv.shape[0] == b and qkv.shape[-1] == 3 * hp and qkv.numel() == b * 3 * hp and qkv.stride(-1) == 1
+    assert q.dtype == torch.uint8 and q.shape == (b, 2, heads, cap, 64) and q[0].is_contiguous()
+    assert scale.dtype == torch.float32 and scale.shape == (b, 2, heads, cap) and scale[0].is_contiguous()
+    assert pos_index.dtype == torch.int64
+    lib = L.lib()
+    key = (qkv.device.index, b, heads, cap)
+    ws = _DECODE_WS.get(key)
+    if ws is None:
+        ws = _DECODE_WS[key] = torch.zeros(lib.cogv_attention_decode_workspace_bytes(b, heads, cap), dtype=torch.uint8, device=qkv.device)
+    out = torch.empty((b, 1, hp), dtype=qkv.dtype, device=qkv.device) if combine else None
+    d = L.AttnDecodeKv8Desc()
+    d.dtype, d.B, d.H, d.capacity, d.head_dim, d.scale = dt_code(qkv), b, heads, cap, 64, 0.125
+    d.qkv, d.qkv_bs = qkv.data_ptr(), qkv.stride(0)
+    d.kv_q, d.kv_q_bs = q.data_ptr(), q.stride(0)
+    d.kv_scale, d.kv_scale_bs = scale.data_ptr(), scale.stride(0)
+    d.out, d.out_bs = (out.data_ptr(), out.stride(0)) if combine else (None, hp)
+    d.pos = pos_index.data_ptr()
+    d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
+    d.skip_combine = 0 if combine else 1
+    L.check(lib.cogv_attention_decode_kv8(C.byref(d), _stream()), "cogv_attention_decode_kv8")
+    return out if combine else ws
+
+
 def gemv_attn(partials, batch, heads, capacity, w, bias=None, absmax=None):
     """Attention-output projection of a decode step with the split-combine as its prologue (cogv_gemv_attn):
     out [batch, N] = (combined attention output [batch, heads * 64]) . w^T + bias.  `partials`: what

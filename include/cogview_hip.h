@@ -299,6 +299,38 @@ typedef struct cogv_attn_decode_desc {
 } cogv_attn_decode_desc;
 size_t cogv_attention_decode_workspace_bytes(int B, int H, int capacity);
 int cogv_attention_decode(const cogv_attn_decode_desc* d, void* stream);
+/* ------------------------------------------------------------------ 8-bit key/value cache for the decode step (OCP E4M3, one scale per head)
+ * The decode attention requests every slot of the fixed-capacity cache on every step (generation/sampling.py:139-148: one
+ * model call per generated token), so a step streams the whole cache.  Here the cache holds E4M3 bytes with one fp32 scale per
+ * (slot, head, K | V), head-major:
+ *     q     uint8 [B][2][H][capacity][64]   plane 0: keys, plane 1: values   (q_bs: BYTES between batch rows)
+ *     scale fp32  [B][2][H][capacity]                                        (scale_bs: floats between batch rows)
+ * by the rule of cogv_quantize_rows_e4m3 on the 64 elements of one head of one slot: scale = max|x| / 448 (1.0 when all are
+ * zero), q = rne_e4m3(float(x) / scale) with a true fp32 division.  136 bytes per (slot, head) for its key and value instead of 256.
+ * cogv_kv_quantize_e4m3 (the memories of a prefill, mpu/sparse_transformer.py:526-546): kv = the 16-bit K | V rows
+ * [B][n][2 * H * 64] (kv_bs / kv_rs: batch / row strides in elements) -> slots [slot0, slot0 + n) of q / scale; bit-identical to
+ * cogv_quantize_rows_e4m3 on the [rows, 64] view.  q 16-byte aligned, scale 4-byte; fp16 / bf16, else 3 (unsupported). */
+int cogv_kv_quantize_e4m3(int dtype, const void* kv, long long kv_bs, long long kv_rs, int B, int n, int H, void* q, long long q_bs,
+                          float* scale, long long scale_bs, int capacity, int slot0, void* stream);
+/* cogv_attention_decode on that cache (generation/sampling.py:139-148): same contract -- one query row per batch row, slots
+ * [0, *pos] attended, *pos device data, every load issued before it is read, slots past *pos or the capacity without influence
+ * whatever bytes they hold -- except that the new token's key / value are QUANTIZED FIRST, stored into slot *pos as bytes +
+ * scale, and attended in their dequantized form (a token's key has one value in every step that reads it).  128 keys per split
+ * and the 66-float partials of cogv_attention_decode: workspace, skip_combine, cogv_gemv_attn and cogv_gemv_attn_w8 as there.
+ * 1 (bad argument): misaligned kv_q (16 B) / kv_scale (4 B), head_dim != 64, short workspace; 3 (unsupported): other dtypes. */
+typedef struct cogv_attn_decode_kv8_desc {
+  int dtype; int B, H, capacity, head_dim;
+  float scale;                       /* 1/sqrt(head_dim) */
+  const void* qkv; long long qkv_bs;
+  void* kv_q; long long kv_q_bs;
+  float* kv_scale; long long kv_scale_bs;
+  void* out; long long out_bs;
+  const long long* pos;
+  void* workspace; size_t workspace_bytes;
+  int skip_combine;
+} cogv_attn_decode_kv8_desc;
+/* one decode step's attention per layer on the 8-bit cache (the model call of generation/sampling.py:139-148) */
+int cogv_attention_decode_kv8(const cogv_attn_decode_kv8_desc* d, void* stream);
 /* Sparse training form, backward: cogv_attention_bwd with sparse_window > 0 writes dq as usual, but dk / dv are
  * SLOT-SPACE buffers [B * s_q / sparse_window][s_k slots][H][64] (dk_bs / dv_bs = the stride of one (batch, query block)
  * plane) -- the gradient of each gathered copy of a key, the same quantity the reference's autograd holds for pivot_k

@@ -2,7 +2,9 @@
 (generation.GraphDecoder), eager K/V-cache memories (kv_cache=True) and the reference-style layer-input memories (every
 step re-projects K and V of the whole memory).  `--weights e4m3`: in the same run, the captured step on the 8-bit copies of the
 weights (GraphDecoder(weights="e4m3")) next to the 16-bit one -- ms per token of each, and the relative L2 / largest difference
-of their logits on the step that was timed."""
+of their logits on the step that was timed.  `--kv e4m3`: the same comparison for the 8-bit key/value cache
+(GraphDecoder(kv="e4m3")) against the 16-bit cache, both on the weights `--weights` names (default: 16-bit).  MB_DECODE_SKIP_EAGER=1
+skips the eager timing of the first decoder."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 os.environ.setdefault("MASTER_ADDR", "127.0.0.1"); os.environ.setdefault("MASTER_PORT", "29589")
@@ -23,7 +25,7 @@ tokens, pos = tokens.expand(B, -1).contiguous(), pos.expand(B, -1).contiguous()
 dec = GraphDecoder(model, batch=B, capacity=1152)
 with torch.no_grad():
     dec.prefill(tokens[:, :pre], pos[:, :pre])
-    for mode in ("eager fixed-capacity step", "captured graph"):
+    for mode in (("captured graph",) if os.environ.get("MB_DECODE_SKIP_EAGER") == "1" else ("eager fixed-capacity step", "captured graph")):
         if mode == "captured graph":
             dec.capture()
         for t in range(4):
@@ -34,35 +36,63 @@ with torch.no_grad():
             nxt = lg[:, -1].float().argmax(-1)                   # consume the logits on the device, as a sampler would
         torch.cuda.synchronize(); dt = (time.time() - t0) / 20
         print(f"GraphDecoder {mode}: decode {dt*1e3:.2f} ms/token at memory length ~{pre}" + (f" (batch {B})" if B > 1 else ""), flush=True)
-if "--weights" in sys.argv:
-    fmt = sys.argv[sys.argv.index("--weights") + 1]
-    dec8 = GraphDecoder(model, batch=B, capacity=1152, weights=fmt)
+WFMT = sys.argv[sys.argv.index("--weights") + 1] if "--weights" in sys.argv else None
+KVFMT = sys.argv[sys.argv.index("--kv") + 1] if "--kv" in sys.argv else None
+
+
+def _alternate(base, other, base_name, other_name):
+    """Both captured decoders at the same history, timed in turn, twice (the order must not matter).  Returns (ms, last logits)."""
+    while other.length < base.length:
+        other.step(tokens[:, pre:pre + 1], pos[:, pre:pre + 1])
+    ms, last = {}, {}
+    for rep in range(2):
+        for name, d in ((base_name, base), (other_name, other)):
+            d.length -= 24
+            for t in range(4):
+                d.step(tokens[:, pre:pre + 1], pos[:, pre:pre + 1])
+            torch.cuda.synchronize(); t0 = time.time()
+            for t in range(20):
+                lg = d.step(tokens[:, pre:pre + 1], pos[:, pre:pre + 1])
+                nxt = lg[:, -1].float().argmax(-1)
+            torch.cuda.synchronize()
+            ms.setdefault(name, []).append((time.time() - t0) / 20 * 1e3)
+            last[name] = lg.float().clone()
+    return ms, last
+
+
+def _report(ms, last, a, b, what, tail=""):
+    print(f"captured graph, {a}: {min(ms[a]):.2f} ms/token; {b}: {min(ms[b]):.2f} ms/token "
+          f"({min(ms[a]) / min(ms[b]):.2f}x; runs {['%.2f' % v for v in ms[a]]} / {['%.2f' % v for v in ms[b]]})"
+          + (f" (batch {B})" if B > 1 else "") + tail, flush=True)
+    lg16, lg8 = last[a], last[b]
+    print(f"logits {what} on the timed step: rel-L2 {((lg8 - lg16).norm() / lg16.norm()).item():.3e}, "
+          f"max |difference| {(lg8 - lg16).abs().max().item():.3e} (max |logit| {lg16.abs().max().item():.3f})", flush=True)
+
+
+if WFMT is not None:
+    dec8 = GraphDecoder(model, batch=B, capacity=1152, weights=WFMT)
     with torch.no_grad():
         dec8.prefill(tokens[:, :pre], pos[:, :pre])
         dec8.capture()
-        while dec8.length < dec.length:                          # the same history (and memory length) as the 16-bit decoder
-            dec8.step(tokens[:, pre:pre + 1], pos[:, pre:pre + 1])
-        ms, last = {}, {}
-        for rep in range(2):                                     # 16-bit, 8-bit, and once more each: the order must not matter
-            for name, d in (("16-bit", dec), (fmt, dec8)):
-                d.length -= 24
-                for t in range(4):
-                    d.step(tokens[:, pre:pre + 1], pos[:, pre:pre + 1])
-                torch.cuda.synchronize(); t0 = time.time()
-                for t in range(20):
-                    lg = d.step(tokens[:, pre:pre + 1], pos[:, pre:pre + 1])
-                    nxt = lg[:, -1].float().argmax(-1)
-                torch.cuda.synchronize()
-                ms.setdefault(name, []).append((time.time() - t0) / 20 * 1e3)
-                last[name] = lg.float().clone()
-        lg16, lg8 = last["16-bit"], last[fmt]
+        ms, last = _alternate(dec, dec8, "16-bit weights", f"{WFMT} weights")
     w8_bytes = sum(t.numel() * t.element_size() for t in dec8.w8.tensors())
-    print(f"captured graph, 16-bit weights: {min(ms['16-bit']):.2f} ms/token; {fmt} weights: {min(ms[fmt]):.2f} ms/token "
-          f"({min(ms['16-bit']) / min(ms[fmt]):.2f}x; runs {['%.2f' % v for v in ms['16-bit']]} / {['%.2f' % v for v in ms[fmt]]})"
-          + (f" (batch {B})" if B > 1 else "") + f"; 8-bit copies {w8_bytes / 2 ** 30:.2f} GiB", flush=True)
-    print(f"logits {fmt} vs 16-bit on the timed step: rel-L2 {((lg8 - lg16).norm() / lg16.norm()).item():.3e}, "
-          f"max |difference| {(lg8 - lg16).abs().max().item():.3e} (max |logit| {lg16.abs().max().item():.3f})", flush=True)
+    _report(ms, last, "16-bit weights", f"{WFMT} weights", f"{WFMT} vs 16-bit", f"; 8-bit copies {w8_bytes / 2 ** 30:.2f} GiB")
+    if KVFMT is not None:
+        del dec
+        dec = dec8                                               # the 8-bit cache is compared on the same weights
     del dec8
+if KVFMT is not None:
+    wname = f"{WFMT or '16-bit'} weights"
+    deck = GraphDecoder(model, batch=B, capacity=1152, weights=WFMT, kv=KVFMT)
+    with torch.no_grad():
+        deck.prefill(tokens[:, :pre], pos[:, :pre])
+        deck.capture()
+        ms, last = _alternate(dec, deck, f"{wname}, 16-bit cache", f"{wname}, {KVFMT} cache")
+    b16 = sum(c.numel() * c.element_size() for c in dec.caches)
+    b8 = sum(t.numel() * t.element_size() for t in deck.kv8.tensors())
+    _report(ms, last, f"{wname}, 16-bit cache", f"{wname}, {KVFMT} cache", f"{KVFMT} cache vs 16-bit cache",
+            f"; cache bytes per step {b16 / 1e9:.3f} GB -> {b8 / 1e9:.3f} GB")
+    del deck
 del model, dec
 torch.cuda.empty_cache()
 if os.environ.get("MB_DECODE_GRAPH_ONLY") == "1":

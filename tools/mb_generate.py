@@ -9,7 +9,8 @@ reference's three stages joined on the device -- eight candidates from generate_
 (the host tail: full logits in fp32) and with inverse_prompt_score_on_device in the same run (ms per candidate, largest score
 difference, peak allocated memory of each), ranked by rerank_generated, the best one magnified with fill=DeviceFiller.
 `--weights e4m3` (text -> image and `--super-resolution` legs): the device forms also run with the decode steps on 8-bit copies
-of the weights (generate_on_device / DeviceFiller `weights=`), timed next to the 16-bit ones."""
+of the weights (generate_on_device / DeviceFiller `weights=`), timed next to the 16-bit ones.  `--kv e4m3`: the same legs with the
+8-bit key/value cache (`kv=`), alone or together with `--weights`."""
 import os, sys, time, types
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -39,6 +40,7 @@ mpu.initialize_model_parallel(1); torch.manual_seed(1); mpu.model_parallel_cuda_
 L, h, heads, V = 48, 2560, 40, 58240
 SR = "--super-resolution" in sys.argv
 W8 = sys.argv[sys.argv.index("--weights") + 1] if "--weights" in sys.argv else None
+KV8 = sys.argv[sys.argv.index("--kv") + 1] if "--kv" in sys.argv else None
 ids = IdSpace()
 # super-resolution windows reach 1305 positions: filling_sequence's memory must hold them all, as the decode graph does
 max_mem = 1408 if SR else 1089
@@ -72,13 +74,13 @@ if SR:
     print(f"device form: {len(plans)} prefills (each draws one code), {replays} decode replays = {replays - given} generated "
           f"+ {given} given inside the runs; {sum(p['trailing'] for p in plans)} trailing given ids copied on the host; "
           f"{t_dev / (replays + len(plans)) * 1e3:.2f} ms per model call", flush=True)
-    if W8:
-        filler8 = DeviceFiller(model, args, seed=1, weights=W8)
+    if W8 or KV8:
+        filler8 = DeviceFiller(model, args, seed=1, weights=W8, kv=KV8)
         torch.cuda.synchronize(); t0 = time.time()
         big8 = magnify(model, ids, code, text_t, args, fill=filler8)
         torch.cuda.synchronize(); t_w8 = time.time() - t0
         assert big8.shape == (1, 4096) and int(big8.max()) < 8192
-        print(f"DeviceFiller weights={W8}: {t_w8:.2f} s (quantization + prefills + capture included), "
+        print(f"DeviceFiller weights={W8} kv={KV8}: {t_w8:.2f} s (quantization + prefills + capture included), "
               f"{t_w8 / (replays + len(plans)) * 1e3:.2f} ms per model call; {t_dev / t_w8:.2f}x the 16-bit device form", flush=True)
     sys.exit(0)
 args = types.SimpleNamespace(temperature=1.0, top_k=200, top_p=0.0, is_sparse=0)
@@ -132,11 +134,11 @@ for nb in (1, 8):
     print(f"batch {nb}: generate_on_device {t_dev:.2f} s = {t_dev / 1024 * 1e3:.2f} ms/token (prefill + capture included); "
           f"filling_sequence kv_cache=True {t_host:.2f} s = {t_host / 1024 * 1e3:.2f} ms/token; speed-up {t_host / t_dev:.1f}x",
           flush=True)
-    if W8:
-        generate_on_device(model, seq.clone(), args, seed=0, weights=W8)         # warm-up
+    if W8 or KV8:
+        generate_on_device(model, seq.clone(), args, seed=0, weights=W8, kv=KV8)         # warm-up
         torch.cuda.synchronize(); t0 = time.time()
-        out8, scores8 = generate_on_device(model, seq.clone(), args, seed=1, weights=W8)
+        out8, scores8 = generate_on_device(model, seq.clone(), args, seed=1, weights=W8, kv=KV8)
         torch.cuda.synchronize(); t_w8 = time.time() - t0
         assert int(out8[:, -1024:].max()) < 8192 and torch.isfinite(scores8).all()
-        print(f"batch {nb}: generate_on_device weights={W8} {t_w8:.2f} s = {t_w8 / 1024 * 1e3:.2f} ms/token (quantization + prefill + "
+        print(f"batch {nb}: generate_on_device weights={W8} kv={KV8} {t_w8:.2f} s = {t_w8 / 1024 * 1e3:.2f} ms/token (quantization + prefill + "
               f"capture included); {t_dev / t_w8:.2f}x the 16-bit device form", flush=True)
