@@ -81,6 +81,7 @@ class AttnDecodeDesc(C.Structure):
         ("out", C.c_void_p), ("out_bs", C.c_longlong),
         ("pos", C.c_void_p),
         ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("skip_combine", C.c_int),
+        ("first", C.c_void_p),
     ]
 
 
@@ -94,6 +95,7 @@ class AttnDecodeKv8Desc(C.Structure):
         ("out", C.c_void_p), ("out_bs", C.c_longlong),
         ("pos", C.c_void_p),
         ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("skip_combine", C.c_int),
+        ("first", C.c_void_p),
     ]
 
 

@@ -1107,12 +1107,18 @@ __global__ __launch_bounds__(NT, 2) void attn_bwd_dkdv_kernel(const AttnArgs p) 
 // second small launch combines the partials in split order (deterministic).  The new token's key / value come straight from the QKV GEMM's
 // output row and are written into the cache slot *pos by the split that owns it: the cat + index_copy_ launches of the
 // generic cache append disappear.  Valid slots are [0, *pos] (device data: no launch parameter depends on the length).
+// RAGGED (cogv_attn_decode_desc.first != NULL; a second instantiation, the plain one compiles what it always did): row b
+// attends slots [first[b], *pos] -- rows of one launch hold right-aligned contexts of different lengths, slots below
+// first[b] are padding.  A padding slot is treated like a slot past *pos: it takes the new token's bits through the masks
+// below and a score of -inf, so whatever it holds never enters a product; a split that lies wholly in the padding leaves
+// the partial (-inf, 0, 0...) a split past *pos leaves, which both combines weight with 0.
 struct DecodeArgs {
   const void* qkv; void* cache; void* out; const long long* pos; float* ws; int* tickets;
   long long qkv_bs, cache_bs, out_bs; int cache_rs;
   int B, H, cap, nsplit; float scale_l2e;
+  const int* first;
 };
-template <typename T>
+template <typename T, bool RAGGED = false>
 __global__ __launch_bounds__(256) void attn_decode_kernel(const DecodeArgs p) {
   __shared__ float red_o[32][64];
   __shared__ float red_m[4], red_l[32];
@@ -1126,6 +1132,8 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const DecodeArgs p) {
   T* crow = reinterpret_cast<T*>(p.cache) + b * p.cache_bs + head * HD + dch * 8;
   float sc[4]; u32x4 v8[4], kc8[4];
   float m_loc = -INFINITY;
+  int first_b = 0;
+  if (RAGGED) first_b = p.first[b];          // requested with the cache rows, ahead of *pos
 #pragma unroll
   for (int ps = 0; ps < 4; ++ps) {
     const long long key = (long long)split * 128 + ps * 32 + kg;
@@ -1143,10 +1151,12 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const DecodeArgs p) {
 #endif
   }
   const long long pos = *p.pos;
+  // first[b] < 0 counts as 0; first[b] > *pos leaves the new token's own slot
+  const long long first = RAGGED ? (first_b < 0 ? 0 : (first_b > pos ? pos : (long long)first_b)) : 0;
 #pragma unroll
   for (int ps = 0; ps < 4; ++ps) {
     const long long key = (long long)split * 128 + ps * 32 + kg;
-    const bool valid = key <= pos && key < p.cap;
+    const bool valid = (!RAGGED || key >= first) && key <= pos && key < p.cap;
     const bool cached = valid && key != pos;
     // (bit masks, not a select: the compiler turns a select of a loaded value into a branch and sinks the load into it)
     const uint32_t mk = cached ? 0xffffffffu : 0u;
@@ -1445,8 +1455,9 @@ extern "C" int cogv_attention_decode(const cogv_attn_decode_desc* d, void* strea
   if (!d->qkv || !d->cache || (!d->out && !d->skip_combine) || !d->pos || !d->workspace) return COGV_ERR_ARG;
   if (!aligned16(d->qkv) || !aligned16(d->cache) || ((d->qkv_bs | d->cache_bs | d->cache_rs) & 7)) return COGV_ERR_ARG;
   if (d->workspace_bytes < cogv_attention_decode_workspace_bytes(d->B, d->H, d->capacity) || ((uintptr_t)d->workspace & 15)) return COGV_ERR_ARG;
+  if ((uintptr_t)d->first & 3) return COGV_ERR_ARG;
   DecodeArgs a;
-  a.qkv = d->qkv; a.cache = d->cache; a.out = d->out; a.pos = d->pos;
+  a.qkv = d->qkv; a.cache = d->cache; a.out = d->out; a.pos = d->pos; a.first = d->first;
   a.tickets = nullptr;
   a.ws = reinterpret_cast<float*>(d->workspace);
   a.qkv_bs = d->qkv_bs; a.cache_bs = d->cache_bs; a.out_bs = d->out_bs; a.cache_rs = d->cache_rs;
@@ -1456,10 +1467,12 @@ extern "C" int cogv_attention_decode(const cogv_attn_decode_desc* d, void* strea
   dim3 grid(a.nsplit, a.H, a.B);
   // skip_combine: the consumer (cogv_gemv_attn: the attention-output projection of a decode step) recombines the partials itself
   if (d->dtype == COGV_F16) {
-    hipLaunchKernelGGL((attn_decode_kernel<f16_t>), grid, dim3(256), 0, st, a);
+    if (a.first) hipLaunchKernelGGL((attn_decode_kernel<f16_t, true>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((attn_decode_kernel<f16_t>), grid, dim3(256), 0, st, a);
     if (!d->skip_combine) hipLaunchKernelGGL((attn_decode_combine_kernel<f16_t>), dim3(a.H, a.B), dim3(64), 0, st, a);
   } else {
-    hipLaunchKernelGGL((attn_decode_kernel<bf16_t>), grid, dim3(256), 0, st, a);
+    if (a.first) hipLaunchKernelGGL((attn_decode_kernel<bf16_t, true>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((attn_decode_kernel<bf16_t>), grid, dim3(256), 0, st, a);
     if (!d->skip_combine) hipLaunchKernelGGL((attn_decode_combine_kernel<bf16_t>), dim3(a.H, a.B), dim3(64), 0, st, a);
   }
   return cogv_check_launch();

@@ -107,13 +107,16 @@ __global__ __launch_bounds__(256) void kv_quantize_e4m3_kernel(const KvQuantArgs
 // stored into slot *pos as bytes + scale, and the step's own attention uses the dequantized values -- a token's key has one value
 // in every step that reads it.  Bytes become fp32 exactly (v_cvt_pk_f32_fp8); the scale multiplies the 64-term dot product (keys)
 // and the probability (values): all arithmetic fp32.
+// RAGGED (cogv_attn_decode_kv8_desc.first != NULL; a second instantiation): row b attends slots [first[b], *pos], as in
+// attn_decode_kernel -- a padding slot takes the new token's bytes and scales through the masks below and a score of -inf.
 struct DecodeKv8Args {
   const void* qkv; uint8_t* q; float* scale; const long long* pos; float* ws;
   long long qkv_bs, q_bs, scale_bs;
   int B, H, cap, nsplit; float scale_l2e;
+  const int* first;
 };
 constexpr int RED_LD = 68;        // floats per row of the output reduction (16-byte rows, off the 64-float bank period)
-template <typename T>
+template <typename T, bool RAGGED = false>
 __global__ __launch_bounds__(256) void attn_decode_kv8_kernel(const DecodeKv8Args p) {
   __shared__ __attribute__((aligned(16))) float red_o[64 * RED_LD];
   __shared__ float red_p[4][64];
@@ -130,6 +133,8 @@ __global__ __launch_bounds__(256) void attn_decode_kv8_kernel(const DecodeKv8Arg
   uint8_t* kq = p.q + b * p.q_bs + prow * HD + part * 16;
   float* ks = p.scale + b * p.scale_bs + prow;
   u32x4 kc[2], vc[2]; uint32_t ksc[2], vsc[2];
+  int first_b = 0;
+  if (RAGGED) first_b = p.first[b];          // requested with the cache rows, ahead of *pos
 #pragma unroll
   for (int ps = 0; ps < 2; ++ps) {
     const int key = split * 128 + ps * 64 + kg;
@@ -149,11 +154,13 @@ __global__ __launch_bounds__(256) void attn_decode_kv8_kernel(const DecodeKv8Arg
   float qf[16];
   unpack8<T>(q0, qf); unpack8<T>(q1, qf + 8);
   const long long pos = *p.pos;
+  // first[b] < 0 counts as 0; first[b] > *pos leaves the new token's own slot
+  const long long first = RAGGED ? (first_b < 0 ? 0 : (first_b > pos ? pos : (long long)first_b)) : 0;
   float sc[2], m_loc = -INFINITY;
 #pragma unroll
   for (int ps = 0; ps < 2; ++ps) {
     const int key = split * 128 + ps * 64 + kg;
-    const bool valid = key <= pos && key < p.cap;
+    const bool valid = (!RAGGED || key >= first) && key <= pos && key < p.cap;
     const bool cached = valid && key != pos;
     // (bit masks, not a select: the compiler turns a select of a loaded value into a branch and sinks the load into it).  Every
     // slot that is not a cached one takes the new token's bytes and scales: whatever the cache holds there never enters a product
@@ -244,17 +251,23 @@ extern "C" int cogv_attention_decode_kv8(const cogv_attn_decode_kv8_desc* d, voi
   if (((uintptr_t)d->qkv & 15) || ((uintptr_t)d->kv_q & 15) || ((uintptr_t)d->kv_scale & 3) || (d->qkv_bs & 7) || (d->kv_q_bs & 15)) return COGV_ERR_ARG;
   if (d->kv_q_bs < 2LL * d->H * d->capacity * HD || d->kv_scale_bs < 2LL * d->H * d->capacity) return COGV_ERR_ARG;
   if (d->workspace_bytes < cogv_attention_decode_workspace_bytes(d->B, d->H, d->capacity) || ((uintptr_t)d->workspace & 15)) return COGV_ERR_ARG;
+  if ((uintptr_t)d->first & 3) return COGV_ERR_ARG;
   if (d->dtype != COGV_F16 && d->dtype != COGV_BF16) return COGV_ERR_UNSUPPORTED;
   DecodeKv8Args a;
-  a.qkv = d->qkv; a.q = reinterpret_cast<uint8_t*>(d->kv_q); a.scale = d->kv_scale; a.pos = d->pos;
+  a.qkv = d->qkv; a.q = reinterpret_cast<uint8_t*>(d->kv_q); a.scale = d->kv_scale; a.pos = d->pos; a.first = d->first;
   a.ws = reinterpret_cast<float*>(d->workspace);
   a.qkv_bs = d->qkv_bs; a.q_bs = d->kv_q_bs; a.scale_bs = d->kv_scale_bs;
   a.B = d->B; a.H = d->H; a.cap = d->capacity; a.nsplit = (d->capacity + 127) / 128;
   a.scale_l2e = d->scale * 1.4426950408889634f;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   dim3 grid(a.nsplit, a.H, a.B);
-  if (d->dtype == COGV_F16) hipLaunchKernelGGL((attn_decode_kv8_kernel<f16_t>), grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((attn_decode_kv8_kernel<bf16_t>), grid, dim3(256), 0, st, a);
+  if (d->dtype == COGV_F16) {
+    if (a.first) hipLaunchKernelGGL((attn_decode_kv8_kernel<f16_t, true>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((attn_decode_kv8_kernel<f16_t>), grid, dim3(256), 0, st, a);
+  } else {
+    if (a.first) hipLaunchKernelGGL((attn_decode_kv8_kernel<bf16_t, true>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((attn_decode_kv8_kernel<bf16_t>), grid, dim3(256), 0, st, a);
+  }
   // skip_combine: the consumer (cogv_gemv_attn / cogv_gemv_attn_w8) recombines the partials itself
   if (!d->skip_combine) return cogv_attn_decode_combine_launch(d->dtype, d->workspace, d->out, d->out_bs, a.B, a.H, a.nsplit, stream);
   return cogv_check_launch();

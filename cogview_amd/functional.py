@@ -557,12 +557,13 @@ class _LayerCtx:
                  "d_attn", "d_ao", "d_mo", "kbits")
 
 
-def _layer_forward(layer, x, absmax_x, sep, drops, keep, kv_slot=None):
+def _layer_forward(layer, x, absmax_x, sep, drops, keep, kv_slot=None, mask=None):
     """x [b,s,h] fp32 (the residual stream) -> (out fp32, absmax_out); `keep` is a _LayerCtx to fill (None: inference,
     nothing retained).  Everything that feeds a GEMM (a, qkv, att, ao, c, g, mo) is in the 16-bit storage type; the
     stream x -> y -> out stays fp32: LN1 / LN2 read it, LN3 / LN4 add their output to it in fp32.
     kv_slot (inference): the layer's key/value cache (mpu.transformer.KVCacheSlot): the new keys / values are appended
-    and attention runs over the cache.
+    and attention runs over the cache.  mask (with a growing kv_slot only): an arbitrary mask tensor instead of `sep` (a prefill
+    of right-aligned prompts of different lengths, generation/decoder.py), through the general-mask kernels.
     Kernel chain (MP=1): LN1 | QKV GEMM+bias | attention | dense GEMM+bias+dropout+absmax | LN3+residual+absmax |
     LN2 | h->4h GEMM+bias+GeLU (+ stored gelu') | 4h->h GEMM+bias+dropout+absmax | LN4+residual+absmax."""
     att_m, mlp_m = layer.attention, layer.mlp
@@ -595,6 +596,8 @@ def _layer_forward(layer, x, absmax_x, sep, drops, keep, kv_slot=None):
         table = getattr(kv_slot, "table", None)     # fixed-capacity cache of a captured decode step: gathered form
         if table is not None:
             att, lse = ops.attention_fwd(q, kc, vc, kv_index=table)
+        elif mask is not None:
+            att, lse = ops.attention_fwd(q, kc, vc, mask=general_mask(mask, b, s, kc.shape[1], q.dtype))
         else:
             att, lse = ops.attention_fwd(q, kc, vc, sep=sep, dropout=d_attn)
 
@@ -974,14 +977,16 @@ def _decode_fuse_combine():
 def decode_attention(qkv, slot, heads, combine=True):
     """The decode attention of one layer, chosen by the slot's type: a 16-bit StaticKVSlot (ops.attention_decode on its cache)
     or an 8-bit StaticKV8Slot (ops.attention_decode_kv8 on its bytes and scales); both write the new token's key / value into
-    the slot at pos_index.  combine=False: the split partials for gemv_attn / gemv_attn_w8."""
+    the slot at pos_index.  combine=False: the split partials for gemv_attn / gemv_attn_w8.  A slot that carries `.first` (a
+    ragged decoder: one first attended slot per cache row) hands it on; without one the calls are what they always were."""
+    kw = {} if combine else {"combine": False}
+    if getattr(slot, "first", None) is not None:
+        kw["first"] = slot.first
     if getattr(slot, "scale", None) is not None:
-        res = (ops.attention_decode_kv8(qkv, slot, slot.pos_index, heads) if combine else
-               ops.attention_decode_kv8(qkv, slot, slot.pos_index, heads, combine=False))
+        res = ops.attention_decode_kv8(qkv, slot, slot.pos_index, heads, **kw)
         slot.out = slot.q
         return res
-    res = (ops.attention_decode(qkv, slot.cache, slot.pos_index, heads) if combine else
-           ops.attention_decode(qkv, slot.cache, slot.pos_index, heads, combine=False))
+    res = ops.attention_decode(qkv, slot.cache, slot.pos_index, heads, **kw)
     slot.out = slot.cache
     return res
 
@@ -1141,13 +1146,13 @@ def decode_layers_w8(tr, h0, absmax0, slots, w8):
     return ops.gemm_w8(out.view(b, h), w8.emb).view(b, 1, w8.emb[0].shape[0])
 
 
-def transformer_layer_kv(layer, x, absmax_x, sep, kv_slot):
+def transformer_layer_kv(layer, x, absmax_x, sep, kv_slot, mask=None):
     """The fused layer chain for incremental decoding (no gradient): 9 kernels + the cache append instead of the ~20 of
-    the op-by-op composition."""
+    the op-by-op composition.  mask: an arbitrary mask tensor in place of `sep` (a growing cache only)."""
     xc = x if x.is_contiguous() else x.contiguous()
     if absmax_x is None:
         absmax_x = ops.absmax(xc)
-    out, slot = _layer_forward(layer, xc, absmax_x, sep, (None, None, None), None, kv_slot=kv_slot)
+    out, slot = _layer_forward(layer, xc, absmax_x, sep, (None, None, None), None, kv_slot=kv_slot, mask=mask)
     out._cogv_absmax = slot
     return out
 

@@ -50,8 +50,19 @@ def refuse_kv8_unsupported(kv, tr):
                                   f"the 16-bit cache)")
 
 
+def refuse_ragged_unsupported(tr):
+    """ragged=True of the decoders: refused before anything is allocated, as kv= is."""
+    from ..mpu.initialize import mp_world_size_or_1
+    if mp_world_size_or_1() > 1:
+        raise NotImplementedError("ragged=True with model parallelism > 1: one prompt per decoder (ragged=False)")
+    dt = tr.layers[0].attention.query_key_value.weight.dtype
+    if dt not in (torch.float16, torch.bfloat16):
+        raise NotImplementedError(f"ragged=True on a {dt} model: the decode attention that reads `first` is the fp16 / bf16 "
+                                  f"decode step's (ragged=False: one prompt per decoder)")
+
+
 class GraphDecoder:
-    def __init__(self, model, batch=1, capacity=1152, weights=None, kv=None):
+    def __init__(self, model, batch=1, capacity=1152, weights=None, kv=None, ragged=False):
         """model: GPT2Model (optionally inside FP16_Module) in eval mode, dense attention; capacity: slots per cache
         (<= 4096, the gathered form's limit).
         weights="e4m3": the decode step streams 8-bit copies of the weights (OCP E4M3 bytes with one fp32 scale per row,
@@ -65,13 +76,21 @@ class GraphDecoder:
         ops.kv_quantize_e4m3 / ops.attention_decode_kv8) INSTEAD of the 16-bit caches: 0.53 of the bytes a step streams from them
         and of their resident memory.  The prefill stays 16-bit; its memories are quantized into the cache.  Logits differ from
         the 16-bit cache's by the quantization of keys and values.  Composes with weights="e4m3".  One model-parallel partition,
-        dense attention, fp16 / bf16.  None (default): the 16-bit caches, the step is what it was."""
+        dense attention, fp16 / bf16.  None (default): the 16-bit caches, the step is what it was.
+        ragged=True: the cache rows may hold contexts of DIFFERENT lengths (several prompts on one decode step).  Take G
+        prompts with context lengths n_g and P = max n_g: row g's context is right-aligned in slots [P - n_g, P), slots
+        [0, P - n_g) are padding, and every row writes the same slot *pos_index = P, P + 1, ... -- so the sampler's
+        bookkeeping stays shared.  The one new piece of device data is self.first (int32 [batch], zeros): row b attends slots
+        [first[b], *pos_index] (cogv_attn_decode_desc.first).  Its address is baked into a capture, so the choice is made
+        here.  One model-parallel partition, fp16 / bf16.  False (default): nothing is allocated, the step is what it was."""
         m = model
         while hasattr(m, "module"):
             m = m.module
         self.gpt, tr = m, m.transformer
         assert capacity <= 4096
-        self.w8, self.kv = None, kv
+        self.w8, self.kv, self.first = None, kv, None
+        if ragged:
+            refuse_ragged_unsupported(tr)
         if kv is not None:
             refuse_kv8_unsupported(kv, tr)
         if weights is not None:
@@ -90,12 +109,14 @@ class GraphDecoder:
         self.table = torch.arange(capacity, dtype=torch.int64, device=dev)
         self.masked = ((self.table | (1 << 31)) - (1 << 32)).to(torch.int32)       # every slot flagged: nothing visible
         self.table = self.masked.unsqueeze(0).repeat(batch, 1).contiguous()
+        if ragged:
+            self.first = torch.zeros(batch, dtype=torch.int32, device=dev)
         if kv is None:
             self.kv8 = None
             self.caches = [torch.zeros((batch, capacity, 2 * hp), dtype=dt, device=dev) for _ in tr.layers]
-            self.slots = [StaticKVSlot(c, self.pos_index, self.table) for c in self.caches]
+            self.slots = [StaticKVSlot(c, self.pos_index, self.table, self.first) for c in self.caches]
         else:
-            self.kv8 = KV8Cache(len(tr.layers), batch, hp // 64, capacity, self.pos_index, dev)
+            self.kv8 = KV8Cache(len(tr.layers), batch, hp // 64, capacity, self.pos_index, dev, self.first)
             self.caches, self.slots = None, self.kv8.slots
         self.slab = torch.zeros(8 * len(tr.layers) + 16, dtype=torch.float32, device=dev)
         self.graph, self.logits = None, None
@@ -164,6 +185,43 @@ class GraphDecoder:
         self.length = n
         return logits
 
+    def _prefill_ragged(self, tokens, position_ids, pads):
+        """_prefill for G prompts of different lengths (ragged=True): tokens / position_ids [G, P], every prompt right-aligned
+        (row g's ids in columns [pads[g], P)); the padding columns are overwritten here with a real id (the row's first token)
+        and position 0.  One model call under the mask M[g, i, j] = (j <= i) and (j >= pads[g]) (the general-mask attention
+        path: prompt-length work); the memories of prompt g fill its batch // G cache rows, first[b] = pads[g] keeps the
+        padding slots out of every later step.  Returns the logits [G, P, vocab]."""
+        G, P = tokens.shape
+        assert self.first is not None, "built without ragged=True"
+        assert len(pads) == G and self.batch % G == 0 and 0 < P < self.cap and all(0 <= p < P for p in pads)
+        nb, dev = self.batch // G, self.table.device
+        pad_t = torch.tensor(list(pads), dtype=torch.long, device=dev)
+        col = torch.arange(P, dtype=torch.long, device=dev)
+        is_pad = col.unsqueeze(0) < pad_t.unsqueeze(1)                                            # [G, P]
+        tokens = torch.where(is_pad, tokens.gather(1, pad_t.unsqueeze(1)).expand(G, P), tokens)
+        position_ids = position_ids.masked_fill(is_pad, 0)
+        mask = ((col.view(1, 1, P) <= col.view(1, P, 1)) & (col.view(1, 1, P) >= pad_t.view(G, 1, 1))).float().unsqueeze(1)
+        tr = self.gpt.transformer
+        kv_flag, tr.kv_cache = tr.kv_cache, True
+        max_mem, tr.max_memory_length = tr.max_memory_length, max(tr.max_memory_length, self.cap)
+        try:
+            logits, *mems = self.gpt(tokens, position_ids, mask, None, None, 0)
+        finally:
+            tr.kv_cache, tr.max_memory_length = kv_flag, max_mem
+        for i, (slot, mem) in enumerate(zip(self.slots, mems)):
+            rows = mem.repeat_interleave(nb, 0) if nb > 1 else mem          # row g * nb + j: candidate j of prompt g
+            if self.kv8 is not None:
+                slot.load(rows)
+            else:
+                self.caches[i][:, :P].copy_(rows)
+        first = pad_t.repeat_interleave(nb).to(torch.int32)
+        self.first.copy_(first)
+        # (the op-by-op step reads the table: the padding slots stay flagged)
+        self.table[:, :P] = torch.where(col.unsqueeze(0) < first.unsqueeze(1), self.masked[:P].unsqueeze(0), col.to(torch.int32).unsqueeze(0))
+        self.table[:, P:] = self.masked[P:]
+        self.length = P
+        return logits
+
     @torch.no_grad()
     def step(self, token, position):
         """token, position: [batch, 1] (or [batch]) device tensors for the next input.  Returns logits [batch, 1, vocab]
@@ -189,8 +247,8 @@ class SamplingDecoder(GraphDecoder):
     and a run of them needs no host work.  Reference path: generation/sampling.py:139-186 (model call, filter, multinomial,
     beam score) once per token.  Use start() + generate() (step() feeds tokens from the host and is not for this mode)."""
 
-    def __init__(self, model, batch=1, capacity=1152, weights=None, kv=None):
-        super().__init__(model, batch, capacity, weights=weights, kv=kv)
+    def __init__(self, model, batch=1, capacity=1152, weights=None, kv=None, ragged=False):
+        super().__init__(model, batch, capacity, weights=weights, kv=kv, ragged=ragged)
         self.sampling = None
 
     def enable_sampling(self, temperature=1.0, top_k=0, top_p=0.0, allow=None, seed=0, out_tokens=None, out_base=0,
@@ -234,6 +292,22 @@ class SamplingDecoder(GraphDecoder):
         self.pos.copy_(position_ids[:, -1:].expand(self.batch, 1))
         self.scores.zero_()
         self._sample(logits[:, -1], rows=self.batch)
+        return logits
+
+    @torch.no_grad()
+    def start_ragged(self, tokens, position_ids, pads):
+        """start() for G prompts (ragged=True): tokens / position_ids [G, P] right-aligned, pads[g] padding columns in front of
+        prompt g (_prefill_ragged).  Every prompt's last logits draw the first token of its batch // G rows -- the rows are
+        repeated, so the sampler reads [batch, vocab] with a real row stride -- and every row's position counts on from its
+        own prompt's last position id."""
+        assert self.sampling is not None
+        logits = self._prefill_ragged(tokens, position_ids, pads)
+        G, P = tokens.shape
+        nb = self.batch // G
+        self.pos_index.fill_(P - 1)
+        self.pos.copy_(position_ids[:, -1:].repeat_interleave(nb, 0))
+        self.scores.zero_()
+        self._sample(logits[:, -1].repeat_interleave(nb, 0))
         return logits
 
     def capture(self):

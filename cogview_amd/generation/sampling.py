@@ -342,6 +342,30 @@ def plan_device_generation(seq_l, tokenizer, vocab):
     return dict(context=n, run=len(run), nb=-run[0], allow=allow, offset=offset, capacity=_plan_capacity(len(seq_l)))
 
 
+def plan_device_batch(seqs_l, tokenizer, vocab):
+    """Host planning of generate_batch_on_device / DeviceGenerator for G token lists: plan_device_generation per sequence; the
+    contexts may differ in length, but every sequence must have the same run length, the same nb and the same drawable
+    range (one decode graph draws for all of them) -- otherwise NotImplementedError naming generate_on_device, which takes
+    them one after another.  The [ROI2] offset may differ: it is applied to each prompt's position ids.
+    Returns dict(contexts, pads, P, run, nb, rows, allow, offsets, capacity): P = the longest context, pads[g] = P - contexts[g]
+    padding slots in front of prompt g (right-aligned contexts), rows = G * nb cache rows, capacity for P + run slots."""
+    if not seqs_l:
+        raise ValueError("no sequences")
+    longest = max(len(seq_l) for seq_l in seqs_l)
+    if longest > 4096:
+        raise NotImplementedError(f"{longest} positions exceed the decode cache's 4096 slots (generate_on_device has the same limit): "
+                                  f"use filling_sequence")
+    plans = [plan_device_generation(list(seq_l), tokenizer, vocab) for seq_l in seqs_l]
+    for what in ("run", "nb", "allow"):
+        if any(p[what] != plans[0][what] for p in plans):
+            raise NotImplementedError(f"the sequences differ in `{what}` ({[p[what] for p in plans]}): one decode graph draws the same "
+                                      f"run for every row -- use generate_on_device per sequence")
+    contexts = [p["context"] for p in plans]
+    P, run, nb = max(contexts), plans[0]["run"], plans[0]["nb"]
+    return dict(contexts=contexts, pads=[P - n for n in contexts], P=P, run=run, nb=nb, rows=len(plans) * nb, allow=plans[0]["allow"],
+                offsets=[p["offset"] for p in plans], capacity=_plan_capacity(P + run))
+
+
 def plan_device_fill(seq_l, tokenizer, vocab):
     """Host planning of DeviceFiller: what filling_sequence does with nb = 1 -- a context of given ids, then -1 marks with
     given ids anywhere after them (magnify's windows: lines an earlier window wrote sit between generated ones).
@@ -450,6 +474,131 @@ def generate_on_device(model, seq, args, tokenizer=None, seed=0, capture=True, w
                 dec.capture()
             dec.generate(run - 1)
     return torch.cat((tokens.expand(nb, n), out), dim=1).to(seq.device), dec.scores.clone()
+
+
+def _batch_inputs(seqs, plan, device):
+    """The right-aligned context block of a prompt set: tokens / position_ids [G, P] (padding columns zero: the ragged prefill
+    fills them), each prompt's positions counted from 0 with its own [ROI2] offset applied."""
+    G, P = len(seqs), plan["P"]
+    tokens = torch.zeros((G, P), dtype=torch.long, device=device)
+    position_ids = torch.zeros((G, P), dtype=torch.long, device=device)
+    for g, (seq, n, pad, offset) in enumerate(zip(seqs, plan["contexts"], plan["pads"], plan["offsets"])):
+        tokens[g, pad:] = seq[:n].to(device)
+        pos = torch.arange(n, dtype=torch.long, device=device)
+        pos[pos > offset] -= offset
+        position_ids[g, pad:] = pos
+    return tokens, position_ids
+
+
+def _batch_rows(seqs, plan, out, col0):
+    """Per prompt [nb, len(seq_g)]: its context followed by the run its nb rows drew (columns [col0, col0 + run) of `out`)."""
+    nb, run = plan["nb"], plan["run"]
+    res = []
+    for g, (seq, n) in enumerate(zip(seqs, plan["contexts"])):
+        drawn = out[g * nb:(g + 1) * nb, col0:col0 + run].to(seq.device)
+        res.append(torch.cat((seq[:n].unsqueeze(0).expand(nb, n), drawn), dim=1))
+    return res
+
+
+def _refuse_fp32_ragged(model):
+    if model is not None and _unwrap(model).word_embeddings.weight.dtype == torch.float32:
+        raise NotImplementedError("several prompts on one decode graph on a float32 model: use generate_on_device per sequence")
+
+
+def generate_batch_on_device(model, seqs, args, tokenizer=None, seed=0, capture=True, weights=None, kv=None):
+    """generate_on_device for G prompts at once on ONE decode graph (the reference's generate_images_continually walks a file
+    of prompts one after another, generate_samples.py:202-221; a decode step is a weight stream that costs little more for
+    eight rows than for one).  seqs: list of 1-D tensors, each a context of given ids followed by one run of equal marks; the
+    contexts may differ in length, the runs, nb and the drawable range may not (plan_device_batch).  The contexts are
+    right-aligned in the caches (SamplingDecoder(ragged=True)): one prefill under a per-prompt mask, then every replay draws
+    one token for all G * nb rows -- row g * nb + j is candidate j of prompt g.
+    Returns (list of G tensors [nb, len(seq_g)] without padding, scores [G, nb] fp32), on the sequences' device.
+    One prompt is generate_on_device itself (the plain decoder: same launches, same bits).  weights / kv / capture / seed as there."""
+    from .decoder import SamplingDecoder
+    tokenizer = tokenizer if tokenizer is not None else IdSpace()
+    _refuse_unsupported(args, weights=weights, kv=kv)
+    _refuse_fp32_kv8(model, kv)
+    seqs = list(seqs)
+    assert seqs and all(seq.dim() == 1 for seq in seqs)
+    if len(seqs) == 1:
+        tokens, scores = generate_on_device(model, seqs[0], args, tokenizer=tokenizer, seed=seed, capture=capture, weights=weights, kv=kv)
+        return [tokens], scores.view(1, -1)
+    _refuse_fp32_ragged(model)
+    plan = plan_device_batch([seq.tolist() for seq in seqs], tokenizer, _unwrap(model).word_embeddings.weight.shape[0])
+    P, run, nb, rows = plan["P"], plan["run"], plan["nb"], plan["rows"]
+    dec = SamplingDecoder(model, batch=rows, capacity=plan["capacity"], ragged=True, **_decoder_formats(weights, kv))
+    dev = dec.tok.device
+    tokens, position_ids = _batch_inputs(seqs, plan, dev)
+    out = torch.empty((rows, run), dtype=torch.long, device=dev)
+    dec.enable_sampling(args.temperature, args.top_k, args.top_p, plan["allow"], seed, out_tokens=out, out_base=P)
+    with torch.no_grad():
+        dec.start_ragged(tokens, position_ids, plan["pads"])
+        if run > 1:
+            if capture:
+                dec.capture()
+            dec.generate(run - 1)
+    return _batch_rows(seqs, plan, out, 0), dec.scores.clone().view(len(seqs), nb).to(seqs[0].device)
+
+
+class DeviceGenerator:
+    """generate_batch_on_device on ONE ragged SamplingDecoder and ONE captured decode graph that are reused call after call --
+    DeviceFiller's counterpart for a file of prompts (generate_samples.py:202-221): `gen = DeviceGenerator(model, args, rows=8);
+    tokens, scores = gen(seqs)` for any prompt set with G * nb == rows and P + run <= capacity.  What changes from call to call
+    is device data: the caches, `first`, the token / position / slot buffers, the generator offset (it keeps counting across
+    calls, so every call draws fresh numbers) and the output buffer ([rows, capacity], column = slot).  Temperature, top-k /
+    top-p and the drawable range are baked into the capture: a call with other values re-arms the sampler and captures again.
+    A single prompt (G = 1) runs on the same ragged decoder with first = 0.  capture / weights / kv as generate_on_device's."""
+
+    def __init__(self, model, args, rows, capacity=1152, seed=0, capture=True, weights=None, kv=None):
+        _refuse_unsupported(args, weights=weights, kv=kv)
+        _refuse_fp32_kv8(model, kv)
+        _refuse_fp32_ragged(model)
+        if not 0 < capacity <= 4096:
+            raise ValueError(f"capacity {capacity} outside (0, 4096]: the decode cache's limit")
+        if rows < 1:
+            raise ValueError(f"rows = {rows} must be positive")
+        self.model, self.rows, self.capacity, self.seed, self.capture = model, int(rows), int(capacity), int(seed), capture
+        self.weights, self.kv, self.args = weights, kv, args
+        self.dec, self.key, self.out = None, None, None
+
+    def _decoder(self, args, allow):
+        from .decoder import SamplingDecoder
+        if self.dec is None:
+            self.dec = SamplingDecoder(self.model, batch=self.rows, capacity=self.capacity, ragged=True, **_decoder_formats(self.weights, self.kv))
+            self.out = torch.zeros((self.rows, self.capacity), dtype=torch.long, device=self.dec.tok.device)
+        key = (float(args.temperature), int(args.top_k), float(args.top_p), tuple(allow))
+        if key != self.key:
+            offset = self.dec.offset.clone() if self.key is not None else None
+            self.dec.enable_sampling(*key[:3], allow=allow, seed=self.seed, out_tokens=self.out, out_base=0)
+            if offset is not None:
+                self.dec.offset.copy_(offset)
+            self.dec.graph, self.key = None, key
+        return self.dec
+
+    def __call__(self, seqs, args=None, tokenizer=None):
+        """seqs: list of 1-D tensors (generate_batch_on_device's); args: the sampling arguments of this call (default: the
+        constructor's).  Returns (list of [nb, len(seq_g)] token tensors, scores [G, nb] fp32)."""
+        args = args if args is not None else self.args
+        _refuse_unsupported(args)
+        tokenizer = tokenizer if tokenizer is not None else IdSpace()
+        seqs = list(seqs)
+        assert seqs and all(seq.dim() == 1 for seq in seqs)
+        plan = plan_device_batch([seq.tolist() for seq in seqs], tokenizer, _unwrap(self.model).word_embeddings.weight.shape[0])
+        P, run, nb = plan["P"], plan["run"], plan["nb"]
+        if plan["rows"] != self.rows:
+            raise ValueError(f"{len(seqs)} prompts x {nb} rows = {plan['rows']} rows: this generator was built for {self.rows}")
+        if P + run > self.capacity:
+            raise NotImplementedError(f"{P + run} positions exceed this generator's {self.capacity} decode slots: use "
+                                      f"generate_on_device or a larger capacity")
+        dec = self._decoder(args, plan["allow"])
+        tokens, position_ids = _batch_inputs(seqs, plan, dec.tok.device)
+        with torch.no_grad():
+            dec.start_ragged(tokens, position_ids, plan["pads"])
+            if run > 1:
+                if self.capture and dec.graph is None:
+                    dec.capture()
+                dec.generate(run - 1)
+        return _batch_rows(seqs, plan, self.out, P), dec.scores.clone().view(len(seqs), nb).to(seqs[0].device)
 
 
 class DeviceFiller:

@@ -106,11 +106,13 @@ class KVCacheSlot:
 class StaticKVSlot(KVCacheSlot):
     """A layer's key/value cache with FIXED capacity and address for captured decode steps (generation/decoder.py): the
     new keys / values are written at the device-side position `pos_index`, attention runs over all `cap` slots through
-    the gathered form, whose index table flags the slots not written yet -- no launch parameter depends on the length."""
+    the gathered form, whose index table flags the slots not written yet -- no launch parameter depends on the length.
+    first (optional): device int32 [b], the first attended slot of every cache row (a decoder built with ragged=True: rows
+    with right-aligned contexts of different lengths); None: every row attends from slot 0."""
 
-    def __init__(self, cache, pos_index, table):
+    def __init__(self, cache, pos_index, table, first=None):
         super().__init__(None, 0)
-        self.cache, self.pos_index, self.table = cache, pos_index, table
+        self.cache, self.pos_index, self.table, self.first = cache, pos_index, table, first
 
     def append(self, k_new, v_new):
         hp = k_new.shape[-1]
@@ -124,11 +126,12 @@ class StaticKV8Slot(KVCacheSlot):
     q [b, 2, heads, capacity, 64] uint8 -- OCP E4M3 bytes, plane 0 keys, plane 1 values -- and scale [b, 2, heads, capacity]
     fp32, one per (slot, head, K | V) (ops.kv_quantize_e4m3).  The decode attention on it (ops.attention_decode_kv8) quantizes
     the new token's key / value and writes them at the device-side position `pos_index`.  It travels through
-    `mem=` like the other slots, but there is no 16-bit memory to append to or to gather from: whatever asks for one raises."""
+    `mem=` like the other slots, but there is no 16-bit memory to append to or to gather from: whatever asks for one raises.
+    first (optional): as StaticKVSlot's."""
 
-    def __init__(self, q, scale, pos_index):
+    def __init__(self, q, scale, pos_index, first=None):
         super().__init__(None, 0)
-        self.q, self.scale, self.pos_index = q, scale, pos_index
+        self.q, self.scale, self.pos_index, self.first = q, scale, pos_index, first
 
     @property
     def capacity(self):
@@ -157,11 +160,11 @@ class StaticKV8Slot(KVCacheSlot):
 class KV8Cache:
     """The 8-bit key/value caches of a decoder: one StaticKV8Slot per layer on shared allocations."""
 
-    def __init__(self, layers, batch, heads, capacity, pos_index, device):
+    def __init__(self, layers, batch, heads, capacity, pos_index, device, first=None):
         self.q = torch.zeros((layers, batch, 2, heads, capacity, 64), dtype=torch.uint8, device=device)
         self.scale = torch.ones((layers, batch, 2, heads, capacity), dtype=torch.float32, device=device)
         self.pos_index = pos_index
-        self.slots = [StaticKV8Slot(self.q[i], self.scale[i], pos_index) for i in range(layers)]
+        self.slots = [StaticKV8Slot(self.q[i], self.scale[i], pos_index, first) for i in range(layers)]
 
     def dequantize(self):
         """Per layer [b, capacity, 2 * hp] fp32 (keys | values)."""
@@ -293,7 +296,11 @@ class GPT2ParallelTransformerLayer(torch.nn.Module):
             sep = ltor_mask if isinstance(ltor_mask, int) else F_.mask_to_sep(ltor_mask, hidden_states.size(1),
                                                                               hidden_states.size(1))
             if sep is None:
-                raise NotImplementedError("key/value-cache decoding takes the left-to-right mask (int `sep` or its tensor form)")
+                if getattr(mem, "pos_index", None) is not None:
+                    raise NotImplementedError("a fixed-capacity key/value cache takes the left-to-right mask (int `sep` or its tensor form)")
+                # an arbitrary mask tensor on a growing cache (a prefill of right-aligned prompts): general-mask kernels
+                return F_.transformer_layer_kv(self, hidden_states, getattr(hidden_states, "_cogv_absmax", None), 0, mem,
+                                               mask=ltor_mask)
             return F_.transformer_layer_kv(self, hidden_states, getattr(hidden_states, "_cogv_absmax", None), sep, mem)
         # op-by-op composition (memories / no Sandwich-LN), exactly the reference's dataflow
         a = self.input_layernorm(hidden_states)

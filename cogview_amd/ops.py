@@ -612,12 +612,23 @@ def attention_fwd(q, k, v, sep=0, dropout=None, kv_index=None, sparse=None, keep
 _DECODE_WS = {}
 
 
-def attention_decode(qkv, cache, pos_index, heads, combine=True):
+def _decode_first(first, b, dev):
+    """The `first` argument of the decode attentions: int32 [b] on the device, one first attended slot per cache row."""
+    if first is None:
+        return None
+    _need_gpu(first)
+    assert first.dtype == torch.int32 and first.numel() == b and first.is_contiguous() and first.device == dev
+    return first.data_ptr()
+
+
+def attention_decode(qkv, cache, pos_index, heads, combine=True, first=None):
     """combine=False: only the key-split kernel runs; returns the partials workspace for gemv_attn (the attention-output
     projection recombines the splits in its prologue: one launch less).
     One decode step's attention (cogv_attention_decode): qkv [b, 1, 3 * heads * 64] (q | k | v of the new token),
     cache [b, capacity, 2 * heads * 64] (keys | values), pos_index: device int64 scalar = slot of the new token (slots
     [0, pos] are attended; the new key / value are written into slot pos by the kernel).  Returns out [b, 1, heads * 64].
+    first: device int32 [b] -- row r attends slots [first[r], pos] (rows with right-aligned contexts of different lengths;
+    the slots below first[r] are padding and may hold anything).  None: the launch without it.
     The workspace (partial results of the key splits) is kept per (device, shape): fixed addresses, so the call is
     replayable inside a captured graph."""
     _need_gpu(qkv, cache, pos_index)
@@ -639,6 +650,7 @@ def attention_decode(qkv, cache, pos_index, heads, combine=True):
     d.pos = pos_index.data_ptr()
     d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
     d.skip_combine = 0 if combine else 1
+    d.first = _decode_first(first, b, qkv.device)
     L.check(lib.cogv_attention_decode(C.byref(d), _stream()), "cogv_attention_decode")
     return out if combine else ws
 
@@ -659,11 +671,12 @@ def kv_quantize_e4m3(kv, q, scale, slot0=0):
                                           scale.stride(0), cap, int(slot0), _stream()), "cogv_kv_quantize_e4m3")
 
 
-def attention_decode_kv8(qkv, cache8, pos_index, heads, combine=True):
+def attention_decode_kv8(qkv, cache8, pos_index, heads, combine=True, first=None):
     """attention_decode on an 8-bit cache (cogv_attention_decode_kv8): cache8 = (q [b, 2, heads, capacity, 64] uint8,
     scale [b, 2, heads, capacity] fp32) as kv_quantize_e4m3 fills it, or an object with these as .q / .scale (StaticKV8Slot).  The new token's key / value are quantized, written into
     slot pos as bytes + scale, and attended in their dequantized form.  Result, partials (combine=False) and the workspace
-    cache (keyed as attention_decode's: the same buffers) as there."""
+    cache (keyed as attention_decode's: the same buffers) as there; `first` as there (bytes and scales of the padding slots
+    may hold anything)."""
     q, scale = (cache8.q, cache8.scale) if hasattr(cache8, "scale") else cache8
     _need_gpu(qkv, q, scale, pos_index)
     b, cap = q.shape[0], q.shape[3]
@@ -687,6 +700,7 @@ def attention_decode_kv8(qkv, cache8, pos_index, heads, combine=True):
     d.pos = pos_index.data_ptr()
     d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
     d.skip_combine = 0 if combine else 1
+    d.first = _decode_first(first, b, qkv.device)
     L.check(lib.cogv_attention_decode_kv8(C.byref(d), _stream()), "cogv_attention_decode_kv8")
     return out if combine else ws
 

@@ -285,7 +285,13 @@ size_t cogv_attention_keep_bits_bytes(int B, int H, int s_q, int s_k);
  * slots already valid: the kernel attends slots [0, *pos] -- the new token's key / value are taken from qkv and WRITTEN
  * into slot *pos -- so no launch parameter depends on the length (HIP-graph replay).  out: [B][H * 64] (out_bs elements
  * between rows).  Keys are split over workgroups (capacity / 128 per head); a second launch combines the partial softmax
- * results in split order.  workspace: cogv_attention_decode_workspace_bytes() bytes (partials; no initialisation needed). */
+ * results in split order.  workspace: cogv_attention_decode_workspace_bytes() bytes (partials; no initialisation needed).
+ * first (optional; NULL: the launch described above, the same kernel and the same bits): device int32 [B], 4-byte aligned
+ * (else 1, bad argument).  Row b attends slots [first[b], *pos]: the rows of one launch hold right-aligned contexts of
+ * different lengths (generate_samples.py:202-221 walks a file of prompts; here several of them share one decode step), slots
+ * below first[b] are padding and have no influence whatever they hold, NaN included.  first[b] < 0 counts as 0; first[b] >
+ * *pos attends the new token's own slot only.  A key split that lies wholly in the padding leaves the partial (-inf, 0,
+ * 0...) that a split past *pos leaves.  Only slot *pos is written, as without it. */
 typedef struct cogv_attn_decode_desc {
   int dtype; int B, H, capacity, head_dim;
   float scale;                       /* 1/sqrt(head_dim) */
@@ -296,6 +302,7 @@ typedef struct cogv_attn_decode_desc {
   void* workspace; size_t workspace_bytes;
   int skip_combine;                  /* 1: leave the split partials in `workspace` (66 floats per (row, head, split): max,
                                         sum, 64 outputs) for cogv_gemv_attn to combine; `out` is not written and may be NULL */
+  const int* first;                  /* NULL, or int32 [B]: row b attends slots [first[b], *pos] */
 } cogv_attn_decode_desc;
 size_t cogv_attention_decode_workspace_bytes(int B, int H, int capacity);
 int cogv_attention_decode(const cogv_attn_decode_desc* d, void* stream);
@@ -317,7 +324,10 @@ int cogv_kv_quantize_e4m3(int dtype, const void* kv, long long kv_bs, long long 
  * whatever bytes they hold -- except that the new token's key / value are QUANTIZED FIRST, stored into slot *pos as bytes +
  * scale, and attended in their dequantized form (a token's key has one value in every step that reads it).  128 keys per split
  * and the 66-float partials of cogv_attention_decode: workspace, skip_combine, cogv_gemv_attn and cogv_gemv_attn_w8 as there.
- * 1 (bad argument): misaligned kv_q (16 B) / kv_scale (4 B), head_dim != 64, short workspace; 3 (unsupported): other dtypes. */
+ * first: as in cogv_attn_decode_desc (NULL: slots [0, *pos], the same kernel and bits as without the field); a padding slot's
+ * bytes AND scales are without influence.
+ * 1 (bad argument): misaligned kv_q (16 B) / kv_scale (4 B) / first (4 B), head_dim != 64, short workspace; 3 (unsupported):
+ * other dtypes. */
 typedef struct cogv_attn_decode_kv8_desc {
   int dtype; int B, H, capacity, head_dim;
   float scale;                       /* 1/sqrt(head_dim) */
@@ -328,6 +338,7 @@ typedef struct cogv_attn_decode_kv8_desc {
   const long long* pos;
   void* workspace; size_t workspace_bytes;
   int skip_combine;
+  const int* first;
 } cogv_attn_decode_kv8_desc;
 /* one decode step's attention per layer on the 8-bit cache (the model call of generation/sampling.py:139-148) */
 int cogv_attention_decode_kv8(const cogv_attn_decode_kv8_desc* d, void* stream);

@@ -10,7 +10,10 @@ reference's three stages joined on the device -- eight candidates from generate_
 difference, peak allocated memory of each), ranked by rerank_generated, the best one magnified with fill=DeviceFiller.
 `--weights e4m3` (text -> image and `--super-resolution` legs): the device forms also run with the decode steps on 8-bit copies
 of the weights (generate_on_device / DeviceFiller `weights=`), timed next to the 16-bit ones.  `--kv e4m3`: the same legs with the
-8-bit key/value cache (`kv=`), alone or together with `--weights`."""
+8-bit key/value cache (`kv=`), alone or together with `--weights`.
+`--prompts G [--nb N]` (comma lists run several settings in one process: `--prompts 8,2 --nb 1,4`): G prompts of different text
+lengths x N candidates each (default 1) for one 1024-code image per row, on ONE decode graph (generate_batch_on_device) against
+the same prompts through generate_on_device one after another, in the same process; ms per generated token per prompt for each."""
 import os, sys, time, types
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -32,7 +35,8 @@ import torch.distributed as dist
 dist.init_process_group("nccl", init_method="env://", world_size=1, rank=0)
 from cogview_amd import mpu
 from cogview_amd.fp16 import FP16_Module
-from cogview_amd.generation import (DeviceFiller, IdSpace, add_interlacing_beam_marks, filling_sequence, generate_on_device,
+from cogview_amd.generation import (DeviceFiller, IdSpace, add_interlacing_beam_marks, filling_sequence, generate_batch_on_device,
+                                    generate_on_device,
                                     inverse_prompt_score, inverse_prompt_score_on_device, magnify, plan_device_fill,
                                     post_selection_rows, rerank_generated)
 from cogview_amd.model import GPT2Model
@@ -116,6 +120,34 @@ if "--post-selection" in sys.argv:
     assert big.shape == (1, 4096) and int(big.max()) < 8192 and int(order[0]) == int(s_dev.argmax())
     print(f"generate_on_device -> rerank_generated (kept candidate {int(order[0])}, score {sc[0].item():.2f}) -> magnify with "
           f"DeviceFiller: {time.time() - t0:.2f} s for the 64 x 64 codes", flush=True)
+    sys.exit(0)
+
+if "--prompts" in sys.argv:
+    Gs = [int(x) for x in sys.argv[sys.argv.index("--prompts") + 1].split(",")]
+    nbs = [int(x) for x in sys.argv[sys.argv.index("--nb") + 1].split(",")] if "--nb" in sys.argv else [1] * len(Gs)
+    assert len(Gs) == len(nbs)
+    for G, nb in zip(Gs, nbs):
+        seqs = []
+        for g in range(G):                                                     # 20, 18, 23, 21, 26, ... text pieces
+            t = torch.randint(8192, 58192, (20 + 3 * (g // 2) - 2 * (g % 2),)).tolist()
+            seq = t + [ids["[BASE]"], ids["[BOI1]"]] + [-1] * 1024
+            add_interlacing_beam_marks(seq, nb=nb, period=3000)
+            seqs.append(torch.tensor(seq, device="cuda"))
+        generate_batch_on_device(model, seqs, args, seed=0, weights=W8, kv=KV8)           # warm-up (first-use allocations)
+        torch.cuda.synchronize(); t0 = time.time()
+        outs, scores = generate_batch_on_device(model, seqs, args, seed=1, weights=W8, kv=KV8)
+        torch.cuda.synchronize(); t_batch = time.time() - t0
+        assert all(int(o[:, -1024:].max()) < 8192 and o.shape == (nb, len(s)) for o, s in zip(outs, seqs)) and torch.isfinite(scores).all()
+        generate_on_device(model, seqs[0], args, seed=0, weights=W8, kv=KV8)              # warm-up
+        torch.cuda.synchronize(); t0 = time.time()
+        for seq in seqs:
+            out, sc = generate_on_device(model, seq, args, seed=1, weights=W8, kv=KV8)
+            assert int(out[:, -1024:].max()) < 8192 and torch.isfinite(sc).all()
+        torch.cuda.synchronize(); t_seq = time.time() - t0
+        print(f"{G} prompts x {nb} (contexts {[int((s >= 0).sum()) for s in seqs]}, weights={W8} kv={KV8}): one decode graph "
+              f"{t_batch:.2f} s = {t_batch / 1024 / G * 1e3:.2f} ms per generated token per prompt; one after another {t_seq:.2f} s = "
+              f"{t_seq / 1024 / G * 1e3:.2f} ms per generated token per prompt (prefill + capture included in both); "
+              f"{t_seq / t_batch:.2f}x", flush=True)
     sys.exit(0)
 
 for nb in (1, 8):
