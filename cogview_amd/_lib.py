@@ -186,6 +186,7 @@ SIGNATURES = {
     "cogv_gemm_w8": (_i, [C.POINTER(GemmDesc), C.POINTER(W8Weight), _vp]),
     "cogv_gemv_ln_w8": (_i, [C.POINTER(GemmDesc), C.POINTER(LnPrologue), C.POINTER(W8Weight), _vp]),
     "cogv_gemv_attn_w8": (_i, [C.POINTER(GemmDesc), C.POINTER(W8Weight), _vp, _i, _i, _vp]),
+    "cogv_gemv_plan": (_i, [_i, C.POINTER(GemmDesc), C.POINTER(W8Weight), _i, C.POINTER(C.c_int)]),
     "cogv_kv_quantize_e4m3": (_i, [_i, _vp, _i64, _i64, _i, _i, _i, _vp, _i64, _vp, _i64, _i, _i, _vp]),
     "cogv_attention_decode_kv8": (_i, [C.POINTER(AttnDecodeKv8Desc), _vp]),
     "cogv_attention_decode_workspace_bytes": (_sz, [_i, _i, _i]),
@@ -243,3 +244,24 @@ def lib():
 def check(rc, what):
     if rc != 0:
         raise CogviewHipError(f"{what} failed: {_ERR.get(rc, rc)}")
+
+
+OK, ERR_ARG, ERR_UNSUPPORTED = 0, 1, 3
+GEMV_PLAIN, GEMV_ATTN, GEMV_LN = 0, 1, 2
+GEMV_PLAN_INTS = 11
+
+
+def gemv_plan(kind, dtype, M, N, K, w8=False, nsplit=1, ldb=None):
+    """cogv_gemv_plan for a contiguous product of `kind` (GEMV_*): (error code, [generation, form, J | NWK, KCMAX | LMAX, guarded,
+    MT, tiles per workgroup, two halves, threads, workgroups, dynamic LDS bytes]).  Host only: the pointers in the descriptors
+    are aligned stand-ins that nothing reads.  w8: the product on an E4M3 weight; ldb: elements (bytes) between its rows."""
+    d = GemmDesc()
+    d.dtype, d.M, d.N, d.K, d.lda, d.ldb, d.ldc, d.splitk = dtype, M, N, K, K, K if ldb is None else ldb, N, 1
+    d.A, d.B, d.C = 0x1000, 0x2000, 0x3000
+    w = None
+    if w8:
+        w = W8Weight()
+        w.q, w.ldq, w.scale = d.B, d.ldb, 0x4000
+    out = (C.c_int * GEMV_PLAN_INTS)(*([-1] * GEMV_PLAN_INTS))
+    rc = lib().cogv_gemv_plan(kind, C.byref(d), C.byref(w) if w8 else None, nsplit, out)
+    return rc, list(out)

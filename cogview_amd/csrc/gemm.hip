@@ -47,6 +47,7 @@
 #include "gemm_gen3.cuh"
 #include "gemm_gen4.cuh"
 #include "gemv_gen1.cuh"
+#include "gemv_plan.h"
 
 namespace {
 
@@ -225,31 +226,70 @@ void launch_splitk_reduce(GemmArgs& a, hipStream_t st) {
   hipLaunchKernelGGL((splitk_reduce_kernel<T>), dim3(blocks), dim3(256), 0, st, a);
 }
 
-// Second-generation skinny-M kernels (gemv.hip, one translation unit per dtype: 0 bf16, 1 fp16).  COGV_GEMV2=0 keeps the
-// first-generation kernels below (A/B runs); a launcher returns COGV_ERR_UNSUPPORTED for a shape it does not take.
-extern "C" __attribute__((visibility("hidden"))) int cogv_gemv2_launch_0(const void* args, void* stream);
-extern "C" __attribute__((visibility("hidden"))) int cogv_gemv2_launch_1(const void* args, void* stream);
-extern "C" __attribute__((visibility("hidden"))) int cogv_gemv2_attn_launch_0(const void* args, const float* partials, int heads, int nsplit, void* stream);
-extern "C" __attribute__((visibility("hidden"))) int cogv_gemv2_attn_launch_1(const void* args, const float* partials, int heads, int nsplit, void* stream);
-extern "C" __attribute__((visibility("hidden"))) int cogv_gemv2_ln_launch_0(const void* args, int stream_f32, void* stream);
-extern "C" __attribute__((visibility("hidden"))) int cogv_gemv2_ln_launch_1(const void* args, int stream_f32, void* stream);
-inline bool gemv2_enabled() {
-  static const bool on = [] { const char* e = getenv("COGV_GEMV2"); return !e || atoi(e) != 0; }();
-  return on;
+// Skinny-M products (M <= 8: the decode step).  gv_plan (gemv_plan.h) decides every launch: a second-generation kernel of
+// gemv.hip -- one unit per weight format and dtype (0 bf16, 1 fp16), each with one entry point that takes the plan -- or, for
+// 16-bit weights outside its classes and under COGV_GEMV2=0, a first-generation kernel (gemv_gen1.cuh).
+extern "C" __attribute__((visibility("hidden"))) int cogv_gemv2_run_0(int kind, const GvPlan* plan, const GvCall* call);
+extern "C" __attribute__((visibility("hidden"))) int cogv_gemv2_run_1(int kind, const GvPlan* plan, const GvCall* call);
+extern "C" __attribute__((visibility("hidden"))) int cogv_gemv2_w8_run_0(int kind, const GvPlan* plan, const GvCall* call);
+extern "C" __attribute__((visibility("hidden"))) int cogv_gemv2_w8_run_1(int kind, const GvPlan* plan, const GvCall* call);
+
+template <typename T>
+void gemv1_launch(int kind, const GvPlan& pl, const GvCall& c) {
+  const dim3 grid(pl.grid), block(pl.threads);
+  hipStream_t st = reinterpret_cast<hipStream_t>(c.stream);
+  if (kind == GV_LN) {
+    const GemvLnArgs& a = *reinterpret_cast<const GemvLnArgs*>(c.args);       // rows [M, mt) are written as zeros-normalised junk nobody reads
+#define GEMV_LN_LAUNCH(MT_)                                                                                              \
+  do {                                                                                                                   \
+    static bool attr = false;                                                                                            \
+    if (!attr) {                                                                                                         \
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemv_ln_kernel<T, MT_, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 65536); \
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemv_ln_kernel<T, MT_, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 65536);  \
+      attr = true;                                                                                                       \
+    }                                                                                                                    \
+    if (c.stream_f32) hipLaunchKernelGGL((gemv_ln_kernel<T, MT_, true>), grid, block, pl.lds, st, a);                     \
+    else hipLaunchKernelGGL((gemv_ln_kernel<T, MT_, false>), grid, block, pl.lds, st, a);                                 \
+  } while (0)
+    if (pl.mt == 1) GEMV_LN_LAUNCH(1); else if (pl.mt == 2) GEMV_LN_LAUNCH(2); else if (pl.mt == 4) GEMV_LN_LAUNCH(4); else GEMV_LN_LAUNCH(8);
+#undef GEMV_LN_LAUNCH
+    return;
+  }
+  const GemmArgs& a = *reinterpret_cast<const GemmArgs*>(c.args);
+  if (kind == GV_ATTN) hipLaunchKernelGGL((gemv_attn_kernel<T>), grid, block, 0, st, a, c.partials, c.heads, c.nsplit);
+  else hipLaunchKernelGGL((gemv_kernel<T>), grid, block, 0, st, a);
+}
+
+// the launch of a planned product.  (A second-generation launcher answers COGV_ERR_UNSUPPORTED only when the runtime refuses the
+// two-halves kernel its LDS: the first generation takes the product then, where there is one.)
+int gemv_launch(int kind, int fmt, int dtype, GvPlan pl, const GvCall& c) {
+  static int (*const RUN[2][2])(int, const GvPlan*, const GvCall*) = {{cogv_gemv2_run_0, cogv_gemv2_run_1}, {cogv_gemv2_w8_run_0, cogv_gemv2_w8_run_1}};
+  if (pl.generation == 2) {
+    const int rc = RUN[fmt][dtype == COGV_F16](kind, &pl, &c);
+    if (rc != COGV_ERR_UNSUPPORTED || fmt == GV_W8) return rc != COGV_OK ? rc : cogv_check_launch();
+    const GemmArgs& a = *reinterpret_cast<const GemmArgs*>(c.args);          // (GemvLnArgs begins with its GemmArgs)
+    pl = gv_plan_gen1(kind, pl.mt, a.N, a.K);
+  }
+  if (dtype == COGV_F16) gemv1_launch<f16_t>(kind, pl, c);
+  else gemv1_launch<bf16_t>(kind, pl, c);
+  return cogv_check_launch();
+}
+
+// what the 16-bit skinny-M kernels of either generation do not take of a descriptor build_gemm_args accepted
+bool gemv16_refuses(int kind, const cogv_gemm_desc* d) {
+  if (d->trans_a || d->trans_b) return true;
+  if (kind == GV_PLAIN) return (d->flags & COGV_EPI_COLSUM) || d->kernel_variant != 0;      // takes every other fused epilogue
+  const int refused = COGV_EPI_COLSUM | COGV_EPI_ACCUM | COGV_EPI_DGELU | COGV_EPI_MULAUX | COGV_EPI_DROPOUT | (kind == GV_ATTN ? COGV_EPI_GELU : 0);
+  return (d->flags & refused) || d->out_f32 || d->splitk > 1;
 }
 
 template <typename T>
 int launch_gemm(const cogv_gemm_desc* d, GemmArgs& a, hipStream_t st) {
-  // skinny M (decode steps): the HBM-streaming matrix-vector kernel; takes every fused epilogue except the column sums
-  if (a.M <= GEMV_MAX_M && !d->trans_a && !d->trans_b && (a.K & 511) == 0 && (a.N & 7) == 0 && !(d->flags & COGV_EPI_COLSUM) &&
-      (a.lda & 7) == 0 && (a.ldb & 7) == 0 && d->kernel_variant == 0) {
+  // skinny M (decode steps): the HBM-streaming matrix-vector kernels
+  GvPlan pl;
+  if (!gemv16_refuses(GV_PLAIN, d) && gv_plan(GV_PLAIN, GV_W16, a.M, a.N, a.K, a.ldb, 0, pl)) {
     a.splitk = 1;
-    if (gemv2_enabled()) {
-      const int rc2 = std::is_same<T, f16_t>::value ? cogv_gemv2_launch_1(&a, st) : cogv_gemv2_launch_0(&a, st);
-      if (rc2 != COGV_ERR_UNSUPPORTED) return rc2 != COGV_OK ? rc2 : cogv_check_launch();
-    }
-    hipLaunchKernelGGL((gemv_kernel<T>), dim3(a.N / 8), dim3(256), 0, st, a);
-    return cogv_check_launch();
+    return gemv_launch(GV_PLAIN, GV_W16, d->dtype, pl, GvCall{&a, nullptr, 0, 0, 0, st});
   }
   const bool glds_ok = (a.K % BK) == 0 && a.M >= 64 && a.N >= 64 && (!d->trans_a || (a.M & 7) == 0) &&
                        (!d->trans_b || (a.N & 7) == 0) && d->kernel_variant != 1;
@@ -414,80 +454,8 @@ extern "C" int cogv_gemm(const cogv_gemm_desc* d, void* stream) {
   return launch_gemm<bf16_t>(d, a, st);
 }
 
-// y = epilogue(LN_pre([res + LN_post(z)]) . B^T): the decode step's GEMV with its LayerNorms as prologue (gemv_ln_kernel).
-extern "C" int cogv_gemv_ln(const cogv_gemm_desc* d, const cogv_ln_prologue* ln, void* stream) {
-  if (!d || !ln) return COGV_ERR_ARG;
-  GemvLnArgs a;
-  const int rc = build_gemm_args(d, a.g);
-  if (rc != COGV_OK) return rc;
-  if (d->trans_a || d->trans_b || a.g.M > GEMV_MAX_M || (a.g.K & 511) || a.g.K > 4096 || (a.g.N & 7) || (a.g.ldb & 7)) return COGV_ERR_UNSUPPORTED;
-  if (d->flags & (COGV_EPI_COLSUM | COGV_EPI_ACCUM | COGV_EPI_DGELU | COGV_EPI_MULAUX | COGV_EPI_DROPOUT) || d->out_f32 || d->splitk > 1) return COGV_ERR_UNSUPPORTED;
-  if (!ln->z || !ln->gamma || !ln->beta) return COGV_ERR_ARG;
-  if (ln->gamma_post && (!ln->beta_post || !ln->residual)) return COGV_ERR_ARG;
-  if (((uintptr_t)ln->z | (uintptr_t)ln->gamma | (uintptr_t)ln->beta | (uintptr_t)ln->gamma_post | (uintptr_t)ln->beta_post |
-       (uintptr_t)ln->residual | (uintptr_t)ln->t_out) & 15) return COGV_ERR_ARG;
-  a.z = ln->z; a.z_absmax = ln->z_absmax; a.gamma_p = ln->gamma_post; a.beta_p = ln->beta_post; a.res = ln->residual;
-  a.t_out = ln->t_out; a.gamma = ln->gamma; a.beta = ln->beta; a.eps = ln->eps;
-  const bool sf = ln->stream_f32 != 0;
-  a.g.splitk = 1;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (gemv2_enabled()) {
-    const int rc2 = d->dtype == COGV_F16 ? cogv_gemv2_ln_launch_1(&a, sf ? 1 : 0, st) : cogv_gemv2_ln_launch_0(&a, sf ? 1 : 0, st);
-    if (rc2 != COGV_ERR_UNSUPPORTED) return rc2 != COGV_OK ? rc2 : cogv_check_launch();
-  }
-  const int mt = a.g.M <= 1 ? 1 : a.g.M <= 2 ? 2 : a.g.M <= 4 ? 4 : 8;
-  const int shmem = mt * a.g.K * 2;                 // rows [M, mt) are written as zeros-normalised junk nobody reads
-  const dim3 grid(a.g.N / 8), block(256);
-#define GEMV_LN_LAUNCH(T_, MT_)                                                                                          \
-  do {                                                                                                                   \
-    static bool attr = false;                                                                                            \
-    if (!attr) {                                                                                                         \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemv_ln_kernel<T_, MT_, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 65536); \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemv_ln_kernel<T_, MT_, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 65536);  \
-      attr = true;                                                                                                       \
-    }                                                                                                                    \
-    if (sf) hipLaunchKernelGGL((gemv_ln_kernel<T_, MT_, true>), grid, block, shmem, st, a);                               \
-    else hipLaunchKernelGGL((gemv_ln_kernel<T_, MT_, false>), grid, block, shmem, st, a);                                 \
-  } while (0)
-  if (d->dtype == COGV_F16) { if (mt == 1) GEMV_LN_LAUNCH(f16_t, 1); else if (mt == 2) GEMV_LN_LAUNCH(f16_t, 2); else if (mt == 4) GEMV_LN_LAUNCH(f16_t, 4); else GEMV_LN_LAUNCH(f16_t, 8); }
-  else { if (mt == 1) GEMV_LN_LAUNCH(bf16_t, 1); else if (mt == 2) GEMV_LN_LAUNCH(bf16_t, 2); else if (mt == 4) GEMV_LN_LAUNCH(bf16_t, 4); else GEMV_LN_LAUNCH(bf16_t, 8); }
-#undef GEMV_LN_LAUNCH
-  return cogv_check_launch();
-}
-
-// y = epilogue(att . B^T), att = the combination of cogv_attention_decode's split partials (skip_combine form): gemv_attn_kernel.
-extern "C" int cogv_gemv_attn(const cogv_gemm_desc* d, const void* partials, int heads, int capacity, void* stream) {
-  if (!d || !partials || heads <= 0 || capacity <= 0 || capacity > 4096 || ((uintptr_t)partials & 15)) return COGV_ERR_ARG;
-  cogv_gemm_desc dd = *d;
-  dd.A = dd.B;                    // the A operand does not exist: keep build_gemm_args' pointer checks happy
-  dd.lda = dd.K;
-  GemmArgs a;
-  const int rc = build_gemm_args(&dd, a);
-  if (rc != COGV_OK) return rc;
-  if (d->trans_a || d->trans_b || a.M > GEMV_MAX_M || a.K != heads * 64 || (a.K & 511) || (a.N & 7) || (a.ldb & 7)) return COGV_ERR_UNSUPPORTED;
-  if (d->flags & (COGV_EPI_COLSUM | COGV_EPI_ACCUM | COGV_EPI_DGELU | COGV_EPI_MULAUX | COGV_EPI_DROPOUT | COGV_EPI_GELU) || d->out_f32 || d->splitk > 1) return COGV_ERR_UNSUPPORTED;
-  a.splitk = 1;
-  const int nsplit = (capacity + 127) / 128;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (gemv2_enabled()) {
-    const float* pw = reinterpret_cast<const float*>(partials);
-    const int rc2 = d->dtype == COGV_F16 ? cogv_gemv2_attn_launch_1(&a, pw, heads, nsplit, st) : cogv_gemv2_attn_launch_0(&a, pw, heads, nsplit, st);
-    if (rc2 != COGV_ERR_UNSUPPORTED) return rc2 != COGV_OK ? rc2 : cogv_check_launch();
-  }
-  if (d->dtype == COGV_F16) hipLaunchKernelGGL((gemv_attn_kernel<f16_t>), dim3(a.N / 8), dim3(256), 0, st, a, reinterpret_cast<const float*>(partials), heads, nsplit);
-  else hipLaunchKernelGGL((gemv_attn_kernel<bf16_t>), dim3(a.N / 8), dim3(256), 0, st, a, reinterpret_cast<const float*>(partials), heads, nsplit);
-  return cogv_check_launch();
-}
-
-// ---- the three skinny-M products on an 8-bit weight operand (gemv.hip, FormV8 / FormM8; units gemv_w8_<dtype>.o).  The operand
-//      travels in the argument block as B / ldb / wscale.  No first-generation kernel stands behind these: what the launchers
-//      do not take is COGV_ERR_UNSUPPORTED.
-extern "C" __attribute__((visibility("hidden"))) int cogv_gemv2_w8_launch_0(const void* args, void* stream);
-extern "C" __attribute__((visibility("hidden"))) int cogv_gemv2_w8_launch_1(const void* args, void* stream);
-extern "C" __attribute__((visibility("hidden"))) int cogv_gemv2_w8_attn_launch_0(const void* args, const float* partials, int heads, int nsplit, void* stream);
-extern "C" __attribute__((visibility("hidden"))) int cogv_gemv2_w8_attn_launch_1(const void* args, const float* partials, int heads, int nsplit, void* stream);
-extern "C" __attribute__((visibility("hidden"))) int cogv_gemv2_w8_ln_launch_0(const void* args, int stream_f32, void* stream);
-extern "C" __attribute__((visibility("hidden"))) int cogv_gemv2_w8_ln_launch_1(const void* args, int stream_f32, void* stream);
+// ---- the skinny-M products with a prologue, and all three on an 8-bit weight operand (gemv.hip, FormV8 / FormM8: it travels in
+//      the argument block as B / ldb / wscale; no first-generation kernel stands behind those)
 
 // the descriptor with the 8-bit operand in B's place -> argument block; `allowed`: the epilogue flags the product takes
 static int build_w8_args(const cogv_gemm_desc* d, const cogv_w8_weight* w, int allowed, bool has_a, GemmArgs& a) {
@@ -500,47 +468,93 @@ static int build_w8_args(const cogv_gemm_desc* d, const cogv_w8_weight* w, int a
   if (!has_a) { dd.A = dd.B; dd.lda = dd.K; }          // (no A operand: keep build_gemm_args' pointer checks happy)
   const int rc = build_gemm_args(&dd, a);
   if (rc != COGV_OK) return rc;
-  a.splitk = 1;
   a.wscale = w->scale;
   return COGV_OK;
 }
 
-extern "C" int cogv_gemm_w8(const cogv_gemm_desc* d, const cogv_w8_weight* w, void* stream) {
-  GemmArgs a;
-  const int rc = build_w8_args(d, w, COGV_EPI_BIAS | COGV_EPI_GELU | COGV_EPI_ABSMAX, true, a);
-  if (rc != COGV_OK) return rc;
-  if (d->aux) return COGV_ERR_UNSUPPORTED;
-  const int rc2 = d->dtype == COGV_F16 ? cogv_gemv2_w8_launch_1(&a, stream) : cogv_gemv2_w8_launch_0(&a, stream);
-  return rc2 != COGV_OK ? rc2 : cogv_check_launch();
-}
-
-extern "C" int cogv_gemv_ln_w8(const cogv_gemm_desc* d, const cogv_ln_prologue* ln, const cogv_w8_weight* w, void* stream) {
-  if (!ln) return COGV_ERR_ARG;
-  GemvLnArgs a;
-  const int rc = build_w8_args(d, w, COGV_EPI_BIAS | COGV_EPI_GELU | COGV_EPI_ABSMAX, false, a.g);
-  if (rc != COGV_OK) return rc;
-  if (d->aux || a.g.K > 4096) return COGV_ERR_UNSUPPORTED;
+static int gemv_ln_args(const cogv_ln_prologue* ln, GemvLnArgs& a) {
   if (!ln->z || !ln->gamma || !ln->beta) return COGV_ERR_ARG;
   if (ln->gamma_post && (!ln->beta_post || !ln->residual)) return COGV_ERR_ARG;
   if (((uintptr_t)ln->z | (uintptr_t)ln->gamma | (uintptr_t)ln->beta | (uintptr_t)ln->gamma_post | (uintptr_t)ln->beta_post |
        (uintptr_t)ln->residual | (uintptr_t)ln->t_out) & 15) return COGV_ERR_ARG;
   a.z = ln->z; a.z_absmax = ln->z_absmax; a.gamma_p = ln->gamma_post; a.beta_p = ln->beta_post; a.res = ln->residual;
   a.t_out = ln->t_out; a.gamma = ln->gamma; a.beta = ln->beta; a.eps = ln->eps;
-  const int sf = ln->stream_f32 != 0;
-  const int rc2 = d->dtype == COGV_F16 ? cogv_gemv2_w8_ln_launch_1(&a, sf, stream) : cogv_gemv2_w8_ln_launch_0(&a, sf, stream);
-  return rc2 != COGV_OK ? rc2 : cogv_check_launch();
+  return COGV_OK;
 }
 
-extern "C" int cogv_gemv_attn_w8(const cogv_gemm_desc* d, const cogv_w8_weight* w, const void* partials, int heads, int capacity, void* stream) {
+// Descriptor of a product of `kind` (w: its 8-bit weight, or NULL) -> argument block and launch plan, or the entry point's
+// error: the front of cogv_gemv_ln, cogv_gemv_attn, the three _w8 calls and cogv_gemv_plan (cogv_gemm's is launch_gemm).
+static int gemv_front(int kind, const cogv_gemm_desc* d, const cogv_w8_weight* w, int nsplit, GemmArgs& a, GvPlan& pl,
+                      const cogv_ln_prologue* ln = nullptr, GemvLnArgs* la = nullptr) {
+  int rc;
+  if (w) {
+    rc = build_w8_args(d, w, COGV_EPI_BIAS | COGV_EPI_ABSMAX | (kind == GV_ATTN ? 0 : COGV_EPI_GELU), kind == GV_PLAIN, a);
+    if (rc == COGV_OK && kind != GV_ATTN && d->aux) rc = COGV_ERR_UNSUPPORTED;
+  }
+  else if (!d) rc = COGV_ERR_ARG;
+  else {
+    cogv_gemm_desc dd = *d;
+    if (kind == GV_ATTN) { dd.A = dd.B; dd.lda = dd.K; }        // (as above)
+    rc = build_gemm_args(&dd, a);
+    if (rc == COGV_OK && gemv16_refuses(kind, d)) rc = COGV_ERR_UNSUPPORTED;
+  }
+  if (rc != COGV_OK) return rc;
+  a.splitk = 1;
+  if (!gv_shape_taken(kind, a.M, a.N, a.K)) return COGV_ERR_UNSUPPORTED;
+  if (ln && (rc = gemv_ln_args(ln, *la)) != COGV_OK) return rc;             // (a bad prologue is reported before a class's refusal)
+  return gv_plan(kind, w ? GV_W8 : GV_W16, a.M, a.N, a.K, a.ldb, nsplit, pl) ? COGV_OK : COGV_ERR_UNSUPPORTED;
+}
+
+// y = epilogue(LN_pre([res + LN_post(z)]) . B^T): the decode step's GEMV with its LayerNorms as prologue
+static int gemv_ln(const cogv_gemm_desc* d, const cogv_ln_prologue* ln, const cogv_w8_weight* w, void* stream) {
+  if (!ln) return COGV_ERR_ARG;
+  GemvLnArgs a;
+  GvPlan pl;
+  const int rc = gemv_front(GV_LN, d, w, 0, a.g, pl, ln, &a);
+  if (rc != COGV_OK) return rc;
+  return gemv_launch(GV_LN, w ? GV_W8 : GV_W16, d->dtype, pl, GvCall{&a, nullptr, 0, 0, ln->stream_f32 != 0, stream});
+}
+extern "C" int cogv_gemv_ln(const cogv_gemm_desc* d, const cogv_ln_prologue* ln, void* stream) { return gemv_ln(d, ln, nullptr, stream); }
+extern "C" int cogv_gemv_ln_w8(const cogv_gemm_desc* d, const cogv_ln_prologue* ln, const cogv_w8_weight* w, void* stream) {
+  return w ? gemv_ln(d, ln, w, stream) : COGV_ERR_ARG;
+}
+
+// y = epilogue(att . B^T), att = the combination of cogv_attention_decode's split partials (skip_combine form)
+static int gemv_attn(const cogv_gemm_desc* d, const cogv_w8_weight* w, const void* partials, int heads, int capacity, void* stream) {
   if (!partials || heads <= 0 || capacity <= 0 || capacity > 4096 || ((uintptr_t)partials & 15)) return COGV_ERR_ARG;
+  const int nsplit = (capacity + 127) / 128;
   GemmArgs a;
-  const int rc = build_w8_args(d, w, COGV_EPI_BIAS | COGV_EPI_ABSMAX, false, a);
+  GvPlan pl;
+  const int rc = gemv_front(GV_ATTN, d, w, nsplit, a, pl);
   if (rc != COGV_OK) return rc;
   if (a.K != heads * 64) return COGV_ERR_UNSUPPORTED;
-  const int nsplit = (capacity + 127) / 128;
-  const float* pw = reinterpret_cast<const float*>(partials);
-  const int rc2 = d->dtype == COGV_F16 ? cogv_gemv2_w8_attn_launch_1(&a, pw, heads, nsplit, stream) : cogv_gemv2_w8_attn_launch_0(&a, pw, heads, nsplit, stream);
-  return rc2 != COGV_OK ? rc2 : cogv_check_launch();
+  return gemv_launch(GV_ATTN, w ? GV_W8 : GV_W16, d->dtype, pl, GvCall{&a, reinterpret_cast<const float*>(partials), heads, nsplit, 0, stream});
+}
+extern "C" int cogv_gemv_attn(const cogv_gemm_desc* d, const void* partials, int heads, int capacity, void* stream) {
+  return gemv_attn(d, nullptr, partials, heads, capacity, stream);
+}
+extern "C" int cogv_gemv_attn_w8(const cogv_gemm_desc* d, const cogv_w8_weight* w, const void* partials, int heads, int capacity, void* stream) {
+  return w ? gemv_attn(d, w, partials, heads, capacity, stream) : COGV_ERR_ARG;
+}
+
+extern "C" int cogv_gemm_w8(const cogv_gemm_desc* d, const cogv_w8_weight* w, void* stream) {
+  if (!w) return COGV_ERR_ARG;
+  GemmArgs a;
+  GvPlan pl;
+  const int rc = gemv_front(GV_PLAIN, d, w, 0, a, pl);
+  return rc != COGV_OK ? rc : gemv_launch(GV_PLAIN, GV_W8, d->dtype, pl, GvCall{&a, nullptr, 0, 0, 0, stream});
+}
+
+// host-only: the plan the entry points above (and cogv_gemm's skinny case) would launch with
+extern "C" int cogv_gemv_plan(int kind, const cogv_gemm_desc* d, const cogv_w8_weight* w, int nsplit, int out[COGV_GEMV_PLAN_INTS]) {
+  if (!out || kind < COGV_GEMV_PLAIN || kind > COGV_GEMV_LN || (kind == COGV_GEMV_ATTN && nsplit < 1)) return COGV_ERR_ARG;
+  GemmArgs a;
+  GvPlan pl;
+  const int rc = gemv_front(1 << kind, d, w, nsplit, a, pl);
+  if (rc != COGV_OK) return rc;
+  const int v[COGV_GEMV_PLAN_INTS] = {pl.generation, pl.form, pl.p0, pl.p1, pl.guard, pl.mt, pl.tw, pl.k2, pl.threads, pl.grid, pl.lds};
+  for (int i = 0; i < COGV_GEMV_PLAN_INTS; ++i) out[i] = v[i];
+  return COGV_OK;
 }
 
 // Several GEMMs of the same dtype and layout in one persistent launch of the generation-3 kernel (see GroupArgs).

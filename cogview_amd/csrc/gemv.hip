@@ -33,11 +33,12 @@
 // every rounding point stay those of the 16-bit form, and the fp32 sum of column n is multiplied by scale[n] once, in front
 // of the shared epilogue.  A slot of the same shape holds half the bytes, so the class table changes to keep 16-20 KB in flight
 // per wave: FormV8 gives a wave twice the columns (8-byte slots: a lane keeps FormV's 8 contraction elements), FormM8 gives a
-// 16-column tile half the waves (a 16-byte load is two MFMA fragments).  The table stands in front of the launchers below.
+// 16-column tile half the waves (a 16-byte load is two MFMA fragments).  The classes of both formats: gemv_plan.h.
 //
 // Compiled as two translation units (-DCOGV_GEMV_TU=0: bf16, 1: fp16; build.py) for the 16-bit forms and two more with
 // -DCOGV_GEMV_W8 for the 8-bit forms; without the macro this file is empty.
 #include "gemm_shared.cuh"
+#include "gemv_plan.h"
 
 #include <cstdlib>
 #include <type_traits>
@@ -812,285 +813,89 @@ void gemv2_ln_kernel(const GemvLnArgs q) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// host side.  One row: FormV, (J, chunks) classes -- exact for the widths of the model family (h = 1024: K = 1024 / 4096;
-// h = 2560: K = 2560 / 10240), any other multiple of 512 takes the guarded two-column form.  2 .. 8 rows: FormM, the waves of a
-// workgroup by K (4 up to 2560, 8 up to 5120, 16 up to 10240): at most 20 loads per lane.
+// host side: from a launch plan (gemv_plan.h: the class list, and gv_plan(), which gemm.hip asked) to the instantiation.  This
+// unit expands its format's rows of that list once, in gv2_run; nothing here decides anything.
 using TT = std::conditional<COGV_GEMV_TU != 0, f16_t, bf16_t>::type;
-
-inline int gv2_mt(int M) { return M <= 1 ? 1 : M <= 2 ? 2 : M <= 4 ? 4 : 8; }
-// x rows in LDS (dynamic) + the kernels' static arrays stay inside the 64 KB a workgroup gets without an attribute; larger
-// row blocks (K = 10240 with more than two rows) go to the first-generation kernels
-constexpr size_t GV2_MAX_SHMEM = 56 * 1024;
-
-template <int J, int KCMAX, bool G> using FV = FormV<TT, J, KCMAX, G, 1, 4>;
-template <int NWK, int LMAX, bool G, int MT, int TW = 1> using FM = FormM<TT, NWK, TW, LMAX, G, MT>;
-
-// CALL(F, MT) for 2 / 4 / 8 rows with FormM<NWK, TW, LMAX, G, MT>: TW4 = tiles per workgroup at 4 and 8 rows
-#define GV2_M_SWITCH(mt, CALL, NWK_, LMAX_, G_, TW4_)                       \
-  do {                                                                      \
-    if ((mt) == 2) { CALL((FM<NWK_, LMAX_, G_, 2>), 2); }                   \
-    else if ((mt) == 4) { CALL((FM<NWK_, LMAX_, G_, 4, TW4_>), 4); }        \
-    else { CALL((FM<NWK_, LMAX_, G_, 8, TW4_>), 8); }                       \
-  } while (0)
-
-}  // namespace
 
 #define GV2_CAT2(a, b) a##b
 #define GV2_CAT(a, b) GV2_CAT2(a, b)
-#define GV2_UNWRAP(...) __VA_ARGS__
-
 #ifndef COGV_GEMV_W8
-// C = epilogue(A B^T), M <= 8.  COGV_ERR_UNSUPPORTED: the caller falls back to the first-generation kernel.
-extern "C" __attribute__((visibility("hidden"))) int GV2_CAT(cogv_gemv2_launch_, COGV_GEMV_TU)(const void* args, void* stream) {
-  const GemmArgs& a = *reinterpret_cast<const GemmArgs*>(args);
-  const int mt = gv2_mt(a.M), kc = a.K >> 9;
-  if (a.M < 1 || a.M > GEMV_MAX_M || (a.K & 511) || a.K > 10240 || (a.N & 7)) return COGV_ERR_UNSUPPORTED;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-#define GV2_PLAIN(F_, MT_)                                                                                                   \
-  do {                                                                                                                       \
-    typedef GV2_UNWRAP F_ FF;                                                                                                \
-    const size_t shmem = (size_t)MT_ * (a.K + FF::XPAD) * 2;                                                                 \
-    if (shmem > GV2_MAX_SHMEM) return COGV_ERR_UNSUPPORTED;                                                                  \
-    hipLaunchKernelGGL((gemv2_kernel<TT, FF, MT_>), dim3((a.N + FF::COLS - 1) / FF::COLS), dim3(FF::NW * 64), shmem, st, a); \
-  } while (0)
-  // the two-halves kernel: LDS for half the row length; above 64 KB in all (8 rows of K = 10240: 82 KB + 17 KB static) by attribute
-#define GV2_PLAIN_K2(F_, MT_)                                                                                                \
-  do {                                                                                                                       \
-    typedef GV2_UNWRAP F_ FF;                                                                                                \
-    const size_t shmem = (size_t)MT_ * (a.K / 2 + FF::XPAD) * 2;                                                             \
-    static bool attr = false;                                                                                                \
-    if (!attr) {                                                                                                             \
-      if (shmem > GV2_MAX_SHMEM &&                                                                                           \
-          hipFuncSetAttribute(reinterpret_cast<const void*>(&gemv2_k2_kernel<TT, FF, MT_>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                              (int)shmem) != hipSuccess)                                                                    \
-        return COGV_ERR_UNSUPPORTED;                                                                                         \
-      attr = true;                                                                                                           \
-    }                                                                                                                        \
-    hipLaunchKernelGGL((gemv2_k2_kernel<TT, FF, MT_>), dim3((a.N + FF::COLS - 1) / FF::COLS), dim3(FF::NW * 64), shmem, st, a); \
-  } while (0)
-  if (mt == 1) {
-    if (a.K == 1024) GV2_PLAIN((FV<8, 2, false>), 1);
-    else if (a.K == 2560) GV2_PLAIN((FV<4, 5, false>), 1);
-    else if (a.K == 4096) GV2_PLAIN((FV<2, 8, false>), 1);
-    else if (a.K == 10240) GV2_PLAIN((FV<2, 20, false>), 1);
-    else GV2_PLAIN((FV<2, 20, true>), 1);
-  } else {
-    if (a.K == 1024) GV2_M_SWITCH(mt, GV2_PLAIN, 4, 8, false, 1);
-    else if (a.K == 2560) GV2_M_SWITCH(mt, GV2_PLAIN, 4, 20, false, 1);
-    else if (a.K == 4096) GV2_M_SWITCH(mt, GV2_PLAIN, 8, 16, false, 1);
-    else if (a.K == 10240) {
-      if (mt == 2) GV2_PLAIN((FM<16, 20, false, 2>), 2);
-      else if (mt == 4) GV2_PLAIN_K2((FM<16, 20, false, 4>), 4);
-      else GV2_PLAIN_K2((FM<16, 20, false, 8>), 8);
+template <int J, int KCMAX, bool G> using GvV = FormV<TT, J, KCMAX, G, 1, 4>;
+template <int NWK, int LMAX, bool G, int MT, int TW> using GvM = FormM<TT, NWK, TW, LMAX, G, MT>;
+#define GV2_CLASSES GV_CLASSES_16
+#define GV2_RUN GV2_CAT(cogv_gemv2_run_, COGV_GEMV_TU)
+#else   // (units gemv_w8_<dtype>.o: the same kernels on the 8-bit forms; nothing of the 16-bit forms is instantiated here)
+template <int J, int KCMAX, bool G> using GvV = FormV8<TT, J, KCMAX, G, 1, 4>;
+template <int NWK, int LMAX, bool G, int MT, int TW> using GvM = FormM8<TT, NWK, TW, LMAX, G, MT>;
+#define GV2_CLASSES GV_CLASSES_8
+#define GV2_RUN GV2_CAT(cogv_gemv2_w8_run_, COGV_GEMV_TU)
+#endif
+
+// One class at one MT: F its form with one tile per workgroup (plain and attention kind), FL the LayerNorm kind's.  Only the
+// kinds in KINDS are instantiated, the plain one as the two-halves kernel where K2 says so.
+template <typename F, typename FL, int FORM, int P0, int TWL, int MT, int KINDS, bool K2>
+int gv2_launch(int kind, const GvPlan& pl, const GvCall& c) {
+  static_assert(F::NW * 64 == gv_threads(FORM, P0, 1) && F::COLS == gv_cols(FORM, P0, 1) && F::XPAD == gv_xpad(FORM), "gemv_plan.h");
+  static_assert(FL::NW * 64 == gv_threads(FORM, P0, TWL) && FL::COLS == gv_cols(FORM, P0, TWL) && FL::XPAD == gv_xpad(FORM), "gemv_plan.h");
+  const dim3 grid(pl.grid), block(pl.threads);
+  const size_t lds = (size_t)pl.lds;
+  hipStream_t st = reinterpret_cast<hipStream_t>(c.stream);
+  if constexpr ((KINDS & GV_LN) != 0) {
+    if (kind == GV_LN) {
+      const GemvLnArgs& a = *reinterpret_cast<const GemvLnArgs*>(c.args);
+      if (c.stream_f32) hipLaunchKernelGGL((gemv2_ln_kernel<TT, FL, MT, true>), grid, block, lds, st, a);
+      else hipLaunchKernelGGL((gemv2_ln_kernel<TT, FL, MT, false>), grid, block, lds, st, a);
+      return COGV_OK;
     }
-    else if (kc <= 5) GV2_M_SWITCH(mt, GV2_PLAIN, 4, 20, true, 1);
-    else if (kc <= 10) GV2_M_SWITCH(mt, GV2_PLAIN, 8, 20, true, 1);
-    else return COGV_ERR_UNSUPPORTED;
   }
-#undef GV2_PLAIN
-#undef GV2_PLAIN_K2
-  return COGV_OK;
+  const GemmArgs& a = *reinterpret_cast<const GemmArgs*>(c.args);
+  if constexpr ((KINDS & GV_ATTN) != 0) {
+    if (kind == GV_ATTN) {
+      hipLaunchKernelGGL((gemv2_attn_kernel<TT, F, MT>), grid, block, lds, st, a, c.partials, c.heads, c.nsplit);
+      return COGV_OK;
+    }
+  }
+  if constexpr ((KINDS & GV_PLAIN) != 0) {
+    if (kind == GV_PLAIN) {
+      if constexpr (K2) {
+        // the two-halves kernel: LDS for half the row length; above 64 KB in all by attribute
+        static bool attr = false;
+        if (!attr) {
+          if (lds > (size_t)GV_MAX_SHMEM &&
+              hipFuncSetAttribute(reinterpret_cast<const void*>(&gemv2_k2_kernel<TT, F, MT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+            return COGV_ERR_UNSUPPORTED;
+          attr = true;
+        }
+        hipLaunchKernelGGL((gemv2_k2_kernel<TT, F, MT>), grid, block, lds, st, a);
+      } else {
+        hipLaunchKernelGGL((gemv2_kernel<TT, F, MT>), grid, block, lds, st, a);
+      }
+      return COGV_OK;
+    }
+  }
+  return COGV_ERR_UNSUPPORTED;
 }
 
-extern "C" __attribute__((visibility("hidden"))) int GV2_CAT(cogv_gemv2_attn_launch_, COGV_GEMV_TU)(const void* args, const float* partials, int heads,
-                                                                                                  int nsplit, void* stream) {
-  const GemmArgs& a = *reinterpret_cast<const GemmArgs*>(args);
-  const int mt = gv2_mt(a.M), kc = a.K >> 9;
-  if (a.M < 1 || a.M > GEMV_MAX_M || (a.K & 511) || a.K > 10240 || (a.N & 7) || nsplit > 32) return COGV_ERR_UNSUPPORTED;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-#define GV2_ATTN(F_, MT_)                                                                                                         \
-  do {                                                                                                                            \
-    typedef GV2_UNWRAP F_ FF;                                                                                                     \
-    const size_t shmem = (size_t)MT_ * (a.K + FF::XPAD) * 2;                                                                      \
-    if (shmem > GV2_MAX_SHMEM) return COGV_ERR_UNSUPPORTED;                                                                       \
-    hipLaunchKernelGGL((gemv2_attn_kernel<TT, FF, MT_>), dim3((a.N + FF::COLS - 1) / FF::COLS), dim3(FF::NW * 64), shmem, st, a,  \
-                       partials, heads, nsplit);                                                                                  \
-  } while (0)
-  // (the same classes as cogv_gemv2_launch for every (K, M): the combine-prologue form and the two-launch form of the projection
-  //  agree bit for bit -- in FormV a column's arithmetic does not even depend on the class)
-  if (mt == 1) {
-    if (a.K == 1024) GV2_ATTN((FV<8, 2, false>), 1);
-    else if (a.K == 2560) GV2_ATTN((FV<4, 5, false>), 1);
-    else GV2_ATTN((FV<2, 20, true>), 1);
-  } else {
-    if (a.K == 1024) GV2_M_SWITCH(mt, GV2_ATTN, 4, 8, false, 1);
-    else if (a.K == 2560) GV2_M_SWITCH(mt, GV2_ATTN, 4, 20, false, 1);
-    else if (a.K == 4096 || a.K == 10240) return COGV_ERR_UNSUPPORTED;     // (exact FormM classes of the plain form: not instantiated here)
-    else if (kc <= 5) GV2_M_SWITCH(mt, GV2_ATTN, 4, 20, true, 1);
-    else if (kc <= 10) GV2_M_SWITCH(mt, GV2_ATTN, 8, 20, true, 1);
-    else return COGV_ERR_UNSUPPORTED;
-  }
-#undef GV2_ATTN
-  return COGV_OK;
-}
+#define GV2_RUN_V(P0, P1, G, KINDS, K2MTS, TW2, TW48) gv2_launch<GvV<P0, P1, G>, GvV<P0, P1, G>, GV_FORM_V, P0, 1, 1, KINDS, false>(kind, pl, c)
+#define GV2_RUN_MT(P0, P1, G, KINDS, K2MTS, TWL, MT) \
+  gv2_launch<GvM<P0, P1, G, MT, 1>, GvM<P0, P1, G, MT, TWL>, GV_FORM_M, P0, TWL, MT, KINDS, ((K2MTS) & MT) != 0>(kind, pl, c)
+#define GV2_RUN_M(P0, P1, G, KINDS, K2MTS, TW2, TW48)                                  \
+  (pl.mt == 2 ? GV2_RUN_MT(P0, P1, G, KINDS, K2MTS, TW2, 2)                            \
+              : pl.mt == 4 ? GV2_RUN_MT(P0, P1, G, KINDS, K2MTS, TW48, 4) : GV2_RUN_MT(P0, P1, G, KINDS, K2MTS, TW48, 8))
+#define GV2_RUN_ROW(NAME, FORM, KF, KT, P0, P1, G, KINDS, STOP, K2MTS, TW2, TW48) \
+  case GVC_##NAME: return GV2_RUN_##FORM(P0, P1, G, KINDS, K2MTS, TW2, TW48);
 
-extern "C" __attribute__((visibility("hidden"))) int GV2_CAT(cogv_gemv2_ln_launch_, COGV_GEMV_TU)(const void* args, int stream_f32, void* stream) {
-  const GemvLnArgs& a = *reinterpret_cast<const GemvLnArgs*>(args);
-  const int mt = gv2_mt(a.g.M), kc = a.g.K >> 9;
-  if (a.g.M < 1 || a.g.M > GEMV_MAX_M || (a.g.K & 511) || a.g.K > 4096 || (a.g.N & 7)) return COGV_ERR_UNSUPPORTED;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-#define GV2_LN(F_, MT_)                                                                                                          \
-  do {                                                                                                                           \
-    typedef GV2_UNWRAP F_ FF;                                                                                                    \
-    const size_t shmem = (size_t)MT_ * (a.g.K + FF::XPAD) * 2;                                                                   \
-    if (shmem > GV2_MAX_SHMEM) return COGV_ERR_UNSUPPORTED;                                                                      \
-    const dim3 grid((a.g.N + FF::COLS - 1) / FF::COLS), block(FF::NW * 64);                                                      \
-    if (stream_f32) hipLaunchKernelGGL((gemv2_ln_kernel<TT, FF, MT_, true>), grid, block, shmem, st, a);                         \
-    else hipLaunchKernelGGL((gemv2_ln_kernel<TT, FF, MT_, false>), grid, block, shmem, st, a);                                   \
-  } while (0)
-  if (mt == 1) {
-    if (a.g.K == 1024) GV2_LN((FV<8, 2, false>), 1);
-    else if (a.g.K == 2560) GV2_LN((FV<4, 5, false>), 1);
-    else GV2_LN((FormV<TT, 2, 8, true, 1, 4>), 1);
-  } else {
-    if (a.g.K == 1024) GV2_M_SWITCH(mt, GV2_LN, 4, 8, false, 2);
-    else if (a.g.K == 2560) GV2_M_SWITCH(mt, GV2_LN, 4, 20, false, 2);
-    else if (kc <= 5) GV2_M_SWITCH(mt, GV2_LN, 4, 20, true, 2);
-    else GV2_M_SWITCH(mt, GV2_LN, 8, 20, true, 1);
-  }
-#undef GV2_LN
-  return COGV_OK;
-}
-
-#else  // COGV_GEMV_W8: the same three kernels on the 8-bit forms (units gemv_w8_<dtype>.o; nothing above is instantiated here,
-       // and nothing below in the 16-bit units: their code is what it was)
-// Classes.  Bytes in flight per wave as in the 16-bit table; what halves is the number of waves that share a column block:
-//   one row   (FormV8, 4 waves, 8-byte slots):   K = 1024: J = 16 (32 slots, 16 KB)   2560: J = 8 (40, 20 KB)   4096: J = 4 (32, 16 KB)
-//                                                10240: J = 4 (80, 40 KB)   other K % 512 == 0: J = 4 guarded (<= 80; LN prologue: <= 32)
-//   2..8 rows (FormM8, 16-byte loads, NWK waves per 16 columns):   K = 1024: NWK = 2, L = 8   2560: NWK = 2, L = 20   4096: NWK = 4, L = 16
-//                                                10240: NWK = 8, L = 20   guarded: K <= 2560: NWK = 2, K <= 5120: NWK = 4 (L <= 20)
-//   x rows of more than 56 KB are staged in two halves (K = 10240 with 3 .. 8 rows, K = 4096 with 5 .. 8); the guarded classes and
-//   the prologue forms have no such kernel: COGV_ERR_UNSUPPORTED there (5 .. 8 rows above K = 3072).  There is no other kernel
-//   to fall back to: every shape outside this table is COGV_ERR_UNSUPPORTED.
-namespace {
-template <int J, int KCMAX, bool G> using FV8 = FormV8<TT, J, KCMAX, G, 1, 4>;
-template <int NWK, int LMAX, bool G, int MT, int TW = 1> using FM8 = FormM8<TT, NWK, TW, LMAX, G, MT>;
-// CALL(F, MT) for 2 / 4 / 8 rows with FormM8<NWK, TW, LMAX, G, MT>: TW2 / TW4 = tiles per workgroup at 2 and at 4 / 8 rows
-#define GV2_M8_SWITCH(mt, CALL, NWK_, LMAX_, G_, TW2_, TW4_)                \
-  do {                                                                      \
-    if ((mt) == 2) { CALL((FM8<NWK_, LMAX_, G_, 2, TW2_>), 2); }            \
-    else if ((mt) == 4) { CALL((FM8<NWK_, LMAX_, G_, 4, TW4_>), 4); }       \
-    else { CALL((FM8<NWK_, LMAX_, G_, 8, TW4_>), 8); }                      \
-  } while (0)
-inline bool gv2_w8_args_ok(const GemmArgs& a, int kmax) {
-  return a.M >= 1 && a.M <= GEMV_MAX_M && (a.K & 511) == 0 && a.K <= kmax && (a.N & 7) == 0 && (a.ldb & 15) == 0 && a.ldb >= a.K &&
-         a.wscale && (((uintptr_t)a.B | (uintptr_t)a.wscale) & 15) == 0;
-}
 }  // namespace
 
-extern "C" __attribute__((visibility("hidden"))) int GV2_CAT(cogv_gemv2_w8_launch_, COGV_GEMV_TU)(const void* args, void* stream) {
-  const GemmArgs& a = *reinterpret_cast<const GemmArgs*>(args);
-  const int mt = gv2_mt(a.M), kc = a.K >> 9;
-  if (!gv2_w8_args_ok(a, 10240)) return COGV_ERR_UNSUPPORTED;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-#define GV2_PLAIN(F_, MT_)                                                                                                   \
-  do {                                                                                                                       \
-    typedef GV2_UNWRAP F_ FF;                                                                                                \
-    const size_t shmem = (size_t)MT_ * (a.K + FF::XPAD) * 2;                                                                 \
-    if (shmem > GV2_MAX_SHMEM) return COGV_ERR_UNSUPPORTED;                                                                  \
-    hipLaunchKernelGGL((gemv2_kernel<TT, FF, MT_>), dim3((a.N + FF::COLS - 1) / FF::COLS), dim3(FF::NW * 64), shmem, st, a); \
-  } while (0)
-#define GV2_PLAIN_K2(F_, MT_)                                                                                                \
-  do {                                                                                                                       \
-    typedef GV2_UNWRAP F_ FF;                                                                                                \
-    const size_t shmem = (size_t)MT_ * (a.K / 2 + FF::XPAD) * 2;                                                             \
-    static bool attr = false;                                                                                                \
-    if (!attr) {                                                                                                             \
-      if (shmem > GV2_MAX_SHMEM &&                                                                                           \
-          hipFuncSetAttribute(reinterpret_cast<const void*>(&gemv2_k2_kernel<TT, FF, MT_>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                              (int)shmem) != hipSuccess)                                                                    \
-        return COGV_ERR_UNSUPPORTED;                                                                                         \
-      attr = true;                                                                                                           \
-    }                                                                                                                        \
-    hipLaunchKernelGGL((gemv2_k2_kernel<TT, FF, MT_>), dim3((a.N + FF::COLS - 1) / FF::COLS), dim3(FF::NW * 64), shmem, st, a); \
-  } while (0)
-  if (mt == 1) {
-    if (a.K == 1024) GV2_PLAIN((FV8<16, 2, false>), 1);
-    else if (a.K == 2560) GV2_PLAIN((FV8<8, 5, false>), 1);
-    else if (a.K == 4096) GV2_PLAIN((FV8<4, 8, false>), 1);
-    else if (a.K == 10240) GV2_PLAIN((FV8<4, 20, false>), 1);
-    else GV2_PLAIN((FV8<4, 20, true>), 1);
-  } else {
-    if (a.K == 1024) GV2_M8_SWITCH(mt, GV2_PLAIN, 2, 8, false, 1, 1);
-    else if (a.K == 2560) GV2_M8_SWITCH(mt, GV2_PLAIN, 2, 20, false, 1, 1);
-    else if (a.K == 4096) {
-      if (mt == 2) GV2_PLAIN((FM8<4, 16, false, 2>), 2);
-      else if (mt == 4) GV2_PLAIN((FM8<4, 16, false, 4>), 4);
-      else GV2_PLAIN_K2((FM8<4, 16, false, 8>), 8);
-    }
-    else if (a.K == 10240) {
-      if (mt == 2) GV2_PLAIN((FM8<8, 20, false, 2>), 2);
-      else if (mt == 4) GV2_PLAIN_K2((FM8<8, 20, false, 4>), 4);
-      else GV2_PLAIN_K2((FM8<8, 20, false, 8>), 8);
-    }
-    else if (kc <= 5) GV2_M8_SWITCH(mt, GV2_PLAIN, 2, 20, true, 1, 1);
-    else if (kc <= 10) GV2_M8_SWITCH(mt, GV2_PLAIN, 4, 20, true, 1, 1);
-    else return COGV_ERR_UNSUPPORTED;
-  }
-#undef GV2_PLAIN
-#undef GV2_PLAIN_K2
-  return COGV_OK;
-}
 
-extern "C" __attribute__((visibility("hidden"))) int GV2_CAT(cogv_gemv2_w8_attn_launch_, COGV_GEMV_TU)(const void* args, const float* partials, int heads,
-                                                                                                     int nsplit, void* stream) {
-  const GemmArgs& a = *reinterpret_cast<const GemmArgs*>(args);
-  const int mt = gv2_mt(a.M), kc = a.K >> 9;
-  if (!gv2_w8_args_ok(a, 10240) || nsplit > 32) return COGV_ERR_UNSUPPORTED;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-#define GV2_ATTN(F_, MT_)                                                                                                         \
-  do {                                                                                                                            \
-    typedef GV2_UNWRAP F_ FF;                                                                                                     \
-    const size_t shmem = (size_t)MT_ * (a.K + FF::XPAD) * 2;                                                                      \
-    if (shmem > GV2_MAX_SHMEM) return COGV_ERR_UNSUPPORTED;                                                                       \
-    hipLaunchKernelGGL((gemv2_attn_kernel<TT, FF, MT_>), dim3((a.N + FF::COLS - 1) / FF::COLS), dim3(FF::NW * 64), shmem, st, a,  \
-                       partials, heads, nsplit);                                                                                  \
-  } while (0)
-  // (for every (K, M) the association of cogv_gemv2_w8_launch: the combine-prologue form and the two-launch form of the projection
-  //  agree bit for bit -- a FormM8 class's arithmetic depends on NWK only, so the guarded NWK = 4 class stands in for K = 4096)
-  if (mt == 1) {
-    if (a.K == 1024) GV2_ATTN((FV8<16, 2, false>), 1);
-    else if (a.K == 2560) GV2_ATTN((FV8<8, 5, false>), 1);
-    else GV2_ATTN((FV8<4, 20, true>), 1);
-  } else {
-    if (a.K == 1024) GV2_M8_SWITCH(mt, GV2_ATTN, 2, 8, false, 1, 1);
-    else if (a.K == 2560) GV2_M8_SWITCH(mt, GV2_ATTN, 2, 20, false, 1, 1);
-    else if (kc <= 5) GV2_M8_SWITCH(mt, GV2_ATTN, 2, 20, true, 1, 1);
-    else if (kc <= 10) GV2_M8_SWITCH(mt, GV2_ATTN, 4, 20, true, 1, 1);
-    else return COGV_ERR_UNSUPPORTED;
+// the unit's one entry point: the kernel of plan `pl` (generation 2, of this unit's format) for a product of `kind`
+extern "C" __attribute__((visibility("hidden"))) int GV2_RUN(int kind, const GvPlan* plan, const GvCall* call) {
+  const GvPlan& pl = *plan;
+  const GvCall& c = *call;
+  switch (pl.cls) {
+    GV2_CLASSES(GV2_RUN_ROW)
+    default: return COGV_ERR_UNSUPPORTED;
   }
-#undef GV2_ATTN
-  return COGV_OK;
 }
-
-extern "C" __attribute__((visibility("hidden"))) int GV2_CAT(cogv_gemv2_w8_ln_launch_, COGV_GEMV_TU)(const void* args, int stream_f32, void* stream) {
-  const GemvLnArgs& a = *reinterpret_cast<const GemvLnArgs*>(args);
-  const int mt = gv2_mt(a.g.M), kc = a.g.K >> 9;
-  if (!gv2_w8_args_ok(a.g, 4096)) return COGV_ERR_UNSUPPORTED;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-#define GV2_LN(F_, MT_)                                                                                                          \
-  do {                                                                                                                           \
-    typedef GV2_UNWRAP F_ FF;                                                                                                    \
-    const size_t shmem = (size_t)MT_ * (a.g.K + FF::XPAD) * 2;                                                                   \
-    if (shmem > GV2_MAX_SHMEM) return COGV_ERR_UNSUPPORTED;                                                                      \
-    const dim3 grid((a.g.N + FF::COLS - 1) / FF::COLS), block(FF::NW * 64);                                                      \
-    if (stream_f32) hipLaunchKernelGGL((gemv2_ln_kernel<TT, FF, MT_, true>), grid, block, shmem, st, a);                         \
-    else hipLaunchKernelGGL((gemv2_ln_kernel<TT, FF, MT_, false>), grid, block, shmem, st, a);                                   \
-  } while (0)
-  // (the prologue wants 4 or 8 waves: 2 tiles per workgroup at 2 rows, 4 at 4 and 8 rows -- the thread counts of the 16-bit table)
-  if (mt == 1) {
-    if (a.g.K == 1024) GV2_LN((FV8<16, 2, false>), 1);
-    else if (a.g.K == 2560) GV2_LN((FV8<8, 5, false>), 1);
-    else GV2_LN((FormV8<TT, 4, 8, true, 1, 4>), 1);
-  } else {
-    if (a.g.K == 1024) GV2_M8_SWITCH(mt, GV2_LN, 2, 8, false, 2, 4);
-    else if (a.g.K == 2560) GV2_M8_SWITCH(mt, GV2_LN, 2, 20, false, 2, 4);
-    else if (kc <= 5) GV2_M8_SWITCH(mt, GV2_LN, 2, 20, true, 2, 4);
-    else GV2_M8_SWITCH(mt, GV2_LN, 4, 20, true, 2, 2);
-  }
-#undef GV2_LN
-  return COGV_OK;
-}
-#endif  // COGV_GEMV_W8
 
 #endif  // COGV_GEMV_TU

@@ -1024,15 +1024,27 @@ class W8Weights:
 
 
 def w8_decode_supported(tr, batch):
-    """What the 8-bit skinny-M kernels cover (include/cogview_hip.h, cogv_gemm_w8): both contraction lengths of the model, h and
-    4h, at this row count.  Returns None, or the reason as a string."""
+    """The 8-bit decode step at this row count: every product it will issue -- the chain's (decode_chain) where
+    decode_chain_supported, else the layer-by-layer step's (decode_layers_w8) -- is put to the library's own launch plan
+    (cogv_gemv_plan: host only, nothing is touched).  The tied-logits product is asked with h columns: N decides a grid, never
+    whether a class takes the product.  Returns None, or the reason as a string."""
+    from . import _lib
+    att = tr.layers[0].attention
     h = tr.layers[0].input_layernorm.weight.shape[0]
     f = tr.layers[0].mlp.dense_h_to_4h.weight.shape[0]
+    hp = att.num_attention_heads_per_partition * 64
     if batch > 8:
         return f"batch {batch} > 8 rows"
-    for k in (h, f):
-        if k % 512 or k > 10240 or (batch > 1 and k > 5120 and k not in (10240,)) or (batch > 4 and k > 3072 and k not in (4096, 10240)):
-            return f"contraction length {k} at {batch} row(s) is outside the 8-bit kernels' classes"
+    plain, attn, ln = _lib.GEMV_PLAIN, _lib.GEMV_ATTN, _lib.GEMV_LN
+    if decode_chain_supported(tr, batch):
+        # (the projection's form follows _decode_fuse_combine() at run time: both must be there)
+        products = [(ln, 3 * hp, h), (plain, h, hp)] + ([(attn, h, hp)] if hp % 512 == 0 else []) + [(ln, f, h), (plain, h, f), (ln, h, h)]
+    else:
+        products = [(plain, 3 * hp, h), (plain, h, hp), (plain, f, h), (plain, h, f), (plain, h, h)]
+    dtype = _lib.BF16 if att.query_key_value.weight.dtype == torch.bfloat16 else _lib.F16
+    for kind, n, k in products:
+        if _lib.gemv_plan(kind, dtype, batch, n, k, w8=True)[0] != _lib.OK:
+            return f"contraction length {k} at {batch} row(s) is outside the 8-bit kernels' classes ({('plain', 'combine-prologue', 'LayerNorm-prologue')[kind]} product, {n} columns)"
     return None
 
 
@@ -1044,20 +1056,30 @@ def decode_chain(tr, h0, absmax0, slots, emb_weight, w8=None):
     prologue of the tied-logits GEMV.  Same arithmetic and rounding points as the layer-by-layer path
     (mpu/sparse_transformer.py:314-342, 612; model/gpt2_modeling.py:115-118).  h0 [b, 1, h]; slots: StaticKVSlot per
     layer.  Returns logits [b, 1, V].
-    w8 (W8Weights): the same five launches on the 8-bit copies of the weights (_decode_chain_w8)."""
-    if w8 is not None:
-        return _decode_chain_w8(tr, h0, absmax0, slots, w8)
+    w8 (W8Weights): launch for launch the same chain on the 8-bit copies of the weights, each product reading (q, scale) in
+    place of the 16-bit matrix (emb_weight is not read)."""
     b, s, h = h0.shape
     assert s == 1
-    dev = h0.device
+    if w8 is None:
+        gemv_ln, gemm, logits_w = ops.gemv_ln, ops.gemm, emb_weight
+        operands = ((l.attention.query_key_value.weight, l.attention.dense.weight, l.mlp.dense_h_to_4h.weight, l.mlp.dense_4h_to_h.weight)
+                    for l in tr.layers)
+
+        def gemv_attn(parts, npp, cap, w, bias):
+            return ops.gemv_attn(parts, b, npp, cap, w, bias=bias)
+    else:
+        gemv_ln, gemm, logits_w, operands = ops.gemv_ln_w8, ops.gemm_w8, w8.emb, w8.layers
+
+        def gemv_attn(parts, npp, cap, w, bias):
+            return ops.gemv_attn_w8(parts, b, npp, cap, w, w8.dtype, bias=bias)
     z, z_absmax, post, res = h0.view(b, h), absmax0, None, None
-    for layer, slot in zip(tr.layers, slots):
+    for layer, slot, (w_qkv, w_dense, w_h4h, w_4hh) in zip(tr.layers, slots, operands):
         att_m, mlp_m = layer.attention, layer.mlp
         eps = layer.input_layernorm.eps
         npp = att_m.num_attention_heads_per_partition
         hp = npp * 64
-        qkv, x = ops.gemv_ln(z, att_m.query_key_value.weight, att_m.query_key_value.bias, layer.input_layernorm.weight,
-                             layer.input_layernorm.bias, eps, z_absmax, post, res, want_t=post is not None)
+        qkv, x = gemv_ln(z, w_qkv, att_m.query_key_value.bias, layer.input_layernorm.weight, layer.input_layernorm.bias, eps,
+                         z_absmax, post, res, want_t=post is not None)
         if x is None:
             x = z
         # (round 4) the Sandwich scale of the two branch outputs, max|ao| and max|mo|, is taken by the CONSUMING launch's LayerNorm
@@ -1067,49 +1089,18 @@ def decode_chain(tr, h0, absmax0, slots, emb_weight, w8=None):
         if hp % 512 == 0 and _decode_fuse_combine():
             # the key splits' partials are combined in the prologue of the attention-output GEMV (one launch less)
             parts = decode_attention(qkv.view(b, 1, 3 * hp), slot, npp, combine=False)
-            ao = ops.gemv_attn(parts, b, npp, _slot_capacity(slot), att_m.dense.weight, bias=att_m.dense.bias)
+            ao = gemv_attn(parts, npp, _slot_capacity(slot), w_dense, att_m.dense.bias)
         else:
             att = decode_attention(qkv.view(b, 1, 3 * hp), slot, npp)
-            ao = ops.gemm(att.view(b, hp), att_m.dense.weight, bias=att_m.dense.bias)
-        g, y = ops.gemv_ln(ao, mlp_m.dense_h_to_4h.weight, mlp_m.dense_h_to_4h.bias, layer.post_attention_layernorm.weight,
-                           layer.post_attention_layernorm.bias, eps, None,
-                           (layer.third_layernorm.weight, layer.third_layernorm.bias), x, want_t=True, gelu=True)
-        mo = ops.gemm(g, mlp_m.dense_4h_to_h.weight, bias=mlp_m.dense_4h_to_h.bias)
+            ao = gemm(att.view(b, hp), w_dense, bias=att_m.dense.bias)
+        g, y = gemv_ln(ao, w_h4h, mlp_m.dense_h_to_4h.bias, layer.post_attention_layernorm.weight,
+                       layer.post_attention_layernorm.bias, eps, None,
+                       (layer.third_layernorm.weight, layer.third_layernorm.bias), x, want_t=True, gelu=True)
+        mo = gemm(g, w_4hh, bias=mlp_m.dense_4h_to_h.bias)
         z, z_absmax, post, res = mo, None, (layer.fourth_layernorm.weight, layer.fourth_layernorm.bias), y
     fl = tr.final_layernorm
-    logits, _ = ops.gemv_ln(z, emb_weight, None, fl.weight, fl.bias, fl.eps, z_absmax, post, res)
-    return logits.view(b, 1, emb_weight.shape[0])
-
-
-def _decode_chain_w8(tr, h0, absmax0, slots, w8):
-    """decode_chain on the 8-bit weights w8 (W8Weights): launch for launch the same chain, each product reading (q, scale) in
-    place of the 16-bit matrix."""
-    b, s, h = h0.shape
-    assert s == 1
-    z, z_absmax, post, res = h0.view(b, h), absmax0, None, None
-    for layer, slot, (w_qkv, w_dense, w_h4h, w_4hh) in zip(tr.layers, slots, w8.layers):
-        att_m, mlp_m = layer.attention, layer.mlp
-        eps = layer.input_layernorm.eps
-        npp = att_m.num_attention_heads_per_partition
-        hp = npp * 64
-        qkv, x = ops.gemv_ln_w8(z, w_qkv, att_m.query_key_value.bias, layer.input_layernorm.weight, layer.input_layernorm.bias, eps,
-                                z_absmax, post, res, want_t=post is not None)
-        if x is None:
-            x = z
-        if hp % 512 == 0 and _decode_fuse_combine():
-            parts = decode_attention(qkv.view(b, 1, 3 * hp), slot, npp, combine=False)
-            ao = ops.gemv_attn_w8(parts, b, npp, _slot_capacity(slot), w_dense, w8.dtype, bias=att_m.dense.bias)
-        else:
-            att = decode_attention(qkv.view(b, 1, 3 * hp), slot, npp)
-            ao = ops.gemm_w8(att.view(b, hp), w_dense, bias=att_m.dense.bias)
-        g, y = ops.gemv_ln_w8(ao, w_h4h, mlp_m.dense_h_to_4h.bias, layer.post_attention_layernorm.weight,
-                              layer.post_attention_layernorm.bias, eps, None,
-                              (layer.third_layernorm.weight, layer.third_layernorm.bias), x, want_t=True, gelu=True)
-        mo = ops.gemm_w8(g, w_4hh, bias=mlp_m.dense_4h_to_h.bias)
-        z, z_absmax, post, res = mo, None, (layer.fourth_layernorm.weight, layer.fourth_layernorm.bias), y
-    fl = tr.final_layernorm
-    logits, _ = ops.gemv_ln_w8(z, w8.emb, None, fl.weight, fl.bias, fl.eps, z_absmax, post, res)
-    return logits.view(b, 1, w8.emb[0].shape[0])
+    logits, _ = gemv_ln(z, logits_w, None, fl.weight, fl.bias, fl.eps, z_absmax, post, res)
+    return logits.view(b, 1, logits.shape[1])
 
 
 def decode_layers_w8(tr, h0, absmax0, slots, w8):

@@ -302,26 +302,14 @@ def gemm_reserve_cus(n):
     return int(L.lib().cogv_gemm_reserve_cus(int(n)))
 
 
-def gemv_ln(z, w, bias, gamma, beta, eps, z_absmax=None, post=None, residual=None, want_t=False, gelu=False, absmax=None):
-    """Decode-step GEMV with its LayerNorms as prologue (cogv_gemv_ln): z [M, K] (M <= 8), w [N, K].
-        t = residual + SandwichLN(z; post = (gamma_p, beta_p), scale z_absmax)   (post given)   else   t = z
-        out = epilogue(SandwichLN(t; gamma, beta) . w^T + bias)
-    Returns (out [M, N], t [M, K] or None)."""
-    _need_gpu(z, w)
-    assert z.dim() == 2 and w.dim() == 2 and z.is_contiguous() and w.stride(1) == 1 and z.shape[1] == w.shape[1]
-    M, K = z.shape
-    N = w.shape[0]
-    # fp32 residual stream (see sandwich_ln_fwd): the residual of the post-LN form, or z itself in the plain-input form
-    stream32 = (residual.dtype == torch.float32) if post is not None else (z.dtype == torch.float32)
-    if post is not None:
-        assert z.dtype == w.dtype
-    out = torch.empty((M, N), dtype=w.dtype, device=z.device)
+def _skinny_desc(out, K, bias, gelu, absmax):
+    """The descriptor of a skinny-M product into out [M, N] with its epilogue flags; the operands (A, B / ldb or an 8-bit
+    weight) are the caller's."""
     d = L.GemmDesc()
-    d.dtype = dt_code(w)
-    d.M, d.N, d.K = M, N, K
-    d.A, d.lda = z.data_ptr(), K
-    d.B, d.ldb = w.data_ptr(), w.stride(0)
-    d.C, d.ldc = out.data_ptr(), N
+    d.dtype = dt_code(out)
+    d.M, d.N, d.K = out.shape[0], out.shape[1], K
+    d.A, d.lda = None, K
+    d.C, d.ldc = out.data_ptr(), out.shape[1]
     flags = 0
     if bias is not None:
         flags |= L.EPI_BIAS
@@ -332,11 +320,19 @@ def gemv_ln(z, w, bias, gamma, beta, eps, z_absmax=None, post=None, residual=Non
         flags |= L.EPI_ABSMAX
         d.absmax = absmax.data_ptr()
     d.flags, d.splitk = flags, 1
+    return d
+
+
+def _ln_prologue(z, gamma, beta, eps, z_absmax, post, residual, want_t):
+    """(cogv_ln_prologue, t [M, K] or None) of gemv_ln / gemv_ln_w8; z and (post-LN form) gamma share the product's 16-bit type."""
+    # fp32 residual stream (see sandwich_ln_fwd): the residual of the post-LN form, or z itself in the plain-input form
+    stream32 = (residual.dtype == torch.float32) if post is not None else (z.dtype == torch.float32)
     ln = L.LnPrologue()
     ln.z = z.data_ptr()
     ln.z_absmax = None if z_absmax is None else z_absmax.data_ptr()
     t = None
     if post is not None:
+        assert z.dtype == gamma.dtype
         assert residual is not None and residual.is_contiguous() and residual.shape == z.shape     # z_absmax None: taken in the kernel
         ln.gamma_post, ln.beta_post, ln.residual = post[0].data_ptr(), post[1].data_ptr(), residual.data_ptr()
         if want_t:
@@ -344,6 +340,23 @@ def gemv_ln(z, w, bias, gamma, beta, eps, z_absmax=None, post=None, residual=Non
             ln.t_out = t.data_ptr()
     ln.gamma, ln.beta, ln.eps = gamma.data_ptr(), beta.data_ptr(), float(eps)
     ln.stream_f32 = int(stream32)
+    return ln, t
+
+
+def gemv_ln(z, w, bias, gamma, beta, eps, z_absmax=None, post=None, residual=None, want_t=False, gelu=False, absmax=None):
+    """Decode-step GEMV with its LayerNorms as prologue (cogv_gemv_ln): z [M, K] (M <= 8), w [N, K].
+        t = residual + SandwichLN(z; post = (gamma_p, beta_p), scale z_absmax)   (post given)   else   t = z
+        out = epilogue(SandwichLN(t; gamma, beta) . w^T + bias)
+    Returns (out [M, N], t [M, K] or None)."""
+    _need_gpu(z, w)
+    assert z.dim() == 2 and w.dim() == 2 and z.is_contiguous() and w.stride(1) == 1 and z.shape[1] == w.shape[1]
+    assert post is None or z.dtype == w.dtype
+    M, K = z.shape
+    out = torch.empty((M, w.shape[0]), dtype=w.dtype, device=z.device)
+    d = _skinny_desc(out, K, bias, gelu, absmax)
+    d.A = z.data_ptr()
+    d.B, d.ldb = w.data_ptr(), w.stride(0)
+    ln, t = _ln_prologue(z, gamma, beta, eps, z_absmax, post, residual, want_t)
     L.check(L.lib().cogv_gemv_ln(C.byref(d), C.byref(ln), _stream()), "cogv_gemv_ln")
     return out, t
 
@@ -621,6 +634,26 @@ def _decode_first(first, b, dev):
     return first.data_ptr()
 
 
+def _decode_desc(d, qkv, pos_index, b, heads, cap, combine, first):
+    """What the two decode attentions share: (descriptor with every field but the cache's, out or None, workspace).  The
+    workspace (partial results of the key splits) is kept per (device, shape): fixed addresses, so the call is replayable
+    inside a captured graph."""
+    hp = heads * 64
+    key = (qkv.device.index, b, heads, cap)
+    ws = _DECODE_WS.get(key)
+    if ws is None:
+        ws = _DECODE_WS[key] = torch.zeros(L.lib().cogv_attention_decode_workspace_bytes(b, heads, cap), dtype=torch.uint8, device=qkv.device)
+    out = torch.empty((b, 1, hp), dtype=qkv.dtype, device=qkv.device) if combine else None
+    d.dtype, d.B, d.H, d.capacity, d.head_dim, d.scale = dt_code(qkv), b, heads, cap, 64, 0.125
+    d.qkv, d.qkv_bs = qkv.data_ptr(), qkv.stride(0)
+    d.out, d.out_bs = (out.data_ptr(), out.stride(0)) if combine else (None, hp)
+    d.pos = pos_index.data_ptr()
+    d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
+    d.skip_combine = 0 if combine else 1
+    d.first = _decode_first(first, b, qkv.device)
+    return d, out, ws
+
+
 def attention_decode(qkv, cache, pos_index, heads, combine=True, first=None):
     """combine=False: only the key-split kernel runs; returns the partials workspace for gemv_attn (the attention-output
     projection recombines the splits in its prologue: one launch less).
@@ -628,30 +661,15 @@ def attention_decode(qkv, cache, pos_index, heads, combine=True, first=None):
     cache [b, capacity, 2 * heads * 64] (keys | values), pos_index: device int64 scalar = slot of the new token (slots
     [0, pos] are attended; the new key / value are written into slot pos by the kernel).  Returns out [b, 1, heads * 64].
     first: device int32 [b] -- row r attends slots [first[r], pos] (rows with right-aligned contexts of different lengths;
-    the slots below first[r] are padding and may hold anything).  None: the launch without it.
-    The workspace (partial results of the key splits) is kept per (device, shape): fixed addresses, so the call is
-    replayable inside a captured graph."""
+    the slots below first[r] are padding and may hold anything).  None: the launch without it."""
     _need_gpu(qkv, cache, pos_index)
     b, cap = cache.shape[0], cache.shape[1]
     hp = heads * 64
     assert qkv.shape[0] == b and qkv.shape[-1] == 3 * hp and qkv.numel() == b * 3 * hp and cache.shape[2] == 2 * hp
     assert qkv.stride(-1) == 1 and cache.stride(2) == 1 and pos_index.dtype == torch.int64
-    lib = L.lib()
-    key = (qkv.device.index, b, heads, cap)
-    ws = _DECODE_WS.get(key)
-    if ws is None:
-        ws = _DECODE_WS[key] = torch.zeros(lib.cogv_attention_decode_workspace_bytes(b, heads, cap), dtype=torch.uint8, device=qkv.device)
-    out = torch.empty((b, 1, hp), dtype=qkv.dtype, device=qkv.device) if combine else None
-    d = L.AttnDecodeDesc()
-    d.dtype, d.B, d.H, d.capacity, d.head_dim, d.scale = dt_code(qkv), b, heads, cap, 64, 0.125
-    d.qkv, d.qkv_bs = qkv.data_ptr(), qkv.stride(0)
+    d, out, ws = _decode_desc(L.AttnDecodeDesc(), qkv, pos_index, b, heads, cap, combine, first)
     d.cache, d.cache_bs, d.cache_rs = cache.data_ptr(), cache.stride(0), cache.stride(1)
-    d.out, d.out_bs = (out.data_ptr(), out.stride(0)) if combine else (None, hp)
-    d.pos = pos_index.data_ptr()
-    d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
-    d.skip_combine = 0 if combine else 1
-    d.first = _decode_first(first, b, qkv.device)
-    L.check(lib.cogv_attention_decode(C.byref(d), _stream()), "cogv_attention_decode")
+    L.check(L.lib().cogv_attention_decode(C.byref(d), _stream()), "cogv_attention_decode")
     return out if combine else ws
 
 
@@ -685,23 +703,10 @@ def attention_decode_kv8(qkv, cache8, pos_index, heads, combine=True, first=None
     assert q.dtype == torch.uint8 and q.shape == (b, 2, heads, cap, 64) and q[0].is_contiguous()
     assert scale.dtype == torch.float32 and scale.shape == (b, 2, heads, cap) and scale[0].is_contiguous()
     assert pos_index.dtype == torch.int64
-    lib = L.lib()
-    key = (qkv.device.index, b, heads, cap)
-    ws = _DECODE_WS.get(key)
-    if ws is None:
-        ws = _DECODE_WS[key] = torch.zeros(lib.cogv_attention_decode_workspace_bytes(b, heads, cap), dtype=torch.uint8, device=qkv.device)
-    out = torch.empty((b, 1, hp), dtype=qkv.dtype, device=qkv.device) if combine else None
-    d = L.AttnDecodeKv8Desc()
-    d.dtype, d.B, d.H, d.capacity, d.head_dim, d.scale = dt_code(qkv), b, heads, cap, 64, 0.125
-    d.qkv, d.qkv_bs = qkv.data_ptr(), qkv.stride(0)
+    d, out, ws = _decode_desc(L.AttnDecodeKv8Desc(), qkv, pos_index, b, heads, cap, combine, first)
     d.kv_q, d.kv_q_bs = q.data_ptr(), q.stride(0)
     d.kv_scale, d.kv_scale_bs = scale.data_ptr(), scale.stride(0)
-    d.out, d.out_bs = (out.data_ptr(), out.stride(0)) if combine else (None, hp)
-    d.pos = pos_index.data_ptr()
-    d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
-    d.skip_combine = 0 if combine else 1
-    d.first = _decode_first(first, b, qkv.device)
-    L.check(lib.cogv_attention_decode_kv8(C.byref(d), _stream()), "cogv_attention_decode_kv8")
+    L.check(L.lib().cogv_attention_decode_kv8(C.byref(d), _stream()), "cogv_attention_decode_kv8")
     return out if combine else ws
 
 
@@ -713,20 +718,8 @@ def gemv_attn(partials, batch, heads, capacity, w, bias=None, absmax=None):
     N, K = w.shape
     assert K == heads * 64 and w.stride(1) == 1 and batch <= 8
     out = torch.empty((batch, N), dtype=w.dtype, device=w.device)
-    d = L.GemmDesc()
-    d.dtype = dt_code(w)
-    d.M, d.N, d.K = batch, N, K
-    d.A, d.lda = None, K
+    d = _skinny_desc(out, K, bias, False, absmax)
     d.B, d.ldb = w.data_ptr(), w.stride(0)
-    d.C, d.ldc = out.data_ptr(), N
-    flags = 0
-    if bias is not None:
-        flags |= L.EPI_BIAS
-        d.bias = bias.data_ptr()
-    if absmax is not None:
-        flags |= L.EPI_ABSMAX
-        d.absmax = absmax.data_ptr()
-    d.flags, d.splitk = flags, 1
     L.check(L.lib().cogv_gemv_attn(C.byref(d), _p(partials), int(heads), int(capacity), _stream()), "cogv_gemv_attn")
     return out
 
@@ -753,23 +746,9 @@ def _w8_call(x_dtype, M, K, qs, bias, gelu, absmax):
     assert q.dim() == 2 and q.dtype == torch.uint8 and q.stride(1) == 1 and q.shape[1] == K, "q [N, K] uint8 with K matching the input"
     assert scale.dtype == torch.float32 and scale.is_contiguous() and scale.numel() == q.shape[0]
     N = q.shape[0]
+    assert bias is None or bias.dtype == x_dtype
     out = torch.empty((M, N), dtype=x_dtype, device=q.device)
-    d = L.GemmDesc()
-    d.dtype = dt_code(x_dtype)
-    d.M, d.N, d.K = M, N, K
-    d.A, d.lda = None, K
-    d.C, d.ldc = out.data_ptr(), N
-    flags = 0
-    if bias is not None:
-        assert bias.dtype == x_dtype
-        flags |= L.EPI_BIAS
-        d.bias = bias.data_ptr()
-    if gelu:
-        flags |= L.EPI_GELU
-    if absmax is not None:
-        flags |= L.EPI_ABSMAX
-        d.absmax = absmax.data_ptr()
-    d.flags, d.splitk = flags, 1
+    d = _skinny_desc(out, K, bias, gelu, absmax)
     w = L.W8Weight()
     w.q, w.ldq, w.scale = q.data_ptr(), q.stride(0), scale.data_ptr()
     return d, w, out
@@ -793,22 +772,8 @@ def gemv_ln_w8(z, qs, bias, gamma, beta, eps, z_absmax=None, post=None, residual
     _need_gpu(z, gamma)
     assert z.dim() == 2 and z.is_contiguous()
     M, K = z.shape
-    stream32 = (residual.dtype == torch.float32) if post is not None else (z.dtype == torch.float32)
-    if post is not None:
-        assert z.dtype == gamma.dtype
     d, w, out = _w8_call(gamma.dtype, M, K, qs, bias, gelu, absmax)
-    ln = L.LnPrologue()
-    ln.z = z.data_ptr()
-    ln.z_absmax = None if z_absmax is None else z_absmax.data_ptr()
-    t = None
-    if post is not None:
-        assert residual is not None and residual.is_contiguous() and residual.shape == z.shape
-        ln.gamma_post, ln.beta_post, ln.residual = post[0].data_ptr(), post[1].data_ptr(), residual.data_ptr()
-        if want_t:
-            t = torch.empty_like(residual)
-            ln.t_out = t.data_ptr()
-    ln.gamma, ln.beta, ln.eps = gamma.data_ptr(), beta.data_ptr(), float(eps)
-    ln.stream_f32 = int(stream32)
+    ln, t = _ln_prologue(z, gamma, beta, eps, z_absmax, post, residual, want_t)
     L.check(L.lib().cogv_gemv_ln_w8(C.byref(d), C.byref(ln), C.byref(w), _stream()), "cogv_gemv_ln_w8")
     return out, t
 

@@ -161,6 +161,20 @@ int cogv_gemv_ln_w8(const cogv_gemm_desc* d, const cogv_ln_prologue* ln, const c
 /* cogv_gemv_attn (the attention-output projection mpu/sparse_transformer.py:163-166 with the split combine as prologue) on
  * an 8-bit weight; bit-identical to the combine launch followed by cogv_gemm_w8. */
 int cogv_gemv_attn_w8(const cogv_gemm_desc* d, const cogv_w8_weight* w, const void* partials, int heads, int capacity, void* stream);
+/* Host-only query (no device is touched, no pointer of d or w is dereferenced): what the skinny-M product of `kind` would launch
+ * for this descriptor -- cogv_gemm's M <= 8 case, cogv_gemv_attn, cogv_gemv_ln, or with w != NULL cogv_gemm_w8, cogv_gemv_attn_w8,
+ * cogv_gemv_ln_w8 -- from the function those launches use, and their errors for the descriptor (1 bad argument, 3 not taken; out
+ * is left untouched then).  nsplit: the key splits the attention kind combines ((capacity + 127) / 128; ignored otherwise).
+ * out = { generation (2: a kernel of the class list in csrc/gemv_plan.h; 1: the first-generation kernel behind the 16-bit
+ * products, also under COGV_GEMV2=0 -- the fields up to `two halves` are 0 then, rows excepted), form (0 V: one row, 1 M: 2 .. 8
+ * rows on the matrix core), columns per wave J (V) | waves per 16-column tile NWK (M), 512-chunks of K KCMAX (V) | loads per lane
+ * LMAX (M), guarded (1: a class for every K up to its maximum), rows MT (M rounded up to 1, 2, 4, 8), 16-column tiles per workgroup,
+ * two halves (1: the x rows are staged in two halves of K), threads per workgroup, workgroups, dynamic LDS bytes }. */
+#define COGV_GEMV_PLAIN 0
+#define COGV_GEMV_ATTN 1
+#define COGV_GEMV_LN 2
+#define COGV_GEMV_PLAN_INTS 11
+int cogv_gemv_plan(int kind, const cogv_gemm_desc* d, const cogv_w8_weight* w, int nsplit, int out[COGV_GEMV_PLAN_INTS]);
 
 /* ------------------------------------------------------------------ Sandwich-LN
  * y = [residual +] LayerNorm_{eps*(amax/8)^2}(x) * gamma + beta ; amax = *absmax_in (NULL: plain LN).
