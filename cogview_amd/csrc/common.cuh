@@ -172,6 +172,34 @@ __device__ __forceinline__ float absmax_pk_block(uint32_t m, uint32_t* smem) {
   return bits_to_f<T>((uint16_t)r);
 }
 
+// Mean and 1 / sqrt(variance + eps) of ONE row of h (a multiple of 512) elements of T, taken by one whole wave in exactly
+// ln_fwd_kernel's arithmetic (layernorm.hip): lane l adds the elements of its vectors (64 v + l) * 8, v ascending, in one
+// chain, then one DPP wave sum; the squared deviations likewise.  The decode step's LayerNorm prologues (gemv.hip,
+// gemv_gen1.cuh) take the statistics of the post-LayerNorm with it from the rows they hold in LDS, so that the residual
+// stream they write is the Sandwich-LN kernel's to the bit.  `row`: 16-byte aligned (LDS or global).
+template <typename T>
+__device__ __forceinline__ void ln_row_stats_wave(const T* row, int h, float inv_h, float eps, int lane, float& mean, float& rstd) {
+  // the roundings are spelled out, not left to contraction: as ln_fwd_kernel is compiled, a squared deviation is rounded before
+  // it is added (packed multiplies), and variance * 1/h + eps is one fused multiply-add
+#pragma clang fp contract(off)
+  float s = 0.f;
+  for (int col = lane * 8; col < h; col += 512) {
+    float x[8];
+    unpack8<T>(*reinterpret_cast<const u32x4*>(row + col), x);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) s += x[i];
+  }
+  mean = wave_sum_uniform(s) * inv_h;
+  float q = 0.f;
+  for (int col = lane * 8; col < h; col += 512) {
+    float x[8];
+    unpack8<T>(*reinterpret_cast<const u32x4*>(row + col), x);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { const float d = x[i] - mean; q += d * d; }
+  }
+  rstd = 1.0f / sqrtf(__builtin_fmaf(wave_sum_uniform(q), inv_h, eps));
+}
+
 // ---------------------------------------------------------------- the fp32 residual stream
 // Round 3: the residual stream of the transformer (embedding output, y = x + LN3(.), out = y + LN4(.), and its
 // gradient) is held in fp32; everything that feeds a GEMM stays in the 16-bit storage type.  Rounding the stream to

@@ -596,6 +596,7 @@ void gemv2_ln_kernel(const GemvLnArgs q) {
   constexpr int NW = F::NW;
   extern __shared__ __attribute__((aligned(16))) char gv2_smem[];           // x_in [MT][K + pad] as T
   __shared__ float part[NW][MT][2];
+  __shared__ float pstat[MT][2];            // post-LayerNorm: mean, rstd per row
   __shared__ typename F::Shared sh;
   __shared__ uint32_t redm[16];
   __shared__ float s_amax;
@@ -693,39 +694,32 @@ void gemv2_ln_kernel(const GemvLnArgs q) {
     }
     const float c = zamax * 0.125f;
     const float eps_p = q.eps * c * c;
-    float s[MT], qq[MT];
+    // mean and rstd per row as ln_fwd_kernel takes them (one wave per row, common.cuh: ln_row_stats_wave) from the z rows in
+    // LDS -- x_in's place, which is written much later: t is the Sandwich-LN kernel's to the bit whatever the form's wave count
 #pragma unroll
-    for (int m = 0; m < MT; ++m) {
-      s[m] = 0.f;
-#pragma unroll
-      for (int u = 0; u < NV; ++u)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) s[m] += tv[m][u][i];            // vectors past K are zero
-    }
-    block_sums(s);
-#pragma unroll
-    for (int m = 0; m < MT; ++m) {
-      const float mean = s[m] * inv_k;
-      qq[m] = 0.f;
+    for (int m = 0; m < MT; ++m)
 #pragma unroll
       for (int u = 0; u < NV; ++u)
-        if (okv[u])
-#pragma unroll
-          for (int i = 0; i < 8; ++i) { const float d = tv[m][u][i] - mean; qq[m] += d * d; }
+        if (okv[u]) *reinterpret_cast<u32x4*>(xs + (size_t)m * XS + vv[u] * 8) = zr[m][u];
+    __syncthreads();
+    for (int m = wave; m < MT; m += NW) {
+      float mean = 0.f, rstd = 0.f;                                  // rows >= M: zeros nobody reads
+      if (m < p.M) ln_row_stats_wave<T>(xs + (size_t)m * XS, K, inv_k, eps_p, lane, mean, rstd);
+      if (lane == 0) { pstat[m][0] = mean; pstat[m][1] = rstd; }
     }
-    block_sums(qq);
+    __syncthreads();
     float gp[NV][8], bp[NV][8];
 #pragma unroll
     for (int u = 0; u < NV; ++u) { unpack8<T>(gpr[u], gp[u]); unpack8<T>(bpr[u], bp[u]); }
 #pragma unroll
     for (int m = 0; m < MT; ++m) {
-      const float mean = s[m] * inv_k, rstd = 1.0f / sqrtf(qq[m] * inv_k + eps_p);
+      const float mean = pstat[m][0], rstd = pstat[m][1];
 #pragma unroll
       for (int u = 0; u < NV; ++u) {
         float r[8], o[8];
         SR::to_f(rr[m][u], r);
 #pragma unroll
-        for (int i = 0; i < 8; ++i) o[i] = (tv[m][u][i] - mean) * rstd * gp[u][i] + bp[u][i];
+        for (int i = 0; i < 8; ++i) o[i] = fmaf((tv[m][u][i] - mean) * rstd, gp[u][i], bp[u][i]);   // ln_fwd_kernel's: one fused multiply-add
         if (!SF) { u32x4 lo = pack8<T>(o); unpack8<T>(lo, o); }   // all-T form: LayerNorm output rounded before the residual add
 #pragma unroll
         for (int i = 0; i < 8; ++i) o[i] += r[i];

@@ -150,6 +150,32 @@ def test_plan_grid(kind, w8):
     assert n == (7 if kind == "ln" else 10) * 6 * 2 * 2
 
 
+@pytest.mark.parametrize("kind,w8", list(PLANS))
+def test_the_gpu_sweep_grid_reaches_every_plan(kind, w8):
+    """tests/gemv_cells.py (the grid tests/test_gemv_cells_gpu.py launches): every distinct entry of PLANS -- the first generation's
+    included -- is the plan of some (M, K) of that grid, in both dtypes.  An entry is (generation, form, J | NWK, KCMAX | LMAX,
+    guarded, tiles, two halves, MT); the grid columns do not identify it.  No exemptions: a new entry wants a new grid point."""
+    from tests import gemv_cells as GC
+
+    def ident(entry, mt):
+        form, p0, p1, guard, tw, k2 = entry[:6]
+        return (1, 0, 0, 0, 0, 0, 0, mt) if form is None else (2, form, p0, p1, guard, tw, k2, mt)
+
+    want = {ident(e, mt) for row in PLANS[(kind, w8)].values() for e, mt in zip(row, (1, 2, 4, 8)) if e is not None}
+    assert len(want) >= 8
+    for dtype in (F16, BF16):
+        reached = set()
+        for K in GC.ks(kind):
+            for M_ in GC.MS:
+                rc, out = query(kind, w8, M_, 136, K, dtype)
+                if rc == OK:
+                    assert out[5] == MT[M_]
+                    reached.add(GC.plan_id(out))
+        assert not want - reached, (kind, w8, dtype, sorted(want - reached))
+    # ... and the two K of the first generation's LayerNorm kernel that take their LDS by attribute are both grid points
+    assert {3584, 4096} <= set(GC.ks("ln")) and 8 in GC.MS
+
+
 @pytest.mark.parametrize("kind,w8,M_,K,want", [
     ("plain", W16, 1, 2560, (OK, [2, V, 4, 5, 0, 1, 1, 0, 256, 9, 5120])),
     ("plain", W8, 1, 1024, (OK, [2, V, 16, 2, 0, 1, 1, 0, 256, 3, 2048])),
