@@ -176,6 +176,7 @@ SIGNATURES = {
     "cogv_ln_bwd_plan": (_i, [_i, _i, _i, _f, _i, _i, C.POINTER(C.c_int)]),
     "cogv_ln_bwd_pair_plan": (_i, [_i, _i, _f, C.POINTER(C.c_int)]),
     "cogv_gemm_reserve_cus": (_i, [_i]),
+    "cogv_gemm_plan": (_i, [C.POINTER(GemmDesc), _i, _i, C.POINTER(C.c_int)]),
     "cogv_attention_fwd": (_i, [C.POINTER(AttnDesc), _vp]),
     "cogv_attention_bwd": (_i, [C.POINTER(AttnDesc), _vp]),
     "cogv_attention_plan": (_i, [C.POINTER(AttnDesc), _i, C.POINTER(C.c_int)]),
@@ -249,6 +250,18 @@ def check(rc, what):
 OK, ERR_ARG, ERR_UNSUPPORTED = 0, 1, 3
 GEMV_PLAIN, GEMV_ATTN, GEMV_LN = 0, 1, 2
 GEMV_PLAN_INTS = 11
+GEMM_PLAN_INTS = 17
+GEMM_PLAN_FIELDS = ("family", "generation", "tile_m", "tile_n", "tiles_m", "tiles_n", "splitk", "ktiles_per_split", "item_start", "items",
+                    "grid_x", "grid_y", "threads", "lds", "reduce_blocks", "xp_ok", "layout")
+
+
+def gemm_plan(descs, count=0, num_cus=0):
+    """cogv_gemm_plan: (error code, one dict of GEMM_PLAN_FIELDS per problem) of what cogv_gemm (count 0: `descs` is one GemmDesc)
+    or cogv_gemm_grouped (count >= 1: an array of them) would launch; host only, no pointer in a descriptor is read."""
+    n = max(count, 1)
+    out = (C.c_int * (GEMM_PLAN_INTS * n))()
+    rc = lib().cogv_gemm_plan(descs if count else C.byref(descs), count, num_cus, out)
+    return rc, [dict(zip(GEMM_PLAN_FIELDS, out[i * GEMM_PLAN_INTS:(i + 1) * GEMM_PLAN_INTS])) for i in range(n if rc == OK else 0)]
 
 
 def gemv_plan(kind, dtype, M, N, K, w8=False, nsplit=1, ldb=None):

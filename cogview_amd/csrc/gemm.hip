@@ -11,29 +11,36 @@
 // "trans" means the operand is stored with the contraction index as the SLOW dimension (A stored [K][M], B stored
 // [K][N]): dgrad's W and both weight-gradient operands.  No transposed copies exist in HBM.
 //
-// This file: the host side (dispatch, grouped launch, split-K reduce, C entry points).  The kernels live in the headers
+// This file: the host side (argument checks, launches, split-K reduce, C entry points).  The kernels live in the headers
 // included below, one per generation -- gemm_gen4.cuh is the one the train step runs; gemm_gen1 / 2 / 3.cuh are the fallbacks
 // for shapes it does not take; gemm_lds.cuh holds the LDS images and fragment reads generations 2-4 share; gemv_gen1.cuh the
 // first-generation skinny-M kernels (csrc/gemv.hip has the second).
-// Four tile kernels, newest first, plus gemv_kernel for M <= 8 (decode steps: a pure HBM stream of the weights);
-// dispatch: launch_gemm:
+// Dispatch: cogv_gemm checks the descriptor (build_gemm_args), gives M <= 8 (decode steps: a pure HBM stream of the weights)
+// to the skinny-M kernels where gemv_plan.h takes the product, and launches every other product from ONE plan -- gemm_plan.h:
+// kernel_variant and shape -> generation, tiles, grid, threads, dynamic LDS, reduce blocks, or the refusal; cogv_gemm_grouped
+// plans its problems with the same functions and cogv_gemm_plan reports them (tests/test_gemm_plan.py).  launch_tiles turns a
+// plan into one launch by (generation, dtype, layout) and one reduce pass per problem that splits K.
+// The four tile kernels, newest first (kernel_variant 10, 9, 3, 1):
 //   generation 4  gemm_w4_kernel     256x256x64 tiles, 4 waves of 128x128 (accumulators fill the AGPR file), software-
 //                                    pipelined quarter-steps, LDS-DMA granule ring, persistent with per-XCD work queues,
-//                                    up to 16 problems per launch.  Default for M, N >= 256.  Its 2 x 4 instantiations
-//                                    compile as separate translation units (-DCOGV_W4_TU=k, build.py).
+//                                    up to 16 problems per launch.  Auto for M, N >= 256, K % 64 == 0, operands < 4 GiB,
+//                                    unless generation 2 fills its rounds 1.1x better.  Its 2 x 4 instantiations compile as
+//                                    separate translation units (-DCOGV_W4_TU=k, build.py).
 //   generation 3  gemm_pp64_kernel   the same tile, ring and queues with 8 waves of 128x64 in a ping-pong schedule
-//                                    (kernel_variant 9; 5-15 % slower than generation 4: 1.5x the LDS fragment bytes).
-//   generation 2  gemm_glds_kernel   256x128x32 tiles, 4 waves, 3-stage LDS-DMA ring, 2 workgroups per CU.
-//                                    For M or N < 256 and operands >= 4 GiB.
-//   generation 1  gemm_kernel        128x128x64 tiles, register-staged with register transposes.  For K % 64 != 0 and
-//                                    other unaligned shapes.
+//                                    (on request only; 5-15 % slower than generation 4: 1.5x the LDS fragment bytes).
+//   generation 2  gemm_glds_kernel   256x128x32 tiles, 4 waves of 128x64, 3-stage LDS-DMA ring, 2 workgroups per CU.
+//                                    For M or N in [64, 256) and operands >= 4 GiB.
+//   generation 1  gemm_kernel        128x128x64 tiles, register-staged with register transposes.  For K % 64 != 0, M or
+//                                    N < 64.
 // All share the fused epilogue (epilogue8): bias, GeLU (+ stored pre-activation), dGeLU, dropout, += C, abs-max for
 // Sandwich-LN, and (generations 3, 4) the bias-gradient column sums of the output.
 #include "common.cuh"
 #include "cogview_hip.h"
 #include "gemm_shared.cuh"
 
+#include <cstddef>
 #include <cstdlib>
+#include <cstring>
 #include <type_traits>
 
 #ifndef COGV_EXP
@@ -48,6 +55,7 @@
 #include "gemm_gen4.cuh"
 #include "gemv_gen1.cuh"
 #include "gemv_plan.h"
+#include "gemm_plan.h"
 
 namespace {
 
@@ -73,28 +81,6 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const GemmArgs p) {
     const float bm = absmax_pk_block<T>(amax_pk, reinterpret_cast<uint32_t*>(red));
     if (threadIdx.x == 0) atomic_max_nonneg(p.absmax, bm);
   }
-}
-
-template <typename T, bool AT, bool BT, int WM, int WN, int MI, int NJ, int BKT>
-void launch_glds(GemmArgs& a, hipStream_t st) {
-  constexpr int TBM = WM * 32 * MI, TBN = WN * 32 * NJ;
-  constexpr int shmem = 3 * (TBM + TBN) * 2 * BKT;
-  a.tiles_m = (a.M + TBM - 1) / TBM; a.tiles_n = (a.N + TBN - 1) / TBN;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_glds_kernel<T, AT, BT, WM, WN, MI, NJ, BKT>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, shmem);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((gemm_glds_kernel<T, AT, BT, WM, WN, MI, NJ, BKT>), dim3(a.tiles_m * a.tiles_n, a.splitk),
-                     dim3(WM * WN * 64), shmem, st, a);
-}
-template <typename T, int WM, int WN, int MI, int NJ, int BKT>
-void launch_glds_layout(const cogv_gemm_desc* d, GemmArgs& a, hipStream_t st) {
-  if (!d->trans_a && !d->trans_b) launch_glds<T, false, false, WM, WN, MI, NJ, BKT>(a, st);
-  else if (!d->trans_a && d->trans_b) launch_glds<T, false, true, WM, WN, MI, NJ, BKT>(a, st);
-  else if (d->trans_a && d->trans_b) launch_glds<T, true, true, WM, WN, MI, NJ, BKT>(a, st);
-  else launch_glds<T, true, false, WM, WN, MI, NJ, BKT>(a, st);
 }
 
 int num_cus() {
@@ -125,105 +111,72 @@ int* sched_slot() {
   return pool[dev] + 16 * (turn[dev]++ % SLOTS);
 }
 
+// one planned launch of KERNEL (its dynamic LDS raised on first use)
+template <auto KERNEL, typename Args>
+int launch_planned(const GemmPlan& pl, const Args& args, hipStream_t st) {
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds);
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(KERNEL, dim3(pl.grid_x, pl.grid_y), dim3(pl.threads), pl.lds, st, args);
+  return COGV_OK;
+}
+
 #ifndef COGV_W4_TU
 // CUs the persistent kernels leave free (cogv_gemm_reserve_cus): a collective that runs CONCURRENTLY with a GEMM needs somewhere
 // to live -- a generation-3 / 4 workgroup owns its CU's whole register file, so a persistent launch over all CUs keeps RCCL's
 // channel workgroups waiting until it ends.
 int g_reserved_cus = 0;
-int persistent_grid(int items) {
-  int n = num_cus() - g_reserved_cus;
-  if (n < 8) n = 8;
-  return items < n ? items : n;
+
+// what the launch plan takes from the device and the environment; cus > 0: plan for that many CUs (cogv_gemm_plan)
+GemmEnv gemm_env(int cus = 0) {
+  // raster group height (experiments: COGV_GEMM_GROUP_M); 4 rows x 8 columns of tiles per XCD by default
+  static const int gm = [] { const char* e = getenv("COGV_GEMM_GROUP_M"); const int v = e ? atoi(e) : 4; return v >= 1 && v <= 32 ? v : 4; }();
+  const char* xp = getenv("COGV_GEMM_XP");                // read per launch: tests and A/B runs switch it inside one process
+  return GemmEnv{cus > 0 ? cus : num_cus(), g_reserved_cus, gm, !xp || atoi(xp) != 0};
 }
 
 // The generation-4 kernel's eight instantiations (2 dtypes x 4 layouts) are compiled from this same file in eight
-// separate translation units (-DCOGV_W4_TU=k, see build.py: they build in parallel); unit k exports cogv_w4_launch_k.
-#define W4_DECL(k) extern "C" __attribute__((visibility("hidden"))) int cogv_w4_launch_##k(const void* ga, int grid, void* stream);
+// separate translation units (-DCOGV_W4_TU=k, see build.py: they build in parallel); unit k = 4 * fp16 + layout index
+// (gemm_layout) exports cogv_w4_launch_k.
+#define W4_DECL(k) extern "C" __attribute__((visibility("hidden"))) int cogv_w4_launch_##k(const GemmPlan* pl, const void* ga, void* stream);
 W4_DECL(0) W4_DECL(1) W4_DECL(2) W4_DECL(3) W4_DECL(4) W4_DECL(5) W4_DECL(6) W4_DECL(7)
 #undef W4_DECL
-typedef int (*w4_launch_fn)(const void*, int, void*);
-const w4_launch_fn W4_LAUNCH[8] = {cogv_w4_launch_0, cogv_w4_launch_1, cogv_w4_launch_2, cogv_w4_launch_3,
-                                   cogv_w4_launch_4, cogv_w4_launch_5, cogv_w4_launch_6, cogv_w4_launch_7};
-// unit index: bit 2 = fp16 (else bf16), bits 1..0 = layout: 0 NT (forward), 1 NN (dgrad: B stored [K, N]),
-// 2 TN (wgrad: both stored contraction-major), 3 A stored [K, M] only
-template <typename T, bool AT, bool BT> constexpr int w4_unit() {
-  return (std::is_same<T, f16_t>::value ? 4 : 0) + (AT ? (BT ? 2 : 3) : (BT ? 1 : 0));
-}
+const decltype(&cogv_w4_launch_0) W4_LAUNCH[8] = {cogv_w4_launch_0, cogv_w4_launch_1, cogv_w4_launch_2, cogv_w4_launch_3,
+                                                  cogv_w4_launch_4, cogv_w4_launch_5, cogv_w4_launch_6, cogv_w4_launch_7};
 
-template <typename T, bool AT, bool BT, int GEN = 3>
-int launch_pp64(GroupArgs& ga, hipStream_t st) {
-  constexpr int shmem = 2 * 65536;
-  ga.sched = sched_slot();
-  if (!ga.sched) return COGV_ERR_LAUNCH;
-  {   // raster group height (experiments: COGV_GEMM_GROUP_M); 4 rows x 8 columns of tiles per XCD by default
-    static const int gm = [] { const char* e = getenv("COGV_GEMM_GROUP_M"); const int v = e ? atoi(e) : 4; return v >= 1 && v <= 32 ? v : 4; }();
-    ga.group_m = gm;
-  }
-  ga.item_start[0] = 0;
-  for (int i = 0; i < ga.count; ++i) {
-    GemmArgs& a = ga.g[i];
-    a.tiles_m = (a.M + 255) / 256; a.tiles_n = (a.N + 255) / 256;
-    ga.item_start[i + 1] = ga.item_start[i] + a.tiles_m * a.tiles_n * a.splitk;
-  }
-  for (int i = ga.count; i < MAX_GROUP; ++i) ga.item_start[i + 1] = ga.item_start[ga.count];
-  const int num_cu = num_cus();
-  const int items = ga.item_start[ga.count];
-  if constexpr (GEN == 4) {
-    ga.xp_ok = 0; ga.xp_magic_ig = ga.xp_magic_gfull = ga.xp_magic_gtail = 0u;
-    const char* xp_env = getenv("COGV_GEMM_XP");          // read per launch: tests and A/B runs switch it inside one process
-    const bool xp_enabled = !xp_env || atoi(xp_env) != 0;
-    const GemmArgs& a0 = ga.g[0];
-    const int nkt = a0.K / 64;
-    if (xp_enabled && ga.count == 1 && a0.splitk == 1 && nkt >= 4 && (nkt & 1) == 0 && items > num_cu) {
-      // multiplicative forms of the three divisions of the tile order, verified against the dividing form for EVERY item of
-      // this geometry (cached: a training step launches a handful of distinct geometries)
-      struct Geo { int tm, tn, gm, ok; uint32_t mig, mgf, mgt; };
-      static Geo cache[32];
-      static int ncache = 0;
-      const Geo* hit = nullptr;
-      for (int i = 0; i < ncache; ++i)
-        if (cache[i].tm == a0.tiles_m && cache[i].tn == a0.tiles_n && cache[i].gm == ga.group_m) { hit = &cache[i]; break; }
-      Geo g;
-      if (!hit) {
-        g.tm = a0.tiles_m; g.tn = a0.tiles_n; g.gm = ga.group_m;
-        const uint32_t tail = (uint32_t)(a0.tiles_m % ga.group_m);
-        g.mig = w4_magic((uint32_t)(ga.group_m * a0.tiles_n)); g.mgf = w4_magic((uint32_t)ga.group_m); g.mgt = w4_magic(tail);
-        g.ok = 1;
-        for (uint32_t b = 0; b < (uint32_t)items && g.ok; ++b) {
-          uint32_t m1, n1, m2, n2;
-          w4_tile_slow(b, (uint32_t)g.tm, (uint32_t)g.tn, (uint32_t)g.gm, m1, n1);
-          w4_tile_fast(b, (uint32_t)g.tm, (uint32_t)g.tn, (uint32_t)g.gm, g.mig, g.mgf, g.mgt, m2, n2);
-          if (m1 != m2 || n1 != n2) g.ok = 0;
-        }
-        if (ncache < 32) cache[ncache++] = g;
-        hit = &g;
-      }
-      ga.xp_ok = hit->ok; ga.xp_magic_ig = hit->mig; ga.xp_magic_gfull = hit->mgf; ga.xp_magic_gtail = hit->mgt;
-    }
-    return W4_LAUNCH[w4_unit<T, AT, BT>()](&ga, persistent_grid(items), st);
-  } else {
-    static bool attr_set = false;
-    if (!attr_set) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_pp64_kernel<T, AT, BT>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, shmem);
-      attr_set = true;
-    }
-    hipLaunchKernelGGL((gemm_pp64_kernel<T, AT, BT>), dim3(persistent_grid(items)), dim3(512), shmem, st, ga);
-    return COGV_OK;
+// the plan's generation in dtype T and layout index L: TILE_LAUNCH[fp16][L]
+template <typename T, int L>
+int launch_generation(const GemmPlan& pl, const GroupArgs& ga, hipStream_t st) {
+  constexpr bool AT = L >= 2, BT = L == 1 || L == 2;
+  static_assert(gemm_layout(AT, BT) == L, "gemm_plan.h");
+  switch (pl.generation) {
+    case 1: return launch_planned<&gemm_kernel<T, AT, BT>>(pl, ga.g[0], st);
+    case 2: return launch_planned<&gemm_glds_kernel<T, AT, BT, 2, 2, 4, 2, 32>>(pl, ga.g[0], st);      // 4 waves of 128x64
+    case 3: return launch_planned<&gemm_pp64_kernel<T, AT, BT>>(pl, ga, st);
+    default: return W4_LAUNCH[(std::is_same<T, f16_t>::value ? 4 : 0) + L](&pl, &ga, st);
   }
 }
-template <typename T, int GEN = 3>
-int launch_pp64_layout(int trans_a, int trans_b, GroupArgs& ga, hipStream_t st) {
-  if (!trans_a && !trans_b) return launch_pp64<T, false, false, GEN>(ga, st);
-  if (!trans_a && trans_b) return launch_pp64<T, false, true, GEN>(ga, st);
-  if (trans_a && trans_b) return launch_pp64<T, true, true, GEN>(ga, st);
-  return launch_pp64<T, true, false, GEN>(ga, st);
-}
-template <typename T>
-void launch_splitk_reduce(GemmArgs& a, hipStream_t st) {
-  const size_t nvec = (size_t)a.M * (a.N / 8);
-  int blocks = (int)((nvec + 255) / 256); if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL((splitk_reduce_kernel<T>), dim3(blocks), dim3(256), 0, st, a);
+typedef int (*tile_launch_fn)(const GemmPlan&, const GroupArgs&, hipStream_t);
+#define LAYOUTS(T) {launch_generation<T, 0>, launch_generation<T, 1>, launch_generation<T, 2>, launch_generation<T, 3>}
+const tile_launch_fn TILE_LAUNCH[2][4] = {LAYOUTS(bf16_t), LAYOUTS(f16_t)};
+#undef LAYOUTS
+
+// The launch of pl[0 .. count): the plan goes into the argument block(s) build_gemm_args filled, one kernel launch by (generation,
+// dtype, layout), and one reduce pass per problem that splits K.
+int launch_tiles(int dtype, const GemmPlan* pl, int count, const GemmEnv& env, GroupArgs& ga, hipStream_t st) {
+  ga.count = count; ga.group_m = env.group_m;
+  ga.xp_ok = pl[0].xp_ok; ga.xp_magic_ig = pl[0].xp_magic_ig; ga.xp_magic_gfull = pl[0].xp_magic_gfull; ga.xp_magic_gtail = pl[0].xp_magic_gtail;
+  for (int i = 0; i < count; ++i) { ga.g[i].tiles_m = pl[i].tiles_m; ga.g[i].tiles_n = pl[i].tiles_n; ga.item_start[i] = pl[i].item_start; }
+  for (int i = count; i <= MAX_GROUP; ++i) ga.item_start[i] = pl[0].items;
+  if (pl[0].generation >= 3 && !(ga.sched = sched_slot())) return COGV_ERR_LAUNCH;
+  const int rc = TILE_LAUNCH[dtype == COGV_F16][pl[0].layout](pl[0], ga, st);
+  if (rc != COGV_OK) return rc;
+  const auto reduce = dtype == COGV_F16 ? splitk_reduce_kernel<f16_t> : splitk_reduce_kernel<bf16_t>;
+  for (int i = 0; i < count; ++i)
+    if (pl[i].reduce_blocks) hipLaunchKernelGGL(reduce, dim3(pl[i].reduce_blocks), dim3(256), 0, st, ga.g[i]);
+  return cogv_check_launch();
 }
 
 // Skinny-M products (M <= 8: the decode step).  gv_plan (gemv_plan.h) decides every launch: a second-generation kernel of
@@ -281,83 +234,6 @@ bool gemv16_refuses(int kind, const cogv_gemm_desc* d) {
   if (kind == GV_PLAIN) return (d->flags & COGV_EPI_COLSUM) || d->kernel_variant != 0;      // takes every other fused epilogue
   const int refused = COGV_EPI_COLSUM | COGV_EPI_ACCUM | COGV_EPI_DGELU | COGV_EPI_MULAUX | COGV_EPI_DROPOUT | (kind == GV_ATTN ? COGV_EPI_GELU : 0);
   return (d->flags & refused) || d->out_f32 || d->splitk > 1;
-}
-
-template <typename T>
-int launch_gemm(const cogv_gemm_desc* d, GemmArgs& a, hipStream_t st) {
-  // skinny M (decode steps): the HBM-streaming matrix-vector kernels
-  GvPlan pl;
-  if (!gemv16_refuses(GV_PLAIN, d) && gv_plan(GV_PLAIN, GV_W16, a.M, a.N, a.K, a.ldb, 0, pl)) {
-    a.splitk = 1;
-    return gemv_launch(GV_PLAIN, GV_W16, d->dtype, pl, GvCall{&a, nullptr, 0, 0, 0, st});
-  }
-  const bool glds_ok = (a.K % BK) == 0 && a.M >= 64 && a.N >= 64 && (!d->trans_a || (a.M & 7) == 0) &&
-                       (!d->trans_b || (a.N & 7) == 0) && d->kernel_variant != 1;
-  if ((d->flags & COGV_EPI_COLSUM) && !glds_ok) return COGV_ERR_UNSUPPORTED;
-  if (glds_ok) {
-    // variant 3: generation 2 -- 256x128x32, 4 waves (128x64 each), two workgroups per CU (M or N < 256, huge operands)
-    // variant 9: generation 3 -- 256x256x64 ping-pong (8 waves), persistent, 16x16x32 MFMAs
-    // variant 10: generation 4 -- the same tile and ring with 4 waves of 128x128 (a third fewer LDS fragment bytes per
-    //            flop: +5-7 % forward / dgrad, +15 % wgrad over generation 3): default whenever the 256 tile slots per
-    //            round are filled about as well as variant 3's 512
-    // (the intermediate designs -- 256x128x64 / 128x128x32 / 256x256x32 rings, ping-pong on 32-deep tiles -- measured
-    //  within +-5 % of variant 3 and were removed; DESIGN.md section 4 keeps the numbers)
-    int variant = d->kernel_variant;
-    const size_t a_span = (size_t)(d->trans_a ? a.K : a.M) * a.lda * 2, b_span = (size_t)(d->trans_b ? a.K : a.N) * a.ldb * 2;
-    const bool v9_ok = a.M >= 256 && a.N >= 256 && a_span < (1ull << 32) && b_span < (1ull << 32);   // 32-bit DMA offsets
-    if (variant != 0 && variant != 3 && variant != 9 && variant != 10) variant = 0;
-    if ((d->flags & COGV_EPI_COLSUM) && (!v9_ok || (variant != 0 && variant != 9 && variant != 10))) return COGV_ERR_UNSUPPORTED;
-    if ((d->flags & COGV_EPI_COLSUM) && variant != 9) variant = 10;
-    if ((variant == 9 || variant == 10) && !v9_ok) variant = 0;
-    if (variant == 0) {
-      variant = 3;
-      if (v9_ok) {
-        const int cu = num_cus();
-        const int i3 = ((a.M + 255) / 256) * ((a.N + 127) / 128) * a.splitk, i9 = ((a.M + 255) / 256) * ((a.N + 255) / 256) * a.splitk;
-        const float e3 = (float)i3 / (float)(((i3 + 2 * cu - 1) / (2 * cu)) * 2 * cu);
-        const float e9 = (float)i9 / (float)(((i9 + cu - 1) / cu) * cu);
-        if (e9 * 1.1f >= e3) variant = 10;     // measured 1.1-1.4x at equal fill (16x16x32 MFMAs: less power per flop)
-      }
-    }
-    if (variant == 3) launch_glds_layout<T, 2, 2, 4, 2, 32>(d, a, st);
-    else if (variant == 9 || variant == 10) {                                           // generations 3 / 4 (operands < 4 GiB)
-      GroupArgs ga; ga.count = 1; ga.g[0] = a;
-      const int rc = variant == 10 ? launch_pp64_layout<T, 4>(d->trans_a, d->trans_b, ga, st)
-                                   : launch_pp64_layout<T, 3>(d->trans_a, d->trans_b, ga, st);
-      if (rc != COGV_OK) return rc;
-      a.tiles_m = ga.g[0].tiles_m; a.tiles_n = ga.g[0].tiles_n;
-    }
-    else launch_glds_layout<T, 4, 2, 2, 2, 64>(d, a, st);
-    if (a.splitk > 1) {
-      const size_t nvec = (size_t)a.M * (a.N / 8);
-      int blocks = (int)((nvec + 255) / 256); if (blocks > 2048) blocks = 2048;
-      hipLaunchKernelGGL((splitk_reduce_kernel<T>), dim3(blocks), dim3(256), 0, st, a);
-    }
-    return cogv_check_launch();
-  }
-  dim3 grid(a.tiles_m * a.tiles_n, a.splitk), block(NTHREADS);
-  const size_t shmem = 65536;
-#define LAUNCH(AT_, BT_)                                                                                 \
-  do {                                                                                                   \
-    static bool attr_set = false;                                                                        \
-    if (!attr_set) {                                                                                     \
-      hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_kernel<T, AT_, BT_>),                      \
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);                       \
-      attr_set = true;                                                                                   \
-    }                                                                                                    \
-    hipLaunchKernelGGL((gemm_kernel<T, AT_, BT_>), grid, block, shmem, st, a);                           \
-  } while (0)
-  if (!d->trans_a && !d->trans_b) LAUNCH(false, false);
-  else if (!d->trans_a && d->trans_b) LAUNCH(false, true);
-  else if (d->trans_a && d->trans_b) LAUNCH(true, true);
-  else LAUNCH(true, false);
-#undef LAUNCH
-  if (a.splitk > 1) {
-    const size_t nvec = (size_t)a.M * (a.N / 8);
-    int blocks = (int)((nvec + 255) / 256); if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL((splitk_reduce_kernel<T>), dim3(blocks), dim3(256), 0, st, a);
-  }
-  return cogv_check_launch();
 }
 
 }  // namespace
@@ -423,12 +299,7 @@ static int build_gemm_args(const cogv_gemm_desc* d, GemmArgs& a) {
   a.drop_c0 = ((uint64_t)d->dropout_row0 * (uint64_t)d->N) >> 3;       // N % 8 == 0 (checked above)
   a.thr16 = (d->flags & COGV_EPI_DROPOUT) ? (uint32_t)(d->dropout_p * 65536.0f + 0.5f) : 0u;
   a.keep_scale = 65536.0f / (65536.0f - (float)a.thr16);
-  a.tiles_m = (d->M + BM - 1) / BM; a.tiles_n = (d->N + BN - 1) / BN;
-  const int nk = (d->K + BK - 1) / BK;
-  a.splitk = d->splitk > 1 ? d->splitk : 1;
-  if (a.splitk > nk) a.splitk = nk;
-  a.ktiles_per_split = (nk + a.splitk - 1) / a.splitk;
-  a.splitk = (nk + a.ktiles_per_split - 1) / a.ktiles_per_split;   // no empty splits
+  gemm_split(d->K, d->splitk, a.splitk, a.ktiles_per_split);
   a.colsum_ws = d->colsum_partial;
   if ((d->flags & COGV_EPI_COLSUM) && (!d->colsum_partial || ((uintptr_t)d->colsum_partial & 15) || d->splitk > 1 || d->out_f32)) return COGV_ERR_ARG;
   a.ws = reinterpret_cast<float*>(d->workspace);
@@ -445,13 +316,30 @@ extern "C" int cogv_gemm_reserve_cus(int n) {
   return prev;
 }
 
-extern "C" int cogv_gemm(const cogv_gemm_desc* d, void* stream) {
-  GemmArgs a;
+// what cogv_gemm decides before it launches: the argument block, then the skinny-M plan (M <= 8, decode steps: the HBM-streaming
+// matrix-vector kernels) or the tile plan, or the call's error
+static int gemm_front(const cogv_gemm_desc* d, const GemmEnv& env, GemmArgs& a, GvPlan& gv, GemmPlan& pl) {
   const int rc = build_gemm_args(d, a);
   if (rc != COGV_OK) return rc;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (d->dtype == COGV_F16) return launch_gemm<f16_t>(d, a, st);
-  return launch_gemm<bf16_t>(d, a, st);
+  if (!gemv16_refuses(GV_PLAIN, d) && gv_plan(GV_PLAIN, GV_W16, a.M, a.N, a.K, a.ldb, 0, gv)) {
+    pl = GemmPlan{GEMM_SKINNY};
+    return COGV_OK;
+  }
+  return gemm_plan(*d, env, pl) ? COGV_OK : COGV_ERR_UNSUPPORTED;
+}
+
+extern "C" int cogv_gemm(const cogv_gemm_desc* d, void* stream) {
+  GroupArgs ga;
+  GvPlan gv;
+  GemmPlan pl;
+  const GemmEnv env = gemm_env();
+  const int rc = gemm_front(d, env, ga.g[0], gv, pl);
+  if (rc != COGV_OK) return rc;
+  if (pl.family == GEMM_SKINNY) {
+    ga.g[0].splitk = 1;
+    return gemv_launch(GV_PLAIN, GV_W16, d->dtype, gv, GvCall{&ga.g[0], nullptr, 0, 0, 0, stream});
+  }
+  return launch_tiles(d->dtype, &pl, 1, env, ga, reinterpret_cast<hipStream_t>(stream));
 }
 
 // ---- the skinny-M products with a prologue, and all three on an 8-bit weight operand (gemv.hip, FormV8 / FormM8: it travels in
@@ -483,7 +371,7 @@ static int gemv_ln_args(const cogv_ln_prologue* ln, GemvLnArgs& a) {
 }
 
 // Descriptor of a product of `kind` (w: its 8-bit weight, or NULL) -> argument block and launch plan, or the entry point's
-// error: the front of cogv_gemv_ln, cogv_gemv_attn, the three _w8 calls and cogv_gemv_plan (cogv_gemm's is launch_gemm).
+// error: the front of cogv_gemv_ln, cogv_gemv_attn, the three _w8 calls and cogv_gemv_plan (cogv_gemm's is gemm_front).
 static int gemv_front(int kind, const cogv_gemm_desc* d, const cogv_w8_weight* w, int nsplit, GemmArgs& a, GvPlan& pl,
                       const cogv_ln_prologue* ln = nullptr, GemvLnArgs* la = nullptr) {
   int rc;
@@ -557,52 +445,51 @@ extern "C" int cogv_gemv_plan(int kind, const cogv_gemm_desc* d, const cogv_w8_w
   return COGV_OK;
 }
 
-// Several GEMMs of the same dtype and layout in one persistent launch of the generation-3 kernel (see GroupArgs).
-// Every problem must satisfy that kernel's requirements (M, N >= 256, K % 64 == 0, operands < 4 GiB); otherwise
-// COGV_ERR_UNSUPPORTED and the caller issues them one by one.
-extern "C" int cogv_gemm_grouped(const cogv_gemm_desc* descs, int count, void* stream) {
+// Several GEMMs of the same dtype and layout in one persistent launch of the generation-4 kernel (see GroupArgs).
+// Every problem must satisfy that kernel's requirements (gemm_persistent_takes); otherwise COGV_ERR_UNSUPPORTED and the caller
+// issues them one by one.
+static int grouped_front(const cogv_gemm_desc* descs, int count, const GemmEnv& env, GroupArgs& ga, GemmPlan* pl) {
   if (!descs || count < 1 || count > MAX_GROUP) return COGV_ERR_ARG;
-  GroupArgs ga; ga.count = count;
   for (int i = 0; i < count; ++i) {
     const cogv_gemm_desc* d = descs + i;
     const int rc = build_gemm_args(d, ga.g[i]);
     if (rc != COGV_OK) return rc;
     if (d->dtype != descs[0].dtype || d->trans_a != descs[0].trans_a || d->trans_b != descs[0].trans_b) return COGV_ERR_ARG;
-    const GemmArgs& a = ga.g[i];
-    const size_t a_span = (size_t)(d->trans_a ? a.K : a.M) * a.lda * 2, b_span = (size_t)(d->trans_b ? a.K : a.N) * a.ldb * 2;
-    if ((a.K % BK) || a.M < 256 || a.N < 256 || a_span >= (1ull << 32) || b_span >= (1ull << 32)) return COGV_ERR_UNSUPPORTED;
-    if (d->trans_a && (a.M & 7)) return COGV_ERR_UNSUPPORTED;
-    if (d->trans_b && (a.N & 7)) return COGV_ERR_UNSUPPORTED;
+    if (!gemm_persistent_takes(*d)) return COGV_ERR_UNSUPPORTED;
   }
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int lrc = descs[0].dtype == COGV_F16 ? launch_pp64_layout<f16_t, 4>(descs[0].trans_a, descs[0].trans_b, ga, st)
-                                             : launch_pp64_layout<bf16_t, 4>(descs[0].trans_a, descs[0].trans_b, ga, st);
-  if (lrc != COGV_OK) return lrc;
-  for (int i = 0; i < count; ++i)
-    if (ga.g[i].splitk > 1) {
-      if (descs[0].dtype == COGV_F16) launch_splitk_reduce<f16_t>(ga.g[i], st);
-      else launch_splitk_reduce<bf16_t>(ga.g[i], st);
-    }
-  return cogv_check_launch();
+  gemm_plan_persistent(descs, count, 4, env, pl);
+  return COGV_OK;
+}
+
+extern "C" int cogv_gemm_grouped(const cogv_gemm_desc* descs, int count, void* stream) {
+  GroupArgs ga;
+  GemmPlan pl[MAX_GROUP];
+  const GemmEnv env = gemm_env();
+  const int rc = grouped_front(descs, count, env, ga, pl);
+  return rc != COGV_OK ? rc : launch_tiles(descs[0].dtype, pl, count, env, ga, reinterpret_cast<hipStream_t>(stream));
+}
+
+// host-only: the plan cogv_gemm (count 0) or cogv_gemm_grouped (count >= 1) would launch with, or the call's error
+extern "C" int cogv_gemm_plan(const cogv_gemm_desc* descs, int count, int num_cus, int* out) {
+  static_assert(offsetof(GemmPlan, xp_magic_ig) == COGV_GEMM_PLAN_INTS * sizeof(int), "cogview_hip.h");
+  if (!out || count < 0 || num_cus < 0) return COGV_ERR_ARG;
+  GroupArgs ga;
+  GvPlan gv;
+  GemmPlan pl[MAX_GROUP];
+  const GemmEnv env = gemm_env(num_cus);
+  const int rc = count ? grouped_front(descs, count, env, ga, pl) : gemm_front(descs, env, ga.g[0], gv, pl[0]);
+  if (rc != COGV_OK) return rc;
+  for (int i = 0; i < (count ? count : 1); ++i) memcpy(out + i * COGV_GEMM_PLAN_INTS, &pl[i], COGV_GEMM_PLAN_INTS * sizeof(int));
+  return COGV_OK;
 }
 #else   // COGV_W4_TU: one instantiation of the generation-4 kernel and its launcher
 }  // namespace
 
 #define W4_CAT2(a, b) a##b
 #define W4_CAT(a, b) W4_CAT2(a, b)
-extern "C" __attribute__((visibility("hidden"))) int W4_CAT(cogv_w4_launch_, COGV_W4_TU)(const void* ga, int grid, void* stream) {
+extern "C" __attribute__((visibility("hidden"))) int W4_CAT(cogv_w4_launch_, COGV_W4_TU)(const GemmPlan* pl, const void* ga, void* stream) {
   using T = std::conditional<(COGV_W4_TU & 4) != 0, f16_t, bf16_t>::type;
-  constexpr int L = COGV_W4_TU & 3;
-  constexpr bool AT = L >= 2, BT = L == 1 || L == 2;
-  constexpr int shmem = 2 * 65536 + 4 * 4096;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_w4_kernel<T, AT, BT>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, shmem);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((gemm_w4_kernel<T, AT, BT>), dim3(grid), dim3(256), shmem, reinterpret_cast<hipStream_t>(stream),
-                     *reinterpret_cast<const GroupArgs*>(ga));
-  return COGV_OK;
+  constexpr int L = COGV_W4_TU & 3;                      // layout index (gemm_layout)
+  return launch_planned<&gemm_w4_kernel<T, (L >= 2), (L == 1 || L == 2)>>(*pl, *reinterpret_cast<const GroupArgs*>(ga), reinterpret_cast<hipStream_t>(stream));
 }
 #endif

@@ -259,9 +259,7 @@ def gemm(a, b, trans_a=False, trans_b=False, out=None, bias=None, gelu=False, ge
     if accumulate:
         flags |= L.EPI_ACCUM
     lib = L.lib()
-    fuse_colsum = (colsum_out is not None and M >= 256 and N >= 256 and K % 64 == 0 and variant in (0, 9, 10)
-                   and out.dtype != torch.float32 and a.stride(0) * a.shape[0] * 2 < 2 ** 32
-                   and b.stride(0) * b.shape[0] * 2 < 2 ** 32 and (trans_b is False or N % 8 == 0) and not trans_a)
+    fuse_colsum = colsum_out is not None and _fuse_colsum(d, variant)
     if fuse_colsum:
         flags |= L.EPI_COLSUM
         cs_rows = lib.cogv_gemm_colsum_rows(M)
@@ -294,6 +292,23 @@ def gemm(a, b, trans_a=False, trans_b=False, out=None, bias=None, gelu=False, ge
         else:
             colsum(out, out=colsum_out, accumulate=colsum_accumulate)
     return out
+
+
+def _persistent_takes(d, colsum=False):
+    """The library's answer (cogv_gemm_plan, host only) to: does the persistent kernel -- generation 4, the one that fuses the
+    column sums and the one cogv_gemm_grouped launches -- take the problem of descriptor d?  Asked with kernel_variant 10, which
+    falls back to auto dispatch where it does not; with `colsum`, asked as the COGV_EPI_COLSUM launch itself (no split-K; the
+    partial-sum pointer is an aligned stand-in that nothing reads)."""
+    q = L.GemmDesc.from_buffer_copy(d)
+    q.kernel_variant, q.splitk, q.flags, q.colsum_partial = 10, 1, L.EPI_COLSUM if colsum else 0, 16
+    rc, plan = L.gemm_plan(q)
+    return rc == L.OK and plan[0]["family"] == 0 and plan[0]["generation"] == 4
+
+
+def _fuse_colsum(d, variant):
+    """gemm's policy for the bias gradient: fused into the epilogue of a 16-bit, auto-dispatched (or generation 3 / 4) product
+    whose A is stored [M, K], where the library takes it; a separate pass over the output otherwise."""
+    return not d.trans_a and variant in (0, 9, 10) and not d.out_f32 and _persistent_takes(d, colsum=True)
 
 
 def gemm_reserve_cus(n):
@@ -390,8 +405,7 @@ def gemm_grouped(problems, trans_a=True, trans_b=True, accumulate=True):
         kmin = K if kmin is None else min(kmin, K)
         flops += 2.0 * M * N * K
         nbytes += 2.0 * (M * K + N * K + M * N)
-    ok = all(M >= 256 and N >= 256 and K % 64 == 0 for M, N, K in shapes)
-    if not ok:
+    if not all(_persistent_takes(d) for d in descs):
         for a, b, out, acc in problems:
             gemm(a, b, trans_a=trans_a, trans_b=trans_b, out=out, accumulate=acc)
         return

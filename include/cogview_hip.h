@@ -97,7 +97,7 @@ int cogv_colsum_finalize(int dtype, const float* partial, int rows, int N, void*
 /* Up to 16 GEMMs of one dtype and layout (same trans_a / trans_b) in ONE persistent launch: the weight gradients
  * dW = dY^T X of the four linears of a layer -- or of several layers -- (autograd of mpu/layers.py:243,319) fill the
  * 256 CUs together where each alone would leave a partial last round.  COGV_ERR_UNSUPPORTED when a problem does not fit the 256x256x64
- * kernel (M, N >= 256, K % 64 == 0): issue them one by one then.  Split-K as in cogv_gemm, per problem. */
+ * kernel (M, N >= 256, K % 64 == 0, A and B each span < 4 GiB): issue them one by one then.  Split-K as in cogv_gemm, per problem. */
 int cogv_gemm_grouped(const cogv_gemm_desc* descs, int count, void* stream);
 /* Note: the persistent GEMM kernel distributes tiles through per-XCD atomic work queues; the library keeps their
  * counters in 4 KiB of device memory per GPU that it allocates itself on the first GEMM call (its only allocation). */
@@ -107,6 +107,17 @@ int cogv_gemm_pick_splitk_tiles(int tiles_256x256, int K);
  * runs concurrently with the launch: the row-parallel Linear of mpu/layers.py:312-326 computed in row chunks, chunk i's
  * reduce (mpu/mappings.py:22-31) under chunk i + 1's GEMM.  Process-wide, not thread safe; returns the previous value. */
 int cogv_gemm_reserve_cus(int n);
+/* Host-only query (no device is touched, no pointer of a descriptor is dereferenced): what cogv_gemm (count = 0: descs[0] -- F.linear
+ * at mpu/layers.py:243,319, model/gpt2_modeling.py:117 and their autograd) or cogv_gemm_grouped (count >= 1) would launch on a
+ * device of num_cus CUs (0: this device's, 256 without one) under the current cogv_gemm_reserve_cus -- from the function those
+ * launches use (csrc/gemm_plan.h) -- and exactly the error they would return before launching (out is left untouched then).
+ * out: COGV_GEMM_PLAN_INTS ints per problem = { family (0: a tile kernel; 1: cogv_gemm's skinny-M case, the rest 0: see
+ * cogv_gemv_plan), generation (1 .. 4 = kernel_variant 1, 3, 9, 10), tile M, tile N, tiles M, tiles N, effective splitk, k-tiles (of
+ * 64) per split, first item of the problem in the launch's work list, items of the launch, grid x, grid y, threads, dynamic LDS
+ * bytes, blocks of the split-K reduce (0: none), exact prefetch across items (generation 4), layout index (0 NT, 1 NN: trans_b,
+ * 2 TN: both, 3: trans_a only) }. */
+#define COGV_GEMM_PLAN_INTS 17
+int cogv_gemm_plan(const cogv_gemm_desc* descs, int count, int num_cus, int* out);
 
 /* Decode-step matrix-vector product with the layer's LayerNorms as prologue (M <= 8 rows, K = hidden size <= 4096,
  * K % 512 == 0; trans_a = trans_b = 0; epilogue flags BIAS | GELU | ABSMAX only; d->A is ignored):
