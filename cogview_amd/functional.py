@@ -991,10 +991,6 @@ def decode_attention(qkv, slot, heads, combine=True):
     return res
 
 
-def _slot_capacity(slot):
-    return slot.capacity if getattr(slot, "scale", None) is not None else slot.cache.shape[1]
-
-
 def decode_chain_supported(tr, batch):
     """The fused decode chain (decode_chain) covers the dense, single-partition model in a 16-bit type at one token per
     row: what a captured decode step runs."""
@@ -1089,7 +1085,7 @@ def decode_chain(tr, h0, absmax0, slots, emb_weight, w8=None):
         if hp % 512 == 0 and _decode_fuse_combine():
             # the key splits' partials are combined in the prologue of the attention-output GEMV (one launch less)
             parts = decode_attention(qkv.view(b, 1, 3 * hp), slot, npp, combine=False)
-            ao = gemv_attn(parts, npp, _slot_capacity(slot), w_dense, att_m.dense.bias)
+            ao = gemv_attn(parts, npp, slot.capacity, w_dense, att_m.dense.bias)
         else:
             att = decode_attention(qkv.view(b, 1, 3 * hp), slot, npp)
             ao = gemm(att.view(b, hp), w_dense, bias=att_m.dense.bias)

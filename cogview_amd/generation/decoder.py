@@ -17,48 +17,51 @@ from ..mpu.transformer import KV8Cache, StaticKVSlot
 
 
 WEIGHT_FORMATS = ("e4m3",)
-
-
-def refuse_w8_unsupported(weights, tr, batch):
-    """weights= of the decoders: what the 8-bit decode step does not cover, refused before anything is quantized."""
-    from ..mpu.initialize import mp_world_size_or_1
-    if weights not in WEIGHT_FORMATS:
-        raise ValueError(f"weights={weights!r}: None (16-bit) or one of {WEIGHT_FORMATS}")
-    if mp_world_size_or_1() > 1:
-        raise NotImplementedError(f"weights={weights!r} with model parallelism > 1: use the 16-bit decoder (weights=None)")
-    dt = tr.layers[0].attention.query_key_value.weight.dtype
-    if dt not in (torch.float16, torch.bfloat16):
-        raise NotImplementedError(f"weights={weights!r} on a {dt} model: the 8-bit step computes in fp16 / bf16")
-    why = F_.w8_decode_supported(tr, batch)
-    if why is not None:
-        raise NotImplementedError(f"weights={weights!r}: {why}")
-
-
 KV_FORMATS = ("e4m3",)
 
 
-def refuse_kv8_unsupported(kv, tr):
-    """kv= of the decoders: what the 8-bit key/value cache does not cover, refused before anything is allocated."""
+def unwrap(model):
+    while hasattr(model, "module"):
+        model = model.module
+    return model
+
+
+def refuse_unsupported(weights=None, kv=None, ragged=False, args=None, model=None, batch=None, use=None):
+    """The one rule for what the decode step's options do not cover, applied before anything is allocated or quantized.
+    Asked for: weights= / kv= (formats) and ragged=True.  Known, each optional: `args` (a caller's .is_sparse), `model` (its storage
+    type), `batch` (the decoder's rows; with it the 8-bit weight stream is put to the kernels' launch plan).  `use`: what the message
+    advises instead (a caller's host form; default: the decoder's own plain options).  Sparse generation and model parallelism > 1
+    are refused for every caller that hands in `args`, with or without options; a plain decoder refuses nothing."""
     from ..mpu.initialize import mp_world_size_or_1
-    if kv not in KV_FORMATS:
+    if weights is not None and weights not in WEIGHT_FORMATS:
+        raise ValueError(f"weights={weights!r}: None (16-bit) or one of {WEIGHT_FORMATS}")
+    if kv is not None and kv not in KV_FORMATS:
         raise ValueError(f"kv={kv!r}: None (16-bit cache) or one of {KV_FORMATS}")
-    if mp_world_size_or_1() > 1:
-        raise NotImplementedError(f"kv={kv!r} with model parallelism > 1: use the 16-bit cache (kv=None)")
-    dt = tr.layers[0].attention.query_key_value.weight.dtype
-    if dt not in (torch.float16, torch.bfloat16):
-        raise NotImplementedError(f"kv={kv!r} on a {dt} model: the 8-bit cache is read by the fp16 / bf16 decode step (kv=None: "
-                                  f"the 16-bit cache)")
-
-
-def refuse_ragged_unsupported(tr):
-    """ragged=True of the decoders: refused before anything is allocated, as kv= is."""
-    from ..mpu.initialize import mp_world_size_or_1
-    if mp_world_size_or_1() > 1:
-        raise NotImplementedError("ragged=True with model parallelism > 1: one prompt per decoder (ragged=False)")
-    dt = tr.layers[0].attention.query_key_value.weight.dtype
-    if dt not in (torch.float16, torch.bfloat16):
-        raise NotImplementedError(f"ragged=True on a {dt} model: the decode attention that reads `first` is the fp16 / bf16 "
-                                  f"decode step's (ragged=False: one prompt per decoder)")
+    asked = {name: value for name, value in (("weights", weights), ("kv", kv), ("ragged", ragged or None)) if value is not None}
+    what = " with " + ", ".join(f"{name}={value!r}" for name, value in asked.items()) if asked else ""
+    if use is None:
+        use = ", ".join(f"{name}={False if name == 'ragged' else None}" for name in asked)
+    if args is not None:
+        if args.is_sparse == 2:
+            raise NotImplementedError(f"sparse generation (is_sparse = 2){what}: use {use}")
+        if args.is_sparse != 0:
+            raise ValueError('set is_sparse==2 for inference.')
+    if (args is not None or asked) and mp_world_size_or_1() > 1:
+        raise NotImplementedError(f"model parallelism > 1{what}: use {use}")
+    if model is None or not asked:
+        return
+    gpt = unwrap(model)
+    dt = gpt.word_embeddings.weight.dtype
+    # (a caller without the decoder's row count leaves weights= to the decoder, where the transformer is looked at anyway)
+    if dt not in (torch.float16, torch.bfloat16) and (kv is not None or ragged or batch is not None):
+        raise NotImplementedError(f"a {dt} model{what}: the 8-bit formats and the per-row `first` slot are the fp16 / bf16 decode "
+                                  f"step's -- use {use}")
+    if weights is not None and batch is not None:
+        if gpt.word_embeddings.weight.shape[0] % 8:
+            raise NotImplementedError(f"weights={weights!r}: a vocabulary of {gpt.word_embeddings.weight.shape[0]} rows (not a multiple of 8)")
+        why = F_.w8_decode_supported(gpt.transformer, batch)
+        if why is not None:
+            raise NotImplementedError(f"weights={weights!r}: {why}")
 
 
 class GraphDecoder:
@@ -83,20 +86,12 @@ class GraphDecoder:
         bookkeeping stays shared.  The one new piece of device data is self.first (int32 [batch], zeros): row b attends slots
         [first[b], *pos_index] (cogv_attn_decode_desc.first).  Its address is baked into a capture, so the choice is made
         here.  One model-parallel partition, fp16 / bf16.  False (default): nothing is allocated, the step is what it was."""
-        m = model
-        while hasattr(m, "module"):
-            m = m.module
+        m = unwrap(model)
         self.gpt, tr = m, m.transformer
         assert capacity <= 4096
         self.w8, self.kv, self.first = None, kv, None
-        if ragged:
-            refuse_ragged_unsupported(tr)
-        if kv is not None:
-            refuse_kv8_unsupported(kv, tr)
+        refuse_unsupported(weights, kv, ragged, model=m, batch=batch)
         if weights is not None:
-            refuse_w8_unsupported(weights, tr, batch)
-            if m.word_embeddings.weight.shape[0] % 8:
-                raise NotImplementedError(f"weights={weights!r}: a vocabulary of {m.word_embeddings.weight.shape[0]} rows (not a multiple of 8)")
             with torch.no_grad():
                 self.w8 = F_.W8Weights(tr, m.word_embeddings.weight)
         p0 = tr.layers[0].attention.query_key_value.weight
@@ -128,15 +123,12 @@ class GraphDecoder:
         self.slab.zero_()
         with ops.scalar_slab(self.slab):
             h = tr.embed(self.tok, self.pos, self.gpt.word_embeddings)
-            if self.w8 is not None:
-                # the same two paths on the 8-bit copies of the weights
-                if self.fused and F_.decode_chain_supported(tr, self.batch):
-                    return F_.decode_chain(tr, h, h._cogv_absmax, self.slots, self.gpt.word_embeddings.weight, w8=self.w8)
-                return F_.decode_layers_w8(tr, h, h._cogv_absmax, self.slots, self.w8)
             if self.fused and F_.decode_chain_supported(tr, self.batch):
                 # five launches per layer: the LayerNorms ride as prologues of the GEMVs, the cache append inside the
-                # decode attention kernel (functional.decode_chain)
-                return F_.decode_chain(tr, h, h._cogv_absmax, self.slots, self.gpt.word_embeddings.weight)
+                # decode attention kernel (functional.decode_chain); w8: the same chain on the 8-bit copies of the weights
+                return F_.decode_chain(tr, h, h._cogv_absmax, self.slots, self.gpt.word_embeddings.weight, w8=self.w8)
+            if self.w8 is not None:
+                return F_.decode_layers_w8(tr, h, h._cogv_absmax, self.slots, self.w8)
             for layer, slot in zip(tr.layers, self.slots):
                 h = layer(h, 0, mem=slot)
             out = tr.final_layernorm(h)
@@ -163,9 +155,28 @@ class GraphDecoder:
         assert tokens.shape[0] == self.batch
         return self._prefill(tokens, position_ids, attention_mask)
 
-    def _prefill(self, tokens, position_ids, attention_mask):
-        """prefill's body; tokens of ONE row fill every cache row (the keys / values broadcast over the batch)."""
-        assert tokens.shape[0] in (1, self.batch) and tokens.shape[1] < self.cap
+    def _prefill(self, tokens, position_ids, attention_mask, pads=None):
+        """prefill's body; tokens of ONE row fill every cache row (the keys / values broadcast over the batch).
+        pads (ragged=True; attention_mask is not read): G prompts of different lengths, tokens / position_ids [G, P], every prompt
+        right-aligned (row g's ids in columns [pads[g], P)); the padding columns are overwritten here with a real id (the row's
+        first token) and position 0.  One model call under the mask M[g, i, j] = (j <= i) and (j >= pads[g]) (the general-mask
+        attention path: prompt-length work); the memories of prompt g fill its batch // G cache rows, first[b] = pads[g] keeps the
+        padding slots out of every later step.  Returns the logits [rows of tokens, n, vocab]."""
+        G, n = tokens.shape
+        assert n < self.cap
+        dev, nb = self.table.device, 1
+        if pads is None:
+            assert G in (1, self.batch)
+        else:
+            assert self.first is not None, "built without ragged=True"
+            assert len(pads) == G and self.batch % G == 0 and n > 0 and all(0 <= p < n for p in pads)
+            nb = self.batch // G
+            pad_t = torch.tensor(list(pads), dtype=torch.long, device=dev)
+            col = torch.arange(n, dtype=torch.long, device=dev)
+            is_pad = col.unsqueeze(0) < pad_t.unsqueeze(1)                                            # [G, n]
+            tokens = torch.where(is_pad, tokens.gather(1, pad_t.unsqueeze(1)).expand(G, n), tokens)
+            position_ids = position_ids.masked_fill(is_pad, 0)
+            attention_mask = ((col.view(1, 1, n) <= col.view(1, n, 1)) & (col.view(1, 1, n) >= pad_t.view(G, 1, 1))).float().unsqueeze(1)
         tr = self.gpt.transformer
         kv_flag, tr.kv_cache = tr.kv_cache, True
         max_mem, tr.max_memory_length = tr.max_memory_length, max(tr.max_memory_length, self.cap)
@@ -173,54 +184,25 @@ class GraphDecoder:
             logits, *mems = self.gpt(tokens, position_ids, attention_mask, None, None, 0)
         finally:
             tr.kv_cache, tr.max_memory_length = kv_flag, max_mem
-        n = tokens.shape[1]
-        if self.kv8 is not None:
-            for slot, mem in zip(self.slots, mems):       # 1 or B rows of 16-bit keys | values -> bytes + scales of all B rows
-                slot.load(mem)
+        for slot, mem in zip(self.slots, mems):           # 1 or B rows; row g * nb + j: candidate j of prompt g
+            slot.load(mem.repeat_interleave(nb, 0) if nb > 1 else mem)
+        if pads is None:
+            self.table[:, :n] = torch.arange(n, dtype=torch.int32, device=dev)
         else:
-            for c, mem in zip(self.caches, mems):
-                c[:, :n].copy_(mem)
-        self.table[:, :n] = torch.arange(n, dtype=torch.int32, device=self.table.device)
+            first = pad_t.repeat_interleave(nb).to(torch.int32)
+            self.first.copy_(first)
+            # (the op-by-op step reads the table: the padding slots stay flagged)
+            self.table[:, :n] = torch.where(col.unsqueeze(0) < first.unsqueeze(1), self.masked[:n].unsqueeze(0), col.to(torch.int32).unsqueeze(0))
         self.table[:, n:] = self.masked[n:]           # a longer earlier run left these visible (the op-by-op step reads them)
         self.length = n
         return logits
 
-    def _prefill_ragged(self, tokens, position_ids, pads):
-        """_prefill for G prompts of different lengths (ragged=True): tokens / position_ids [G, P], every prompt right-aligned
-        (row g's ids in columns [pads[g], P)); the padding columns are overwritten here with a real id (the row's first token)
-        and position 0.  One model call under the mask M[g, i, j] = (j <= i) and (j >= pads[g]) (the general-mask attention
-        path: prompt-length work); the memories of prompt g fill its batch // G cache rows, first[b] = pads[g] keeps the
-        padding slots out of every later step.  Returns the logits [G, P, vocab]."""
-        G, P = tokens.shape
-        assert self.first is not None, "built without ragged=True"
-        assert len(pads) == G and self.batch % G == 0 and 0 < P < self.cap and all(0 <= p < P for p in pads)
-        nb, dev = self.batch // G, self.table.device
-        pad_t = torch.tensor(list(pads), dtype=torch.long, device=dev)
-        col = torch.arange(P, dtype=torch.long, device=dev)
-        is_pad = col.unsqueeze(0) < pad_t.unsqueeze(1)                                            # [G, P]
-        tokens = torch.where(is_pad, tokens.gather(1, pad_t.unsqueeze(1)).expand(G, P), tokens)
-        position_ids = position_ids.masked_fill(is_pad, 0)
-        mask = ((col.view(1, 1, P) <= col.view(1, P, 1)) & (col.view(1, 1, P) >= pad_t.view(G, 1, 1))).float().unsqueeze(1)
-        tr = self.gpt.transformer
-        kv_flag, tr.kv_cache = tr.kv_cache, True
-        max_mem, tr.max_memory_length = tr.max_memory_length, max(tr.max_memory_length, self.cap)
-        try:
-            logits, *mems = self.gpt(tokens, position_ids, mask, None, None, 0)
-        finally:
-            tr.kv_cache, tr.max_memory_length = kv_flag, max_mem
-        for i, (slot, mem) in enumerate(zip(self.slots, mems)):
-            rows = mem.repeat_interleave(nb, 0) if nb > 1 else mem          # row g * nb + j: candidate j of prompt g
-            if self.kv8 is not None:
-                slot.load(rows)
-            else:
-                self.caches[i][:, :P].copy_(rows)
-        first = pad_t.repeat_interleave(nb).to(torch.int32)
-        self.first.copy_(first)
-        # (the op-by-op step reads the table: the padding slots stay flagged)
-        self.table[:, :P] = torch.where(col.unsqueeze(0) < first.unsqueeze(1), self.masked[:P].unsqueeze(0), col.to(torch.int32).unsqueeze(0))
-        self.table[:, P:] = self.masked[P:]
-        self.length = P
-        return logits
+    def _replay_or_step(self):
+        """One decode step: a replay of the captured graph, else the same launches eagerly.  Returns the logits."""
+        if self.graph is None:
+            return self._step()
+        self.graph.replay()
+        return self.logits
 
     @torch.no_grad()
     def step(self, token, position):
@@ -231,11 +213,7 @@ class GraphDecoder:
         self.pos.copy_(position.view(self.batch, 1))
         self.pos_index.fill_(self.length)
         self.table[:, self.length] = self.length          # this step's own slot becomes visible
-        if self.graph is not None:
-            self.graph.replay()
-            logits = self.logits
-        else:
-            logits = self._step()
+        logits = self._replay_or_step()
         self.length += 1
         return logits
 
@@ -280,6 +258,14 @@ class SamplingDecoder(GraphDecoder):
             self._sample(logits)
         return logits
 
+    def _first_draw(self, last_pos, last_logits, rows=None):
+        """The tail of start / start_ragged after the prefill: every row's first token is drawn from its prompt's last logits, and
+        the draw's bookkeeping leaves the decoder at the next step."""
+        self.pos_index.fill_(self.length - 1)
+        self.pos.copy_(last_pos)
+        self.scores.zero_()
+        self._sample(last_logits, rows=rows)
+
     @torch.no_grad()
     def start(self, tokens, position_ids, attention_mask=0):
         """Prefill ONE context row [1, n] into every cache row, then draw the first token of every row from its last
@@ -287,27 +273,19 @@ class SamplingDecoder(GraphDecoder):
         leaves the decoder at the next step: slot n visible, the drawn ids and positions in the static buffers."""
         assert self.sampling is not None and tokens.shape[0] == 1
         logits = self._prefill(tokens, position_ids, attention_mask)
-        n = tokens.shape[1]
-        self.pos_index.fill_(n - 1)
-        self.pos.copy_(position_ids[:, -1:].expand(self.batch, 1))
-        self.scores.zero_()
-        self._sample(logits[:, -1], rows=self.batch)
+        self._first_draw(position_ids[:, -1:].expand(self.batch, 1), logits[:, -1], rows=self.batch)
         return logits
 
     @torch.no_grad()
     def start_ragged(self, tokens, position_ids, pads):
         """start() for G prompts (ragged=True): tokens / position_ids [G, P] right-aligned, pads[g] padding columns in front of
-        prompt g (_prefill_ragged).  Every prompt's last logits draw the first token of its batch // G rows -- the rows are
+        prompt g (_prefill's pads).  Every prompt's last logits draw the first token of its batch // G rows -- the rows are
         repeated, so the sampler reads [batch, vocab] with a real row stride -- and every row's position counts on from its
         own prompt's last position id."""
         assert self.sampling is not None
-        logits = self._prefill_ragged(tokens, position_ids, pads)
-        G, P = tokens.shape
-        nb = self.batch // G
-        self.pos_index.fill_(P - 1)
-        self.pos.copy_(position_ids[:, -1:].repeat_interleave(nb, 0))
-        self.scores.zero_()
-        self._sample(logits[:, -1].repeat_interleave(nb, 0))
+        logits = self._prefill(tokens, position_ids, None, pads)
+        nb = self.batch // tokens.shape[0]
+        self._first_draw(position_ids[:, -1:].repeat_interleave(nb, 0), logits[:, -1].repeat_interleave(nb, 0))
         return logits
 
     def capture(self):
@@ -328,9 +306,6 @@ class SamplingDecoder(GraphDecoder):
         row.  Returns (out_tokens, scores) -- device tensors; nothing is read back on the way."""
         assert self.sampling is not None and self.length + n <= self.cap, "key/value cache capacity exhausted"
         for _ in range(n):
-            if self.graph is not None:
-                self.graph.replay()
-            else:
-                self._step()
+            self._replay_or_step()
         self.length += n
         return self.out_tokens, self.scores

@@ -10,6 +10,7 @@ re-projected every step, as in mpu/sparse_transformer.py:135-140).
 import torch
 import torch.nn.functional as F
 
+from . import decoder
 from .id_space import IdSpace
 
 
@@ -205,7 +206,7 @@ def inverse_prompt_score_on_device(model, seq, args, tokenizer=None, image_token
     from .. import functional as F_
     from .. import ops
     tokenizer = tokenizer if tokenizer is not None else IdSpace()
-    _refuse_unsupported(args, use="inverse_prompt_score")
+    decoder.refuse_unsupported(args=args, use="inverse_prompt_score")
     assert seq.dim() == 2
     first_text = 2 + image_tokens + 1                            # index of [ROI1]: the text it scores starts right after
     n_text = seq.shape[1] - 1 - first_text
@@ -215,7 +216,7 @@ def inverse_prompt_score_on_device(model, seq, args, tokenizer=None, image_token
         raise ValueError(f"[ROI1] is not at index {first_text} of every row")
     if max_rows is None:
         max_rows = getattr(args, "max_inference_batch_size", None)
-    gpt = _unwrap(model)
+    gpt = decoder.unwrap(model)
     vocab = gpt.word_embeddings.weight.shape[0]
     scores = torch.empty(seq.shape[0], dtype=torch.float32, device=seq.device)
     with torch.no_grad():
@@ -398,50 +399,61 @@ def plan_device_fill(seq_l, tokenizer, vocab):
                 capacity=_plan_capacity(len(seq_l)))
 
 
-def _refuse_unsupported(args, use="filling_sequence", weights=None, kv=None):
-    """What only the host form (`use`) does, refused before the model is touched."""
-    from ..mpu.initialize import mp_world_size_or_1
-    if kv is not None:
-        from .decoder import KV_FORMATS
-        if kv not in KV_FORMATS:
-            raise ValueError(f"kv={kv!r}: None (16-bit cache) or one of {KV_FORMATS}")
-        if args.is_sparse == 2:
-            raise NotImplementedError(f"sparse generation (is_sparse = 2) with kv={kv!r}: use {use}")
-        if mp_world_size_or_1() > 1:
-            raise NotImplementedError(f"model parallelism > 1 with kv={kv!r}: use {use}")
-    if weights is not None:
-        from .decoder import WEIGHT_FORMATS
-        if weights not in WEIGHT_FORMATS:
-            raise ValueError(f"weights={weights!r}: None (16-bit) or one of {WEIGHT_FORMATS}")
-        if args.is_sparse == 2:
-            raise NotImplementedError(f"sparse generation (is_sparse = 2) with weights={weights!r}: use {use}")
-        if mp_world_size_or_1() > 1:
-            raise NotImplementedError(f"model parallelism > 1 with weights={weights!r}: use {use}")
-    if args.is_sparse == 2:
-        raise NotImplementedError(f"sparse generation (is_sparse = 2): use {use}")
-    if args.is_sparse != 0:
-        raise ValueError('set is_sparse==2 for inference.')
-    if mp_world_size_or_1() > 1:
-        raise NotImplementedError(f"model parallelism > 1: use {use}")
+class _DeviceRun:
+    """What the device entry points share: the refusals, ONE lazily built SamplingDecoder with its format keywords, the sampler
+    armed for (temperature, top_k, top_p, allow) -- baked into a capture, so other values re-arm it and drop the graph, while the
+    generator offset keeps counting -- and the run itself: start, capture once, generate.  generate_on_device and
+    generate_batch_on_device use one for one call; DeviceGenerator and DeviceFiller keep theirs call after call.
+    .out [batch, width] receives the id drawn for sequence position out_base + j in column j; .given (DeviceFiller) is the sampler's
+    given table."""
+    given = None
 
+    def __init__(self, model, args, seed=0, capture=True, weights=None, kv=None, ragged=False):
+        decoder.refuse_unsupported(weights, kv, ragged, args=args, model=model, use="filling_sequence")
+        self.model, self.seed, self.capture, self.ragged = model, int(seed), capture, ragged
+        self.formats = {"weights": weights}           # only the keywords that are set: a default build issues the call it always did
+        if kv is not None:
+            self.formats["kv"] = kv
+        if ragged:
+            self.formats["ragged"] = True
+        self.dec, self.key, self.out = None, None, None
 
-def _unwrap(model):
-    while hasattr(model, "module"):
-        model = model.module
-    return model
+    def size(self, batch, capacity, width=None, out_base=0):
+        if not 0 < capacity <= 4096:
+            raise ValueError(f"capacity {capacity} outside (0, 4096]: the decode cache's limit")
+        self.batch, self.capacity, self.out_base = int(batch), int(capacity), out_base
+        self.width = width if width is not None else self.capacity
 
+    def vocab(self):
+        return decoder.unwrap(self.model).word_embeddings.weight.shape[0]
 
-def _decoder_formats(weights, kv):
-    """The format keywords a decoder is built with: only those that are set (a default build issues the call it always did)."""
-    kw = {"weights": weights}
-    if kv is not None:
-        kw["kv"] = kv
-    return kw
+    def _buffers(self, dev):
+        self.out = torch.empty((self.batch, self.width), dtype=torch.long, device=dev)
 
+    def arm(self, args, allow):
+        """The decoder, built at the first call, with the sampler armed for this call's values."""
+        if self.dec is None:
+            self.dec = decoder.SamplingDecoder(self.model, batch=self.batch, capacity=self.capacity, **self.formats)
+            self._buffers(self.dec.tok.device)
+        key = (float(args.temperature), int(args.top_k), float(args.top_p), tuple(allow))
+        if key != self.key:
+            offset = self.dec.offset.clone() if self.key is not None else None
+            self.dec.enable_sampling(*key[:3], allow=allow, seed=self.seed, out_tokens=self.out, out_base=self.out_base, given=self.given)
+            if offset is not None:
+                self.dec.offset.copy_(offset)
+            self.dec.graph, self.key = None, key
+        return self.dec
 
-def _refuse_fp32_kv8(model, kv, use="filling_sequence"):
-    if kv is not None and model is not None and _unwrap(model).word_embeddings.weight.dtype == torch.float32:
-        raise NotImplementedError(f"kv={kv!r} on a float32 model: use {use} (or the 16-bit cache of an fp16 / bf16 model)")
+    def run(self, steps, *context):
+        """start / start_ragged on `context`, then `steps` decode steps on the graph (captured now unless an earlier call did)."""
+        dec = self.dec
+        with torch.no_grad():
+            (dec.start_ragged if self.ragged else dec.start)(*context)
+            if steps:
+                if self.capture and dec.graph is None:
+                    dec.capture()
+                dec.generate(steps)
+        return dec.scores.clone()
 
 
 def generate_on_device(model, seq, args, tokenizer=None, seed=0, capture=True, weights=None, kv=None):
@@ -455,25 +467,17 @@ def generate_on_device(model, seq, args, tokenizer=None, seed=0, capture=True, w
     capture=False runs the same launches eagerly (the reference for the captured form).
     weights="e4m3": the decode steps stream 8-bit copies of the weights (GraphDecoder's `weights`; the prefill stays 16-bit).
     kv="e4m3": the key/value caches hold 8-bit keys and values (GraphDecoder's `kv`); composes with `weights`."""
-    from .decoder import SamplingDecoder
     tokenizer = tokenizer if tokenizer is not None else IdSpace()
-    _refuse_unsupported(args, weights=weights, kv=kv)
-    _refuse_fp32_kv8(model, kv)
+    drv = _DeviceRun(model, args, seed, capture, weights, kv)
     assert seq.dim() == 1
-    plan = plan_device_generation(seq.tolist(), tokenizer, _unwrap(model).word_embeddings.weight.shape[0])
+    plan = plan_device_generation(seq.tolist(), tokenizer, drv.vocab())
     n, run, nb = plan["context"], plan["run"], plan["nb"]
     tokens, attention_mask, position_ids = get_batch(seq[:n], seq.device, args)
     position_ids[position_ids > plan["offset"]] -= plan["offset"]
-    dec = SamplingDecoder(model, batch=nb, capacity=plan["capacity"], **_decoder_formats(weights, kv))
-    out = torch.empty((nb, run), dtype=torch.long, device=tokens.device)
-    dec.enable_sampling(args.temperature, args.top_k, args.top_p, plan["allow"], seed, out_tokens=out, out_base=n)
-    with torch.no_grad():
-        dec.start(tokens, position_ids, attention_mask)
-        if run > 1:
-            if capture:
-                dec.capture()
-            dec.generate(run - 1)
-    return torch.cat((tokens.expand(nb, n), out), dim=1).to(seq.device), dec.scores.clone()
+    drv.size(nb, plan["capacity"], width=run, out_base=n)
+    drv.arm(args, plan["allow"])
+    scores = drv.run(run - 1, tokens, position_ids, attention_mask)
+    return torch.cat((tokens.expand(nb, n), drv.out), dim=1).to(seq.device), scores
 
 
 def _batch_inputs(seqs, plan, device):
@@ -490,19 +494,19 @@ def _batch_inputs(seqs, plan, device):
     return tokens, position_ids
 
 
-def _batch_rows(seqs, plan, out, col0):
-    """Per prompt [nb, len(seq_g)]: its context followed by the run its nb rows drew (columns [col0, col0 + run) of `out`)."""
-    nb, run = plan["nb"], plan["run"]
+def _batch_run(drv, seqs, plan, args):
+    """One prompt set through a ragged run driver.  Returns (per prompt [nb, len(seq_g)]: its context followed by the run its nb
+    rows drew, scores [G, nb]); row g * nb + j is candidate j of prompt g."""
+    P, run, nb = plan["P"], plan["run"], plan["nb"]
+    dec = drv.arm(args, plan["allow"])
+    tokens, position_ids = _batch_inputs(seqs, plan, dec.tok.device)
+    scores = drv.run(run - 1, tokens, position_ids, plan["pads"])
+    col0 = P - drv.out_base
     res = []
     for g, (seq, n) in enumerate(zip(seqs, plan["contexts"])):
-        drawn = out[g * nb:(g + 1) * nb, col0:col0 + run].to(seq.device)
+        drawn = drv.out[g * nb:(g + 1) * nb, col0:col0 + run].to(seq.device)
         res.append(torch.cat((seq[:n].unsqueeze(0).expand(nb, n), drawn), dim=1))
-    return res
-
-
-def _refuse_fp32_ragged(model):
-    if model is not None and _unwrap(model).word_embeddings.weight.dtype == torch.float32:
-        raise NotImplementedError("several prompts on one decode graph on a float32 model: use generate_on_device per sequence")
+    return res, scores.view(len(seqs), nb).to(seqs[0].device)
 
 
 def generate_batch_on_device(model, seqs, args, tokenizer=None, seed=0, capture=True, weights=None, kv=None):
@@ -514,33 +518,19 @@ def generate_batch_on_device(model, seqs, args, tokenizer=None, seed=0, capture=
     one token for all G * nb rows -- row g * nb + j is candidate j of prompt g.
     Returns (list of G tensors [nb, len(seq_g)] without padding, scores [G, nb] fp32), on the sequences' device.
     One prompt is generate_on_device itself (the plain decoder: same launches, same bits).  weights / kv / capture / seed as there."""
-    from .decoder import SamplingDecoder
     tokenizer = tokenizer if tokenizer is not None else IdSpace()
-    _refuse_unsupported(args, weights=weights, kv=kv)
-    _refuse_fp32_kv8(model, kv)
     seqs = list(seqs)
     assert seqs and all(seq.dim() == 1 for seq in seqs)
     if len(seqs) == 1:
         tokens, scores = generate_on_device(model, seqs[0], args, tokenizer=tokenizer, seed=seed, capture=capture, weights=weights, kv=kv)
         return [tokens], scores.view(1, -1)
-    _refuse_fp32_ragged(model)
-    plan = plan_device_batch([seq.tolist() for seq in seqs], tokenizer, _unwrap(model).word_embeddings.weight.shape[0])
-    P, run, nb, rows = plan["P"], plan["run"], plan["nb"], plan["rows"]
-    dec = SamplingDecoder(model, batch=rows, capacity=plan["capacity"], ragged=True, **_decoder_formats(weights, kv))
-    dev = dec.tok.device
-    tokens, position_ids = _batch_inputs(seqs, plan, dev)
-    out = torch.empty((rows, run), dtype=torch.long, device=dev)
-    dec.enable_sampling(args.temperature, args.top_k, args.top_p, plan["allow"], seed, out_tokens=out, out_base=P)
-    with torch.no_grad():
-        dec.start_ragged(tokens, position_ids, plan["pads"])
-        if run > 1:
-            if capture:
-                dec.capture()
-            dec.generate(run - 1)
-    return _batch_rows(seqs, plan, out, 0), dec.scores.clone().view(len(seqs), nb).to(seqs[0].device)
+    drv = _DeviceRun(model, args, seed, capture, weights, kv, ragged=True)
+    plan = plan_device_batch([seq.tolist() for seq in seqs], tokenizer, drv.vocab())
+    drv.size(plan["rows"], plan["capacity"], width=plan["run"], out_base=plan["P"])
+    return _batch_run(drv, seqs, plan, args)
 
 
-class DeviceGenerator:
+class DeviceGenerator(_DeviceRun):
     """generate_batch_on_device on ONE ragged SamplingDecoder and ONE captured decode graph that are reused call after call --
     DeviceFiller's counterpart for a file of prompts (generate_samples.py:202-221): `gen = DeviceGenerator(model, args, rows=8);
     tokens, scores = gen(seqs)` for any prompt set with G * nb == rows and P + run <= capacity.  What changes from call to call
@@ -550,58 +540,33 @@ class DeviceGenerator:
     A single prompt (G = 1) runs on the same ragged decoder with first = 0.  capture / weights / kv as generate_on_device's."""
 
     def __init__(self, model, args, rows, capacity=1152, seed=0, capture=True, weights=None, kv=None):
-        _refuse_unsupported(args, weights=weights, kv=kv)
-        _refuse_fp32_kv8(model, kv)
-        _refuse_fp32_ragged(model)
-        if not 0 < capacity <= 4096:
-            raise ValueError(f"capacity {capacity} outside (0, 4096]: the decode cache's limit")
+        super().__init__(model, args, seed, capture, weights, kv, ragged=True)
+        self.size(rows, capacity)
         if rows < 1:
             raise ValueError(f"rows = {rows} must be positive")
-        self.model, self.rows, self.capacity, self.seed, self.capture = model, int(rows), int(capacity), int(seed), capture
-        self.weights, self.kv, self.args = weights, kv, args
-        self.dec, self.key, self.out = None, None, None
+        self.rows, self.args = self.batch, args
 
-    def _decoder(self, args, allow):
-        from .decoder import SamplingDecoder
-        if self.dec is None:
-            self.dec = SamplingDecoder(self.model, batch=self.rows, capacity=self.capacity, ragged=True, **_decoder_formats(self.weights, self.kv))
-            self.out = torch.zeros((self.rows, self.capacity), dtype=torch.long, device=self.dec.tok.device)
-        key = (float(args.temperature), int(args.top_k), float(args.top_p), tuple(allow))
-        if key != self.key:
-            offset = self.dec.offset.clone() if self.key is not None else None
-            self.dec.enable_sampling(*key[:3], allow=allow, seed=self.seed, out_tokens=self.out, out_base=0)
-            if offset is not None:
-                self.dec.offset.copy_(offset)
-            self.dec.graph, self.key = None, key
-        return self.dec
+    def _buffers(self, dev):
+        self.out = torch.zeros((self.rows, self.capacity), dtype=torch.long, device=dev)
 
     def __call__(self, seqs, args=None, tokenizer=None):
         """seqs: list of 1-D tensors (generate_batch_on_device's); args: the sampling arguments of this call (default: the
         constructor's).  Returns (list of [nb, len(seq_g)] token tensors, scores [G, nb] fp32)."""
         args = args if args is not None else self.args
-        _refuse_unsupported(args)
+        decoder.refuse_unsupported(args=args, use="filling_sequence")
         tokenizer = tokenizer if tokenizer is not None else IdSpace()
         seqs = list(seqs)
         assert seqs and all(seq.dim() == 1 for seq in seqs)
-        plan = plan_device_batch([seq.tolist() for seq in seqs], tokenizer, _unwrap(self.model).word_embeddings.weight.shape[0])
-        P, run, nb = plan["P"], plan["run"], plan["nb"]
+        plan = plan_device_batch([seq.tolist() for seq in seqs], tokenizer, self.vocab())
         if plan["rows"] != self.rows:
-            raise ValueError(f"{len(seqs)} prompts x {nb} rows = {plan['rows']} rows: this generator was built for {self.rows}")
-        if P + run > self.capacity:
-            raise NotImplementedError(f"{P + run} positions exceed this generator's {self.capacity} decode slots: use "
+            raise ValueError(f"{len(seqs)} prompts x {plan['nb']} rows = {plan['rows']} rows: this generator was built for {self.rows}")
+        if plan["P"] + plan["run"] > self.capacity:
+            raise NotImplementedError(f"{plan['P'] + plan['run']} positions exceed this generator's {self.capacity} decode slots: use "
                                       f"generate_on_device or a larger capacity")
-        dec = self._decoder(args, plan["allow"])
-        tokens, position_ids = _batch_inputs(seqs, plan, dec.tok.device)
-        with torch.no_grad():
-            dec.start_ragged(tokens, position_ids, plan["pads"])
-            if run > 1:
-                if self.capture and dec.graph is None:
-                    dec.capture()
-                dec.generate(run - 1)
-        return _batch_rows(seqs, plan, self.out, P), dec.scores.clone().view(len(seqs), nb).to(seqs[0].device)
+        return _batch_run(self, seqs, plan, args)
 
 
-class DeviceFiller:
+class DeviceFiller(_DeviceRun):
     """filling_sequence for nb = 1 on ONE captured decode graph that is reused call after call: magnify's sequence filler
     (`magnify(model, tokenizer, code, text, args, fill=DeviceFiller(model, args))`, super-resolution).  Per call: the given
     table goes to the device, the context is prefilled (one eager model call) and its last logits draw the first mark, then
@@ -618,34 +583,18 @@ class DeviceFiller:
     `weights`), made when the first call builds the decoder.  kv="e4m3": 8-bit key/value caches (GraphDecoder's `kv`)."""
 
     def __init__(self, model, args, seed=0, capacity=1408, capture=True, weights=None, kv=None):
-        _refuse_unsupported(args, weights=weights, kv=kv)
-        _refuse_fp32_kv8(model, kv)
-        if not 0 < capacity <= 4096:
-            raise ValueError(f"capacity {capacity} outside (0, 4096]: the decode cache's limit")
-        self.model, self.seed, self.capacity, self.capture = model, int(seed), int(capacity), capture
-        self.weights, self.kv = weights, kv
-        self.dec, self.key, self.scores = None, None, None
+        super().__init__(model, args, seed, capture, weights, kv)
+        self.size(1, capacity)
+        self.scores = None
 
-    def _decoder(self, args, allow):
-        from .decoder import SamplingDecoder
-        if self.dec is None:
-            self.dec = SamplingDecoder(self.model, batch=1, capacity=self.capacity, **_decoder_formats(self.weights, self.kv))
-            dev = self.dec.tok.device
-            self.out = torch.empty((1, self.capacity), dtype=torch.long, device=dev)
-            self.given = torch.full((self.capacity,), -1, dtype=torch.long, device=dev)
-        key = (float(args.temperature), int(args.top_k), float(args.top_p), tuple(allow))
-        if key != self.key:
-            offset = self.dec.offset.clone() if self.key is not None else None
-            self.dec.enable_sampling(*key[:3], allow=allow, seed=self.seed, out_tokens=self.out, out_base=0, given=self.given)
-            if offset is not None:
-                self.dec.offset.copy_(offset)
-            self.dec.graph, self.key = None, key
-        return self.dec
+    def _buffers(self, dev):
+        super()._buffers(dev)
+        self.given = torch.full((self.capacity,), -1, dtype=torch.long, device=dev)
 
     def __call__(self, model, seq, args, invalid_slices=None, tokenizer=None):
         """filling_sequence's signature and result: the completed row [1, len(seq)] on seq's device.  invalid_slices is
         ignored in favour of the marker rule, as filling_sequence ignores it."""
-        _refuse_unsupported(args)
+        decoder.refuse_unsupported(args=args, use="filling_sequence")
         if model is not self.model:
             raise ValueError("this DeviceFiller was built for another model")
         assert seq.dim() == 1
@@ -654,21 +603,15 @@ class DeviceFiller:
                                       f"filling_sequence or a larger capacity")
         tokenizer = tokenizer if tokenizer is not None else IdSpace()
         seq_l = seq.tolist()
-        plan = plan_device_fill(seq_l, tokenizer, _unwrap(model).word_embeddings.weight.shape[0])
+        plan = plan_device_fill(seq_l, tokenizer, self.vocab())
         n, replays = plan["context"], plan["replays"]
-        dec = self._decoder(args, plan["allow"])
+        dec = self.arm(args, plan["allow"])
         tokens, attention_mask, position_ids = get_batch(seq[:n], dec.tok.device, args)
         position_ids[position_ids > plan["offset"]] -= plan["offset"]
         table = torch.full((self.capacity,), -1, dtype=torch.long)
         table[:len(seq_l)] = torch.tensor(plan["given"], dtype=torch.long)
-        dec.given.copy_(table)                        # before start(): its draw reads the entry of position n (-1)
-        with torch.no_grad():
-            dec.start(tokens, position_ids, attention_mask)
-            if replays:
-                if self.capture and dec.graph is None:
-                    dec.capture()
-                dec.generate(replays)
+        self.given.copy_(table)                       # before start(): its draw reads the entry of position n (-1)
+        self.scores = self.run(replays, tokens, position_ids, attention_mask)
         out = seq.clone()
         out[n:n + replays + 1] = self.out[0, n:n + replays + 1].to(seq.device)
-        self.scores = dec.scores.clone()
         return out.unsqueeze(0)

@@ -114,6 +114,15 @@ class StaticKVSlot(KVCacheSlot):
         super().__init__(None, 0)
         self.cache, self.pos_index, self.table, self.first = cache, pos_index, table, first
 
+    @property
+    def capacity(self):
+        return self.cache.shape[1]
+
+    def load(self, kv, slot0=0):
+        """kv [1 or b, n, 2 * hp] (keys | values of a prefill) -> slots [slot0, slot0 + n) of every cache row."""
+        assert kv.shape[0] in (1, self.cache.shape[0])
+        self.cache[:, slot0:slot0 + kv.shape[1]].copy_(kv)
+
     def append(self, k_new, v_new):
         hp = k_new.shape[-1]
         self.cache.index_copy_(1, self.pos_index, torch.cat((k_new, v_new), -1))

@@ -144,6 +144,23 @@ def test_device_generator_reuse(golden_dir):
     assert torch.equal(scores, want_scores)
 
 
+def test_device_generator_rearm(golden_dir):
+    """a sampled call on [C, C], then a greedy one on [B, A] through the same generator: other sampler values re-arm the sampler and
+    capture again while a graph exists, and give what a fresh decoder gives (top_k = 1: the draws do not depend on the generator
+    offset the re-arm keeps)"""
+    z, c, ids, model = _golden(golden_dir)
+    a, b, cc = _prompts(z, c, 1)
+    gen = DeviceGenerator(model, _sampled(), rows=2, capacity=64)
+    gen([cc.clone(), cc.clone()], tokenizer=ids)
+    graph = gen.dec.graph
+    assert graph is not None
+    outs, scores = gen([b.clone(), a.clone()], args=_greedy(), tokenizer=ids)
+    assert gen.dec.graph is not None and gen.dec.graph is not graph
+    want, want_scores = generate_batch_on_device(model, [b.clone(), a.clone()], _greedy(), tokenizer=ids)
+    assert all(torch.equal(o, w) for o, w in zip(outs, want)), ([o.tolist() for o in outs], [w.tolist() for w in want])
+    assert torch.equal(scores, want_scores)
+
+
 def test_single_prompt_is_generate_on_device(golden_dir):
     z, c, ids, model = _golden(golden_dir)
     a = _prompts(z, c, 4)[0]

@@ -177,6 +177,25 @@ def test_reused_filler_equals_a_fresh_one(golden_dir, monkeypatch, form):
     assert torch.equal(a, b)
 
 
+def test_filler_rearm(golden_dir):
+    """a sampled window, then a greedy one through the same filler: other sampler values re-arm the sampler and capture again
+    while a graph exists, and give what a fresh greedy filler gives (top_k = 1: the draws do not depend on the generator offset
+    the re-arm keeps)"""
+    z, c, ids, model = _toy(golden_dir)
+    first, second = _window(z, c, ids, lines=2, given_lines=1, seed=5), _window(z, c, ids, lines=2, given_lines=1, seed=6)
+    assert first.numel() == 331
+    sampled = _args(top_k=200, temperature=1.02)
+    reused = DeviceFiller(model, sampled, capacity=384)
+    reused(model, first.clone(), sampled, tokenizer=ids)
+    graph = reused.dec.graph
+    assert graph is not None
+    a = reused(model, second.clone(), _args(), tokenizer=ids)
+    assert reused.dec.graph is not None and reused.dec.graph is not graph
+    fresh = DeviceFiller(model, _args(), capacity=384)
+    b = fresh(model, second.clone(), _args(), tokenizer=ids)
+    assert torch.equal(a, b) and torch.equal(reused.scores, fresh.scores)
+
+
 def test_magnify_on_the_device(golden_dir):
     z, c, ids, model = _toy(golden_dir)
     n_img = c["img_tokens"]

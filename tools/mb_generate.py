@@ -13,7 +13,8 @@ of the weights (generate_on_device / DeviceFiller `weights=`), timed next to the
 8-bit key/value cache (`kv=`), alone or together with `--weights`.
 `--prompts G [--nb N]` (comma lists run several settings in one process: `--prompts 8,2 --nb 1,4`): G prompts of different text
 lengths x N candidates each (default 1) for one 1024-code image per row, on ONE decode graph (generate_batch_on_device) against
-the same prompts through generate_on_device one after another, in the same process; ms per generated token per prompt for each."""
+the same prompts through generate_on_device one after another, in the same process; ms per generated token per prompt for each.
+MB_GENERATE_SKIP_HOST=1 leaves out the filling_sequence legs (a parent-against-head comparison of the device forms)."""
 import os, sys, time, types
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -43,6 +44,7 @@ from cogview_amd.model import GPT2Model
 mpu.initialize_model_parallel(1); torch.manual_seed(1); mpu.model_parallel_cuda_manual_seed(1)
 L, h, heads, V = 48, 2560, 40, 58240
 SR = "--super-resolution" in sys.argv
+SKIP_HOST = os.environ.get("MB_GENERATE_SKIP_HOST") == "1"
 W8 = sys.argv[sys.argv.index("--weights") + 1] if "--weights" in sys.argv else None
 KV8 = sys.argv[sys.argv.index("--kv") + 1] if "--kv" in sys.argv else None
 ids = IdSpace()
@@ -67,8 +69,8 @@ if SR:
     big_dev = magnify(model, ids, code, text_t, args, fill=fill)
     torch.cuda.synchronize(); t_dev = time.time() - t0
     torch.cuda.synchronize(); t0 = time.time()
-    big_host = magnify(model, ids, code, text_t, args)
-    torch.cuda.synchronize(); t_host = time.time() - t0
+    big_host = big_dev if SKIP_HOST else magnify(model, ids, code, text_t, args)
+    torch.cuda.synchronize(); t_host = float("nan") if SKIP_HOST else time.time() - t0
     assert big_dev.shape == big_host.shape == (1, 4096) and int(big_dev.max()) < 8192 and int(big_host.max()) < 8192
     plans = [plan_device_fill(s, ids, V) for s in seqs]
     replays = sum(p["replays"] for p in plans)
@@ -160,8 +162,8 @@ for nb in (1, 8):
     torch.cuda.synchronize(); t_dev = time.time() - t0
     assert int(out[:, -1024:].max()) < 8192 and torch.isfinite(scores).all()
     torch.cuda.synchronize(); t0 = time.time()
-    ref = filling_sequence(model, seq.clone(), args)
-    torch.cuda.synchronize(); t_host = time.time() - t0
+    ref = out if SKIP_HOST else filling_sequence(model, seq.clone(), args)
+    torch.cuda.synchronize(); t_host = float("nan") if SKIP_HOST else time.time() - t0
     assert ref.shape == out.shape
     print(f"batch {nb}: generate_on_device {t_dev:.2f} s = {t_dev / 1024 * 1e3:.2f} ms/token (prefill + capture included); "
           f"filling_sequence kv_cache=True {t_host:.2f} s = {t_host / 1024 * 1e3:.2f} ms/token; speed-up {t_host / t_dev:.1f}x",
