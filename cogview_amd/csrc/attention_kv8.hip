@@ -1,20 +1,14 @@
 // Decode step on an 8-bit key/value cache (cogv_kv_quantize_e4m3, cogv_attention_decode_kv8; generation/decoder.py kv="e4m3").
 // The decode attention of attention.hip requests every slot of the fixed-capacity cache on every step, so a step streams the
 // whole cache: here the cache holds OCP E4M3 bytes ("e4m3fn": no infinities, largest value 448) with one fp32 scale per
-// (slot, head, K | V) -- the rule of quantize.hip applied to the 64 elements of one head of one slot:
-//     scale = max |x| / 448   (fp32 division; 1.0 when the 64 elements are all zero)
-//     q     = rne_e4m3( float(x) / scale )                    (a true fp32 division: a CPU reproduces the bytes)
+// (slot, head, K | V) -- the rule of e4m3_stream.cuh with the 64 elements of one head of one slot as the group.
 // Head-major layout, so that the 128 keys of one split are one contiguous 8-KB block:
 //     q     uint8 [B][2][H][capacity][64]      plane 0: keys, plane 1: values
 //     scale fp32  [B][2][H][capacity]
 // 136 bytes per (slot, head) for its key and value instead of 256.  This unit is separate from attention.hip: the 16-bit kernels compile what
 // they always did; the second launch (combine) is attention.hip's, reached through cogv_attn_decode_combine_launch.
-#include "common.cuh"
+#include "e4m3_stream.cuh"
 #include "cogview_hip.h"
-
-#ifndef COGV_DECODE_NT
-#define COGV_DECODE_NT 1
-#endif
 
 // attention.hip: the combine launch of a decode step (partials in split order -> out)
 extern "C" __attribute__((visibility("hidden"))) int cogv_attn_decode_combine_launch(int dtype, const void* ws, void* out, long long out_bs,
@@ -23,14 +17,6 @@ extern "C" __attribute__((visibility("hidden"))) int cogv_attn_decode_combine_la
 namespace {
 
 constexpr int HD = 64;
-
-template <typename V> __device__ __forceinline__ V ld_stream(const V* p) {
-#if COGV_DECODE_NT
-  return __builtin_nontemporal_load(p);          // streamed once per step (gemm_shared.cuh: COGV_DECODE_NT)
-#else
-  return *p;
-#endif
-}
 
 // The 16 elements one lane holds of a head's 64 (two 16-byte words of the 16-bit type), the head spread over 4 adjacent lanes:
 // scale of the head and this lane's 16 E4M3 bytes.  Same operations, in the same order per element, as quantize_rows_e4m3_kernel.
@@ -41,7 +27,7 @@ __device__ __forceinline__ u32x4 quantize_head16(const u32x4& a, const u32x4& b,
   m = max(m, (uint32_t)__shfl_xor((int)m, 1, 64));
   m = max(m, (uint32_t)__shfl_xor((int)m, 2, 64));
   const float amax = bits_to_f<T>((uint16_t)m);
-  const float s = amax == 0.f ? 1.0f : amax / 448.0f;
+  const float s = e4m3_scale(amax);
   scale = s;
   float f[16];
   unpack8<T>(a, f);
@@ -50,22 +36,8 @@ __device__ __forceinline__ u32x4 quantize_head16(const u32x4& a, const u32x4& b,
   for (int i = 0; i < 16; ++i) f[i] = f[i] / s;
   u32x4 q;
 #pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    int x = 0;
-    x = __builtin_amdgcn_cvt_pk_fp8_f32(f[4 * w], f[4 * w + 1], x, false);
-    x = __builtin_amdgcn_cvt_pk_fp8_f32(f[4 * w + 2], f[4 * w + 3], x, true);
-    q[w] = (uint32_t)x;
-  }
+  for (int w = 0; w < 4; ++w) q[w] = pack4_e4m3(f[4 * w], f[4 * w + 1], f[4 * w + 2], f[4 * w + 3]);
   return q;
-}
-
-// 16 E4M3 bytes -> 16 floats, exact (v_cvt_pk_f32_fp8)
-__device__ __forceinline__ void unpack16_e4m3(const u32x4& q, float* f) {
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    const f32x2_t lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)q[w], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)q[w], true);
-    f[4 * w] = lo[0]; f[4 * w + 1] = lo[1]; f[4 * w + 2] = hi[0]; f[4 * w + 3] = hi[1];
-  }
 }
 
 // ---------------------------------------------------------------------------------------------------- cache quantizer
@@ -141,10 +113,10 @@ __global__ __launch_bounds__(256) void attn_decode_kv8_kernel(const DecodeKv8Arg
     // requested whatever *pos says (slots past it hold stale or no data and are replaced below; a key past the capacity re-reads
     // the last row): loads that waited for the position would start one memory latency late
     const int krow = key < p.cap ? key : p.cap - 1;
-    kc[ps] = ld_stream(reinterpret_cast<const u32x4*>(kq + (size_t)krow * HD));
-    vc[ps] = ld_stream(reinterpret_cast<const u32x4*>(kq + (plane + krow) * HD));
-    ksc[ps] = ld_stream(reinterpret_cast<const uint32_t*>(ks + krow));
-    vsc[ps] = ld_stream(reinterpret_cast<const uint32_t*>(ks + plane + krow));
+    kc[ps] = ld_stream<u32x4>(kq + (size_t)krow * HD);
+    vc[ps] = ld_stream<u32x4>(kq + (plane + krow) * HD);
+    ksc[ps] = ld_stream<uint32_t>(ks + krow);
+    vsc[ps] = ld_stream<uint32_t>(ks + plane + krow);
   }
   // (the scheduler otherwise sinks the 16-byte loads below the quantization, behind the wait for the qkv row)
   __builtin_amdgcn_sched_barrier(0);

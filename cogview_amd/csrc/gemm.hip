@@ -342,7 +342,7 @@ extern "C" int cogv_gemm(const cogv_gemm_desc* d, void* stream) {
   return launch_tiles(d->dtype, &pl, 1, env, ga, reinterpret_cast<hipStream_t>(stream));
 }
 
-// ---- the skinny-M products with a prologue, and all three on an 8-bit weight operand (gemv.hip, FormV8 / FormM8: it travels in
+// ---- the skinny-M products with a prologue, and all three on an 8-bit weight operand (gemv.hip, FormV / FormM on W8: it travels in
 //      the argument block as B / ldb / wscale; no first-generation kernel stands behind those)
 
 // the descriptor with the 8-bit operand in B's place -> argument block; `allowed`: the epilogue flags the product takes

@@ -4,6 +4,7 @@
 // with a const void* to these structs, as the generation-4 units do.
 #pragma once
 #include "common.cuh"
+#include "e4m3_stream.cuh"
 #include "cogview_hip.h"
 
 namespace {
@@ -25,7 +26,7 @@ struct GemmArgs {
   float* colsum_ws;     // COGV_EPI_COLSUM partial sums [2 * tiles_m(256)][N] fp32
   union {               // (one slot: the skinny-M products never split K, so the layout of the block stays what it was)
     float* ws;            // split-K slabs [S][M][N] fp32
-    const float* wscale;  // 8-bit weight operand (gemv.hip, FormV8 / FormM8): B is uint8 E4M3 [N][ldb], wscale [N] its row scales
+    const float* wscale;  // 8-bit weight operand (gemv.hip, W8): B is uint8 E4M3 [N][ldb], wscale [N] its row scales
   };
   int splitk;
   int ktiles_per_split;
@@ -37,25 +38,9 @@ struct GemmArgs {
 //      the hot combinations to such instances so that one item's epilogue is a few KB of code, not all paths).
 // 16-byte accesses through EXPLICIT global-address-space pointers: the epilogues take their pointers from a descriptor
 // copy pinned in scalar registers (pp64_epilogue), which hides the pointers' origin from address-space inference --
-// a generic pointer would compile to flat_load / flat_store, which also count on the LDS counter
-#define COGV_GLOBAL __attribute__((address_space(1)))
+// a generic pointer would compile to flat_load / flat_store, which also count on the LDS counter (COGV_GLOBAL: e4m3_stream.cuh)
 __device__ __forceinline__ u32x4 gload16(const void* q) { return *(const COGV_GLOBAL u32x4*)q; }
-// streamed-once data (the weight rows of a decode step: every byte is read by ONE workgroup, once per token): the non-temporal
-// policy (global_load_dwordx4 ... nt) keeps the stream from displacing the step's small reused vectors in the caches.  Measured
-// in the captured 4B decode step (profiles/r05_decode_nt_ab.log): one row (FormV, a wave streams whole weight rows) 2.78 -> 2.69
-// ms per token; 2 / 4 rows (FormM: the 16 lanes of a 16 x 16 fragment read 16 different rows, 16 bytes each per step) 3.06 ->
-// 3.50 and 3.74 -> 4.23 ms -- so FormV and the decode attention's cache rows take it, FormM keeps the default policy.
-// COGV_DECODE_NT=0 builds default-policy loads everywhere.
-#ifndef COGV_DECODE_NT
-#define COGV_DECODE_NT 1
-#endif
-__device__ __forceinline__ u32x4 gload16_stream(const void* q) {
-#if COGV_DECODE_NT
-  return __builtin_nontemporal_load((const COGV_GLOBAL u32x4*)q);
-#else
-  return *(const COGV_GLOBAL u32x4*)q;
-#endif
-}
+// (the streamed loads of the decode step: ld_stream, e4m3_stream.cuh)
 // the aux operand of the stored-tensor epilogues (MULAUX / DGELU: [M][N], every element read exactly once per launch): non-temporal,
 // so that the 535-MB stream of the 4B dGeLU-side dgrad does not take L2 lines from the operand panels -- 1107 -> 1090 us in
 // alternating processes (profiles/r06_gemm_aux_nt_probe.log).  What the aux read costs beyond that is its memory side: with an

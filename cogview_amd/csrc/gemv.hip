@@ -27,16 +27,18 @@
 // The three kernels use the same association for the same K, so the combine-prologue form and the two-launch form of the
 // attention-output projection still agree bit for bit (tests/test_kernels_gpu.py).
 //
-// 8-BIT WEIGHTS (FormV8 / FormM8: B as OCP E4M3 bytes with one fp32 scale per row, cogv_quantize_rows_e4m3).  The decode step is
-// a weight stream, so half the bytes is the lever that is left: the same three kernels, instantiated on two more forms -- the
-// prologues do not know what a weight is.  The bytes are converted in registers (v_cvt_pk_f32_fp8, exact), the arithmetic and
-// every rounding point stay those of the 16-bit form, and the fp32 sum of column n is multiplied by scale[n] once, in front
-// of the shared epilogue.  A slot of the same shape holds half the bytes, so the class table changes to keep 16-20 KB in flight
-// per wave: FormV8 gives a wave twice the columns (8-byte slots: a lane keeps FormV's 8 contraction elements), FormM8 gives a
-// 16-column tile half the waves (a 16-byte load is two MFMA fragments).  The classes of both formats: gemv_plan.h.
+// THE WEIGHT OPERAND.  FormV and FormM are written once and take what B holds as a type parameter: W16 (the dtype's 16 bits) or W8
+// (OCP E4M3 bytes with one fp32 scale per row, cogv_quantize_rows_e4m3; the format: e4m3_stream.cuh).  The decode step is a
+// weight stream, so half the bytes is the lever that is left: the same three kernels on the same two forms -- the prologues do
+// not know what a weight is.  The bytes are converted in registers (v_cvt_pk_f32_fp8, exact), the arithmetic and every rounding
+// point stay those of the 16-bit operand, and the fp32 sum of column n is multiplied by scale[n] once, in front of the shared
+// epilogue.  A slot of the same shape holds half the bytes, so the class table changes to keep 16-20 KB in flight per wave: FormV
+// on W8 gives a wave twice the columns (8-byte slots: a lane keeps its 8 contraction elements), FormM on W8 gives a 16-column
+// tile half the waves (a 16-byte load is two MFMA fragments).  The classes of both formats: gemv_plan.h.
 //
-// Compiled as two translation units (-DCOGV_GEMV_TU=0: bf16, 1: fp16; build.py) for the 16-bit forms and two more with
-// -DCOGV_GEMV_W8 for the 8-bit forms; without the macro this file is empty.
+// Compiled as two translation units (-DCOGV_GEMV_TU=0: bf16, 1: fp16; build.py) for the 16-bit operand and two more with
+// -DCOGV_GEMV_W8 for the 8-bit operand; without the macro this file is empty.  The merge of the forms left the device code of
+// all four units what it was (tools/device_code_diff.py, profiles/r16_gemv_forms_parent_vs_head.log).
 #include "gemm_shared.cuh"
 #include "gemv_plan.h"
 
@@ -67,29 +69,96 @@ __device__ __forceinline__ u32x4 gv2_bias(const GemmArgs& p, int n) {
 }
 
 // =====================================================================================================================
+// The weight operand of a form: what B's rows hold and how a load of them becomes arithmetic.  Nothing else of a form depends
+// on the format.
+//   T, Elem, Slot       the dtype of x and C; a row element of B; what one lane loads per FormV slot (its 8 contraction elements)
+//   load, unpack        a FormV slot from memory (streamed: e4m3_stream.cuh), and as 8 floats
+//   KL, FR, frag        FormM: contraction elements of the 16 rows x 16 bytes one load covers, the MFMA fragments that is, and
+//                       fragment f of a load as the A operand
+//   Scale, scale        what a finishing lane requests for its 8 columns n + 8g .. + 7, behind the weights and far ahead of the tail.
+//                       (n and g apart: W16 asks for nothing, and a column computed at the call only to be dropped moved the
+//                       compares and branches of every 16-bit FormV kernel)
+//   Factors, factors, mul   the same as the 8 factors of the column sums, built once in front of the row loop, and the multiply
+template <typename T_>
+struct W16 {
+  typedef T_ T;
+  typedef T_ Elem;
+  typedef u32x4 Slot;
+  static constexpr int KL = 32, FR = 1;
+  struct Scale {};
+  static __device__ __forceinline__ Slot load(const Elem* q) { return ld_stream<u32x4>(q); }
+  static __device__ __forceinline__ void unpack(const Slot& w, float* f) { unpack8<T>(w, f); }
+  static __device__ __forceinline__ typename HT<T>::v8 frag(const u32x4& w, int) { return __builtin_bit_cast(typename HT<T>::v8, w); }
+  typedef Scale Factors;
+  static __device__ __forceinline__ Scale scale(const GemmArgs&, int, int) { return Scale{}; }
+  static __device__ __forceinline__ Factors factors(const Scale&) { return Factors{}; }
+  static __device__ __forceinline__ float mul(float x, const Factors&, int) { return x; }
+};
+
+// 8-bit weights (see the file header): B is uint8 OCP E4M3 [N][ldb], p.wscale [N] fp32.
+// the row scales of the 8 columns n .. n + 7 a finishing lane multiplies its sums by: requested BEHIND the weights (the memory
+// counter retires in order: they arrive right after the last weight, long before the sums are complete).  Unconditional, with a
+// clamped column, for gv2_bias's reason.
+struct Scale8 { f32x4 a, b; };
+__device__ __forceinline__ Scale8 gv2_scale(const GemmArgs& p, int n) {
+  const float* s = p.wscale + (n < p.N ? n : p.N - 8) + gv2_vzero();
+  return Scale8{*(const COGV_GLOBAL f32x4*)s, *(const COGV_GLOBAL f32x4*)(s + 4)};
+}
+// A FormV slot is 8 BYTES = the same 8 contraction elements of a column as a 16-bit slot, so the x side, the fmaf chain and its
+// order do not change; a slot is half as many bytes, so a wave owns twice as many columns (J).  A FormM load holds 16
+// contraction elements of its row: TWO fragments -- lane l supplies row (l & 15), elements 16 (l >> 4) .. + 15 of the load's
+// 64-element block, the first 8 to one v_mfma_f32_16x16x32 and the last 8 to the next, and the x operand of each takes the same 8
+// elements of its row from LDS (a contraction is a sum over all slots: any slot-to-lane mapping serves as long as both operands
+// use it).  E4M3 -> T is exact (fp16 and bf16 hold every E4M3 value), through fp32 in registers.
+template <typename T_>
+struct W8 {
+  typedef T_ T;
+  typedef uint8_t Elem;
+  typedef u32x2 Slot;
+  static constexpr int KL = 64, FR = 2;
+  typedef Scale8 Scale;
+  static __device__ __forceinline__ Slot load(const Elem* q) { return ld_stream<u32x2>(q); }
+  static __device__ __forceinline__ void unpack(const Slot& w, float* f) { unpack8_e4m3(w[0], w[1], f); }
+  static __device__ __forceinline__ typename HT<T>::v8 frag(const u32x4& w, int f) {
+    float x[8];
+    unpack8_e4m3(w[2 * f], w[2 * f + 1], x);
+    return __builtin_bit_cast(typename HT<T>::v8, pack8<T>(x));
+  }
+  static __device__ __forceinline__ Scale scale(const GemmArgs& p, int n, int g) { return gv2_scale(p, n + g * 8); }
+  struct Factors { float s[8]; };
+  static __device__ __forceinline__ Factors factors(const Scale& sc) { return Factors{{sc.a[0], sc.a[1], sc.a[2], sc.a[3], sc.b[0], sc.b[1], sc.b[2], sc.b[3]}}; }
+  static __device__ __forceinline__ float mul(float x, const Factors& f, int i) { return x * f.s[i]; }      // the row scale, once, in front of the shared epilogue
+};
+
+// =====================================================================================================================
 // FormV: one row (MT = 1; the row-count template parameter is kept general).  A wave owns J whole columns.
-template <typename T, int J, int KCMAX, bool GUARD_, int MT, int NW_>
+template <typename W, int J, int KCMAX, bool GUARD_, int MT, int NW_>
 struct FormV {
+  typedef typename W::T T;
   static constexpr int NW = NW_, COLS = NW_ * J, XPAD = 0, NS = KCMAX * J, XCHUNKS = KCMAX;
+  // NG groups of 8 columns, finished by lanes 0 .. GPW - 1 of every wave (J <= 8: GPW = 1, lane 0 of the first NG waves)
+  static constexpr int NG = (NW_ * J) / 8, GPW = (NG + NW_ - 1) / NW_;
   static constexpr bool GUARD = GUARD_;
-  struct Regs { u32x4 w[NS]; };
+  struct Regs { typename W::Slot w[NS]; };
   struct Shared { float outp[MT][NW_ * J]; };
   // slot s of a wave = (chunk c = s / J, column j = s % J): chunk-major, the order the dot products consume them.  Columns
   // past N (a wave at the ragged end of the matrix) re-read the last row; their results are never stored.
   template <int S0, int S1>
   static __device__ __forceinline__ void issue(Regs& r, const GemmArgs& p, int n0, int K, int wave, int lane) {
-    const T* B = reinterpret_cast<const T*>(p.B);
+    const typename W::Elem* B = reinterpret_cast<const typename W::Elem*>(p.B);
     const int nw = n0 + wave * J, kc = K >> 9;
 #pragma unroll
     for (int s = S0; s < S1; ++s) {
       const int c = s / J, j = s % J;
       const int n = nw + j < p.N ? nw + j : p.N - 1;
-      if (!GUARD || c < kc) r.w[s] = gload16_stream(B + (size_t)n * p.ldb + c * 512 + lane * 8);
+      if (!GUARD || c < kc) r.w[s] = W::load(B + (size_t)n * p.ldb + c * 512 + lane * 8);
     }
   }
-  static __device__ __forceinline__ u32x4 bias(const GemmArgs& p, int n0, int wave, int lane) { return gv2_bias<T>(p, n0 + wave * 8); }
+  // the group of 8 columns this lane finishes (lanes < GPW)
+  static __device__ __forceinline__ int group(int wave, int lane) { return wave * GPW + (lane < GPW ? lane : 0); }
+  static __device__ __forceinline__ u32x4 bias(const GemmArgs& p, int n0, int wave, int lane) { return gv2_bias<T>(p, n0 + group(wave, lane) * 8); }
   // acc[m][j] += sum over this lane's 8 elements of every chunk (ascending): x rows from LDS, 16 bytes per lane and row; then
-  // one DPP wave sum per (row, column), LDS, and lane 0 of wave g runs the fused epilogue on columns n0 + 8g .. + 7.
+  // one DPP wave sum per (row, column), LDS, and the finishing lane of group g runs the fused epilogue on columns n0 + 8g .. + 7.
   // The tail of these launches is a chain of dependent latencies on one lane, so the bias it needs is requested ahead.  A
   // requested abs-max (COGV_EPI_ABSMAX) still costs the tail a memory-side read + atomic per finishing lane; the decode chain
   // does not ask for it any more (cogv_ln_prologue.z_absmax = NULL).  Measured with one returning-nothing atomic per lane
@@ -98,6 +167,8 @@ struct FormV {
   static __device__ __forceinline__ void product(const Regs& r, const GemmArgs& p, const T* xs, int XS, int K, Shared& sh, int n0, int wave,
                                                  int lane, const u32x4& bias_pre) {
     const int kc = K >> 9;
+    const int g = group(wave, lane);
+    const typename W::Scale sc = W::scale(p, n0, g);
     float acc[MT][J];
 #pragma unroll
     for (int m = 0; m < MT; ++m)
@@ -112,7 +183,7 @@ struct FormV {
 #pragma unroll
         for (int j = 0; j < J; ++j) {
           float wf[8];
-          unpack8<T>(r.w[c * J + j], wf);
+          W::unpack(r.w[c * J + j], wf);
 #pragma unroll
           for (int m = 0; m < MT; ++m) {
             float t = acc[m][j];
@@ -131,15 +202,17 @@ struct FormV {
         if (lane == 0) sh.outp[m][wave * J + j] = t;
       }
     __syncthreads();
-    constexpr int NG = (NW_ * J) / 8;
-    if (lane == 0 && wave < NG) {
-      const int n = n0 + wave * 8;
+    // (unsigned compare: at GPW = 1 it folds to lane == 0 before the form is inlined into its kernel -- the compare the 16-bit
+    // kernels were written with; a signed "lane < 1" reaches the same code by another road and moves their compares and branches)
+    if ((unsigned)lane < (unsigned)GPW && g < NG) {
+      const int n = n0 + g * 8;
       if (n < p.N) {
+        const typename W::Factors s8 = W::factors(sc);
         uint32_t am = 0u;
         for (int m = 0; m < p.M && m < MT; ++m) {
           float v[8];
 #pragma unroll
-          for (int i = 0; i < 8; ++i) v[i] = sh.outp[m][wave * 8 + i];
+          for (int i = 0; i < 8; ++i) v[i] = W::mul(sh.outp[m][g * 8 + i], s8, i);
           am = absmax_pk(am, epilogue8<T>(p, m, n, v, &bias_pre));
         }
         if (p.flags & COGV_EPI_ABSMAX) {
@@ -153,9 +226,9 @@ struct FormV {
 
 // =====================================================================================================================
 // FormM: 2 .. 8 rows on the matrix core.  A workgroup owns TW tiles of 16 columns, NWK waves per tile: wave kw of a tile takes the
-// contraction-step PAIRS q = kw, kw + NWK, .. (steps 2q and 2q + 1: 64 consecutive elements = one 128-byte line of each of the
-// 16 weight rows), L = K / 32 / NWK loads of 16 bytes per lane, all requested at the top like FormV's slots.
-//   A operand = weights: lane l supplies row (l & 15) -> column n0 + (l & 15), contraction slots 8 (l >> 4) .. + 7 of the step
+// load PAIRS q = kw, kw + NWK, .. (loads 2q and 2q + 1 of KL contraction elements each: one 128-byte line of each of the 16
+// weight rows), L = K / KL / NWK loads of 16 bytes per lane, all requested at the top like FormV's slots.  Per fragment of a load:
+//   A operand = weights: lane l supplies row (l & 15) -> column n0 + (l & 15), 8 contraction slots of the lane's 16 bytes
 //   B operand = x:       lane l supplies column (l & 15) -> row m = l & 15 (lanes past the row count re-read the last row: those
 //                        result columns are never looked at), the same contraction slots, from LDS (rows padded by 16 bytes
 //                        so that the rows of one step fall into different banks)
@@ -164,239 +237,52 @@ struct FormV {
 // (row, half) and finished by lanes 0 .. 2M - 1 of the tile's first wave in parallel.
 // TW = 2 (eight waves, 32 columns) serves the LayerNorm-prologue kernel at 4 and 8 rows: one 8-element vector per thread and row
 // in the prologue instead of two, and half as many workgroups recomputing it.
-template <typename T, int NWK, int TW, int LMAX, bool GUARD_, int MT>
+template <typename W, int NWK, int TW, int LMAX, bool GUARD_, int MT>
 struct FormM {
-  static constexpr int NW = NWK * TW, COLS = 16 * TW, XPAD = 8, NS = LMAX, XCHUNKS = (LMAX * NWK * 32 + 511) / 512;
+  typedef typename W::T T;
+  typedef typename W::Scale Scale;
+  static constexpr int KL = W::KL, FR = W::FR;
+  static constexpr int NW = NWK * TW, COLS = 16 * TW, XPAD = 8, NS = LMAX, XCHUNKS = (LMAX * NWK * KL + 511) / 512;
   static constexpr bool GUARD = GUARD_;
   struct Regs { u32x4 w[LMAX]; };
   struct Shared { f32x4 red[NW][64]; float outp[TW][16][16]; };
   static __device__ __forceinline__ int kstep(int kw, int i) { return 2 * (kw + NWK * (i >> 1)) + (i & 1); }
   template <int S0, int S1>
   static __device__ __forceinline__ void issue(Regs& r, const GemmArgs& p, int n0, int K, int wave, int lane) {
-    const int L = K / (32 * NWK), kw = wave % NWK, nt = n0 + (wave / NWK) * 16 + (lane & 15);
+    const int L = K / (KL * NWK), kw = wave % NWK, nt = n0 + (wave / NWK) * 16 + (lane & 15);
     const int n = nt < p.N ? nt : p.N - 1;
-    const T* row = reinterpret_cast<const T*>(p.B) + (size_t)n * p.ldb + (lane >> 4) * 8;
+    const typename W::Elem* row = reinterpret_cast<const typename W::Elem*>(p.B) + (size_t)n * p.ldb + (lane >> 4) * (KL / 4);
 #pragma unroll
     for (int i = S0; i < S1; ++i)
-      if (!GUARD || i < L) r.w[i] = gload16(row + 32 * kstep(kw, i));     // (default policy: the non-temporal form measured 12-14 % SLOWER here, profiles/r05_decode_nt_ab.log)
+      if (!GUARD || i < L) r.w[i] = gload16(row + KL * kstep(kw, i));     // (default policy: the non-temporal form measured 12-14 % SLOWER here, profiles/r05_decode_nt_ab.log)
   }
   // lanes 0 .. 15 of a tile's first wave finish: lane t -> row t >> 1, columns (tile) + 8 (t & 1) ..
-  static __device__ __forceinline__ u32x4 bias(const GemmArgs& p, int n0, int wave, int lane) {
-    return gv2_bias<T>(p, n0 + (wave / NWK) * 16 + (lane & 1) * 8);
-  }
-  // steps I0 .. I1 - 1 of this wave; xs holds the x rows from contraction index kofs on
+  static __device__ __forceinline__ int col(int n0, int wave, int lane) { return n0 + (wave / NWK) * 16 + (lane & 1) * 8; }
+  static __device__ __forceinline__ u32x4 bias(const GemmArgs& p, int n0, int wave, int lane) { return gv2_bias<T>(p, col(n0, wave, lane)); }
+  // loads I0 .. I1 - 1 of this wave; xs holds the x rows from contraction index kofs on
   template <int I0, int I1>
   static __device__ __forceinline__ void accumulate(const Regs& r, const T* xs, int XS, int K, int kofs, int wave, int lane, f32x4& acc) {
     typedef typename HT<T>::v8 v8;
-    const int L = K / (32 * NWK), kw = wave % NWK;
+    const int L = K / (KL * NWK), kw = wave % NWK;
     const int mrow = (lane & 15) < MT ? (lane & 15) : MT - 1;
-    const T* xrow = xs + (size_t)mrow * XS + (lane >> 4) * 8 - kofs;
+    const T* xrow = xs + (size_t)mrow * XS + (lane >> 4) * (KL / 4) - kofs;
 #pragma unroll
     for (int i = I0; i < I1; ++i) {
       if (!GUARD || i < L) {
-        const v8 b = *reinterpret_cast<const v8*>(xrow + 32 * kstep(kw, i));
-        acc = HT<T>::mfma16(__builtin_bit_cast(v8, r.w[i]), b, acc);
+        v8 b[FR];
+#pragma unroll
+        for (int f = 0; f < FR; ++f) b[f] = *reinterpret_cast<const v8*>(xrow + KL * kstep(kw, i) + 8 * f);
+#pragma unroll
+        for (int f = 0; f < FR; ++f) acc = HT<T>::mfma16(W::frag(r.w[i], f), b[f], acc);
       }
     }
-  }
-  static __device__ __forceinline__ void finish(f32x4 acc, const GemmArgs& p, Shared& sh, int n0, int wave, int lane, const u32x4& bias_pre) {
-    const int tile = wave / NWK, kw = wave % NWK;
-    sh.red[wave][lane] = acc;
-    __syncthreads();
-    if (kw == 0) {
-      f32x4 s = sh.red[tile * NWK][lane];
-#pragma unroll
-      for (int w = 1; w < NWK; ++w) s += sh.red[tile * NWK + w][lane];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) sh.outp[tile][lane & 15][(lane >> 4) * 4 + i] = s[i];
-    }
-    __syncthreads();
-    if (kw == 0) {
-      const int m = lane >> 1, n = n0 + tile * 16 + (lane & 1) * 8;
-      uint32_t am = 0u;
-      if (m < p.M && m < MT && n < p.N) {
-        float v[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = sh.outp[tile][m][(lane & 1) * 8 + i];
-        am = epilogue8<T>(p, m, n, v, &bias_pre);
-      }
-      if (p.flags & COGV_EPI_ABSMAX) {
-        uint32_t wv = max(am & 0xffffu, am >> 16);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) wv = max(wv, (uint32_t)__shfl_xor((int)wv, o, 64));
-        if (lane == 0) atomic_max_nonneg(p.absmax, bits_to_f<T>((uint16_t)wv));
-      }
-    }
-  }
-  static __device__ __forceinline__ void product(const Regs& r, const GemmArgs& p, const T* xs, int XS, int K, Shared& sh, int n0, int wave,
-                                                 int lane, const u32x4& bias_pre) {
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    accumulate<0, LMAX>(r, xs, XS, K, 0, wave, lane, acc);
-    finish(acc, p, sh, n0, wave, lane, bias_pre);
-  }
-};
-
-// =====================================================================================================================
-// 8-bit weight operand (FormV8 / FormM8, see the file header): B is uint8 OCP E4M3 [N][ldb], p.wscale [N] fp32.
-// 8 E4M3 bytes -> 8 floats, exact (v_cvt_pk_f32_fp8: two bytes of the selected 16-bit half per instruction)
-__device__ __forceinline__ void unpack8_e4m3(uint32_t lo, uint32_t hi, float* f) {
-  const f32x2_t a = __builtin_amdgcn_cvt_pk_f32_fp8((int)lo, false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)lo, true);
-  const f32x2_t c = __builtin_amdgcn_cvt_pk_f32_fp8((int)hi, false), d = __builtin_amdgcn_cvt_pk_f32_fp8((int)hi, true);
-  f[0] = a[0]; f[1] = a[1]; f[2] = b[0]; f[3] = b[1]; f[4] = c[0]; f[5] = c[1]; f[6] = d[0]; f[7] = d[1];
-}
-__device__ __forceinline__ u32x2 gload8_stream(const void* q) {
-#if COGV_DECODE_NT
-  return __builtin_nontemporal_load((const COGV_GLOBAL u32x2*)q);
-#else
-  return *(const COGV_GLOBAL u32x2*)q;
-#endif
-}
-// the row scales of the 8 columns n .. n + 7 a finishing lane multiplies its sums by: requested BEHIND the weights (the memory
-// counter retires in order: they arrive right after the last weight, long before the sums are complete).  Unconditional, with a
-// clamped column, for gv2_bias's reason.
-struct Scale8 { f32x4 a, b; };
-__device__ __forceinline__ Scale8 gv2_scale(const GemmArgs& p, int n) {
-  const float* s = p.wscale + (n < p.N ? n : p.N - 8) + gv2_vzero();
-  return Scale8{*(const COGV_GLOBAL f32x4*)s, *(const COGV_GLOBAL f32x4*)(s + 4)};
-}
-
-// FormV8: FormV on 8-bit weights.  A lane's load is 8 BYTES = the same 8 contraction elements c * 512 + 8 lane .. + 7 of a
-// column as in FormV, so the x side, the fmaf chain and its order are FormV's; a slot is half as many bytes, so a wave owns
-// twice as many columns (J).  NW * J / 8 groups of 8 columns are finished by lanes 0 .. GPW - 1 of every wave.
-template <typename T, int J, int KCMAX, bool GUARD_, int MT, int NW_>
-struct FormV8 {
-  static constexpr int NW = NW_, COLS = NW_ * J, XPAD = 0, NS = KCMAX * J, XCHUNKS = KCMAX;
-  static constexpr int NG = (NW_ * J) / 8, GPW = (NG + NW_ - 1) / NW_;
-  static constexpr bool GUARD = GUARD_;
-  struct Regs { u32x2 w[NS]; };
-  struct Shared { float outp[MT][NW_ * J]; };
-  template <int S0, int S1>
-  static __device__ __forceinline__ void issue(Regs& r, const GemmArgs& p, int n0, int K, int wave, int lane) {
-    const uint8_t* B = reinterpret_cast<const uint8_t*>(p.B);
-    const int nw = n0 + wave * J, kc = K >> 9;
-#pragma unroll
-    for (int s = S0; s < S1; ++s) {
-      const int c = s / J, j = s % J;
-      const int n = nw + j < p.N ? nw + j : p.N - 1;
-      if (!GUARD || c < kc) r.w[s] = gload8_stream(B + (size_t)n * p.ldb + c * 512 + lane * 8);
-    }
-  }
-  static __device__ __forceinline__ u32x4 bias(const GemmArgs& p, int n0, int wave, int lane) {
-    return gv2_bias<T>(p, n0 + (wave * GPW + (lane < GPW ? lane : 0)) * 8);
-  }
-  static __device__ __forceinline__ void product(const Regs& r, const GemmArgs& p, const T* xs, int XS, int K, Shared& sh, int n0, int wave,
-                                                 int lane, const u32x4& bias_pre) {
-    const int kc = K >> 9;
-    const int g = wave * GPW + (lane < GPW ? lane : 0);           // the group of 8 columns this lane finishes (lanes < GPW)
-    const Scale8 sc = gv2_scale(p, n0 + g * 8);
-    float acc[MT][J];
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-      for (int j = 0; j < J; ++j) acc[m][j] = 0.f;
-#pragma unroll
-    for (int c = 0; c < KCMAX; ++c) {
-      if (!GUARD || c < kc) {
-        float x[MT][8];
-#pragma unroll
-        for (int m = 0; m < MT; ++m) unpack8<T>(*reinterpret_cast<const u32x4*>(xs + (size_t)m * XS + c * 512 + lane * 8), x[m]);
-#pragma unroll
-        for (int j = 0; j < J; ++j) {
-          float wf[8];
-          unpack8_e4m3(r.w[c * J + j][0], r.w[c * J + j][1], wf);
-#pragma unroll
-          for (int m = 0; m < MT; ++m) {
-            float t = acc[m][j];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) t = fmaf(x[m][e], wf[e], t);
-            acc[m][j] = t;
-          }
-        }
-      }
-    }
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-      for (int j = 0; j < J; ++j) {
-        const float t = wave_sum_uniform(acc[m][j]);
-        if (lane == 0) sh.outp[m][wave * J + j] = t;
-      }
-    __syncthreads();
-    if (lane < GPW && g < NG) {
-      const int n = n0 + g * 8;
-      if (n < p.N) {
-        const float s8[8] = {sc.a[0], sc.a[1], sc.a[2], sc.a[3], sc.b[0], sc.b[1], sc.b[2], sc.b[3]};
-        uint32_t am = 0u;
-        for (int m = 0; m < p.M && m < MT; ++m) {
-          float v[8];
-#pragma unroll
-          for (int i = 0; i < 8; ++i) v[i] = sh.outp[m][g * 8 + i] * s8[i];      // the row scale, once, in front of the shared epilogue
-          am = absmax_pk(am, epilogue8<T>(p, m, n, v, &bias_pre));
-        }
-        if (p.flags & COGV_EPI_ABSMAX) {
-          const uint32_t wv = max(am & 0xffffu, am >> 16);
-          atomic_max_nonneg(p.absmax, bits_to_f<T>((uint16_t)wv));
-        }
-      }
-    }
-  }
-};
-
-// FormM8: FormM on 8-bit weights.  A lane's 16-byte load holds 16 contraction elements of its row: TWO fragments.  Load i of
-// a wave covers the 64-element block kblock(kw, i) of the tile's 16 rows (blocks in pairs: one 128-byte line of a row); lane l
-// supplies row (l & 15), elements 16 (l >> 4) .. + 15 of the block -- the first 8 to one v_mfma_f32_16x16x32 and the last 8
-// to the next, and the x operand of each takes the same 8 elements of its row from LDS (a contraction is a sum over all slots:
-// any slot-to-lane mapping serves as long as both operands use it).  E4M3 -> T is exact (fp16 and bf16 hold every E4M3 value),
-// through fp32 in registers.  Everything behind the accumulator is FormM's, with the row scale in front of the epilogue.
-template <typename T, int NWK, int TW, int LMAX, bool GUARD_, int MT>
-struct FormM8 {
-  static constexpr int NW = NWK * TW, COLS = 16 * TW, XPAD = 8, NS = LMAX, XCHUNKS = (LMAX * NWK * 64 + 511) / 512;
-  static constexpr bool GUARD = GUARD_;
-  struct Regs { u32x4 w[LMAX]; };
-  struct Shared { f32x4 red[NW][64]; float outp[TW][16][16]; };
-  static __device__ __forceinline__ int kblock(int kw, int i) { return 2 * (kw + NWK * (i >> 1)) + (i & 1); }
-  template <int S0, int S1>
-  static __device__ __forceinline__ void issue(Regs& r, const GemmArgs& p, int n0, int K, int wave, int lane) {
-    const int L = K / (64 * NWK), kw = wave % NWK, nt = n0 + (wave / NWK) * 16 + (lane & 15);
-    const int n = nt < p.N ? nt : p.N - 1;
-    const uint8_t* row = reinterpret_cast<const uint8_t*>(p.B) + (size_t)n * p.ldb + (lane >> 4) * 16;
-#pragma unroll
-    for (int i = S0; i < S1; ++i)
-      if (!GUARD || i < L) r.w[i] = gload16(row + 64 * kblock(kw, i));
-  }
-  static __device__ __forceinline__ u32x4 bias(const GemmArgs& p, int n0, int wave, int lane) {
-    return gv2_bias<T>(p, n0 + (wave / NWK) * 16 + (lane & 1) * 8);
-  }
-  static __device__ __forceinline__ typename HT<T>::v8 frag(uint32_t lo, uint32_t hi) {
-    float f[8];
-    unpack8_e4m3(lo, hi, f);
-    return __builtin_bit_cast(typename HT<T>::v8, pack8<T>(f));
-  }
-  template <int I0, int I1>
-  static __device__ __forceinline__ void accumulate(const Regs& r, const T* xs, int XS, int K, int kofs, int wave, int lane, f32x4& acc) {
-    typedef typename HT<T>::v8 v8;
-    const int L = K / (64 * NWK), kw = wave % NWK;
-    const int mrow = (lane & 15) < MT ? (lane & 15) : MT - 1;
-    const T* xrow = xs + (size_t)mrow * XS + (lane >> 4) * 16 - kofs;
-#pragma unroll
-    for (int i = I0; i < I1; ++i) {
-      if (!GUARD || i < L) {
-        const T* xb = xrow + 64 * kblock(kw, i);
-        const v8 b0 = *reinterpret_cast<const v8*>(xb), b1 = *reinterpret_cast<const v8*>(xb + 8);
-        acc = HT<T>::mfma16(frag(r.w[i][0], r.w[i][1]), b0, acc);
-        acc = HT<T>::mfma16(frag(r.w[i][2], r.w[i][3]), b1, acc);
-      }
-    }
-  }
-  static __device__ __forceinline__ Scale8 scale(const GemmArgs& p, int n0, int wave, int lane) {
-    return gv2_scale(p, n0 + (wave / NWK) * 16 + (lane & 1) * 8);
   }
   // (the two-halves kernel calls this form: its scales are requested here, in the tail)
   static __device__ __forceinline__ void finish(f32x4 acc, const GemmArgs& p, Shared& sh, int n0, int wave, int lane, const u32x4& bias_pre) {
-    finish(acc, p, sh, n0, wave, lane, bias_pre, scale(p, n0, wave, lane));
+    finish(acc, p, sh, n0, wave, lane, bias_pre, W::scale(p, n0 + (wave / NWK) * 16, lane & 1));
   }
   static __device__ __forceinline__ void finish(f32x4 acc, const GemmArgs& p, Shared& sh, int n0, int wave, int lane, const u32x4& bias_pre,
-                                                const Scale8& sc) {
+                                                const Scale& sc) {
     const int tile = wave / NWK, kw = wave % NWK;
     sh.red[wave][lane] = acc;
     __syncthreads();
@@ -409,13 +295,13 @@ struct FormM8 {
     }
     __syncthreads();
     if (kw == 0) {
-      const int m = lane >> 1, n = n0 + tile * 16 + (lane & 1) * 8;
+      const int m = lane >> 1, n = col(n0, wave, lane);
       uint32_t am = 0u;
       if (m < p.M && m < MT && n < p.N) {
-        const float s8[8] = {sc.a[0], sc.a[1], sc.a[2], sc.a[3], sc.b[0], sc.b[1], sc.b[2], sc.b[3]};
+        const typename W::Factors s8 = W::factors(sc);
         float v[8];
 #pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = sh.outp[tile][m][(lane & 1) * 8 + i] * s8[i];
+        for (int i = 0; i < 8; ++i) v[i] = W::mul(sh.outp[tile][m][(lane & 1) * 8 + i], s8, i);
         am = epilogue8<T>(p, m, n, v, &bias_pre);
       }
       if (p.flags & COGV_EPI_ABSMAX) {
@@ -428,7 +314,7 @@ struct FormM8 {
   }
   static __device__ __forceinline__ void product(const Regs& r, const GemmArgs& p, const T* xs, int XS, int K, Shared& sh, int n0, int wave,
                                                  int lane, const u32x4& bias_pre) {
-    const Scale8 sc = scale(p, n0, wave, lane);
+    const Scale sc = W::scale(p, n0 + (wave / NWK) * 16, lane & 1);
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     accumulate<0, LMAX>(r, xs, XS, K, 0, wave, lane, acc);
     finish(acc, p, sh, n0, wave, lane, bias_pre, sc);
@@ -814,16 +700,16 @@ using TT = std::conditional<COGV_GEMV_TU != 0, f16_t, bf16_t>::type;
 #define GV2_CAT2(a, b) a##b
 #define GV2_CAT(a, b) GV2_CAT2(a, b)
 #ifndef COGV_GEMV_W8
-template <int J, int KCMAX, bool G> using GvV = FormV<TT, J, KCMAX, G, 1, 4>;
-template <int NWK, int LMAX, bool G, int MT, int TW> using GvM = FormM<TT, NWK, TW, LMAX, G, MT>;
+using WT = W16<TT>;
 #define GV2_CLASSES GV_CLASSES_16
 #define GV2_RUN GV2_CAT(cogv_gemv2_run_, COGV_GEMV_TU)
-#else   // (units gemv_w8_<dtype>.o: the same kernels on the 8-bit forms; nothing of the 16-bit forms is instantiated here)
-template <int J, int KCMAX, bool G> using GvV = FormV8<TT, J, KCMAX, G, 1, 4>;
-template <int NWK, int LMAX, bool G, int MT, int TW> using GvM = FormM8<TT, NWK, TW, LMAX, G, MT>;
+#else   // (units gemv_w8_<dtype>.o: the same kernels on the 8-bit operand; nothing of the 16-bit operand is instantiated here)
+using WT = W8<TT>;
 #define GV2_CLASSES GV_CLASSES_8
 #define GV2_RUN GV2_CAT(cogv_gemv2_w8_run_, COGV_GEMV_TU)
 #endif
+template <int J, int KCMAX, bool G> using GvV = FormV<WT, J, KCMAX, G, 1, 4>;
+template <int NWK, int LMAX, bool G, int MT, int TW> using GvM = FormM<WT, NWK, TW, LMAX, G, MT>;
 
 // One class at one MT: F its form with one tile per workgroup (plain and attention kind), FL the LayerNorm kind's.  Only the
 // kinds in KINDS are instantiated, the plain one as the two-halves kernel where K2 says so.

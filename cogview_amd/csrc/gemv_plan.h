@@ -7,7 +7,7 @@
 
 enum { GV_PLAIN = 1, GV_ATTN = 2, GV_LN = 4, GV_ALL = 7 };       // kind (bits: a class row names the kinds that take it)
 enum { GV_W16 = 0, GV_W8 = 1 };                                  // weight format: the dtype's 16 bits | E4M3 bytes + row scales
-enum { GV_FORM_V = 0, GV_FORM_M = 1 };                           // FormV / FormV8: one row, vector ALU | FormM / FormM8: 2 .. 8 rows, MFMA
+enum { GV_FORM_V = 0, GV_FORM_M = 1 };                           // FormV: one row, vector ALU | FormM: 2 .. 8 rows, MFMA (either weight operand)
 
 // The classes.  A product of MT rows (1 | 2, 4, 8: the row count rounded up) takes the FIRST row of its format whose form
 // matches (V: MT = 1, M: MT > 1) and whose K range holds K; a kind in STOP ends the search there (first generation / unsupported),

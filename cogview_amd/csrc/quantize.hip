@@ -1,13 +1,9 @@
-// Row-wise 8-bit weight quantizer of the decode step's weight stream (cogv_quantize_rows_e4m3; consumed by the 8-bit forms of
-// gemv.hip).  W[N][K] in the 16-bit storage type -> q[N][K] as OCP E4M3 bytes ("e4m3fn": no infinities, largest value 448) and
-// one fp32 scale per row:
-//     scale[n] = max_k |W[n][k]| / 448   (fp32 division; 1.0 for an all-zero row)
-//     q[n][k]  = rne_e4m3( float(W[n][k]) / scale[n] )          (a true fp32 division, not a reciprocal multiply: a CPU reproduces
-//                                                                the bytes with the same two operations)
-// |w| / scale exceeds 448 by fp32 rounding error at most, which still rounds to 448: no value leaves the representable range.
+// Row-wise 8-bit weight quantizer of the decode step's weight stream (cogv_quantize_rows_e4m3; consumed by the 8-bit operand of
+// gemv.hip).  W[N][K] in the 16-bit storage type -> q[N][K] as OCP E4M3 bytes and one fp32 scale per row: the rule of
+// e4m3_stream.cuh with a row as the group.
 // One workgroup per row, two passes over it (the second is served by L2); the row maximum is taken on the bit patterns and
 // reduced through LDS in a fixed order -- no atomics.  Runs once per weight matrix when a decoder is built: not a hot path.
-#include "common.cuh"
+#include "e4m3_stream.cuh"
 #include "cogview_hip.h"
 
 namespace {
@@ -21,7 +17,7 @@ __global__ __launch_bounds__(256) void quantize_rows_e4m3_kernel(const T* __rest
   uint32_t m = 0u;
   for (int v = threadIdx.x; v < nvec; v += 256) m = absmax_pk8(m, *reinterpret_cast<const u32x4*>(row + v * 8));
   const float amax = absmax_pk_block<T>(m, redm);
-  const float s = amax == 0.f ? 1.0f : amax / 448.0f;
+  const float s = e4m3_scale(amax);
   if (threadIdx.x == 0) scale[n] = s;
   uint8_t* qrow = q + (size_t)n * ldq;
   for (int v = threadIdx.x; v < nvec; v += 256) {
@@ -29,12 +25,7 @@ __global__ __launch_bounds__(256) void quantize_rows_e4m3_kernel(const T* __rest
     unpack8<T>(*reinterpret_cast<const u32x4*>(row + v * 8), f);
 #pragma unroll
     for (int i = 0; i < 8; ++i) f[i] = f[i] / s;
-    int lo = 0, hi = 0;
-    lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], lo, false);
-    lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], lo, true);
-    hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], hi, false);
-    hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], hi, true);
-    *reinterpret_cast<u32x2*>(qrow + v * 8) = u32x2{(uint32_t)lo, (uint32_t)hi};
+    *reinterpret_cast<u32x2*>(qrow + v * 8) = u32x2{pack4_e4m3(f[0], f[1], f[2], f[3]), pack4_e4m3(f[4], f[5], f[6], f[7])};
   }
 }
 
