@@ -52,7 +52,9 @@ const char* cogv_arch(void);            /* "gfx950" */
 #define COGV_EPI_BIAS 1     /* + bias[n]                                                             */
 #define COGV_EPI_GELU 2     /* out = gelu(x); if aux != NULL the rounded pre-activation is stored     */
 #define COGV_EPI_DGELU 4    /* out = x * gelu'(aux[m][n])                                             */
-#define COGV_EPI_DROPOUT 8  /* out = dropout(out), element index m*N+n                                */
+#define COGV_EPI_DROPOUT 8  /* out = dropout(out), element index m*N+n; a dropped element is written as -0.0, and in   *
+                             * a 16-bit output no kept element is (see cogv_sandwich_ln_bwd_marked; an fp32 output  *
+                             * keeps the zero sign its kept fp32 value has; COGV_EPI_ACCUM adds C after the marks)  */
 #define COGV_EPI_ABSMAX 16  /* atomicMax(*absmax, max|out|) -- feeds the Sandwich-LN scale            */
 #define COGV_EPI_ACCUM 32   /* out += C (gradient accumulation / tied embedding)                      */
 #define COGV_EPI_COLSUM 64  /* column sums of the (rounded) output per 128-row slab -> colsum_partial:      *

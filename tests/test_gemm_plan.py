@@ -355,3 +355,105 @@ def test_python_predicates_against_their_predecessors():
     # the grouped predicate disagrees in all three ways; the column sums' already knew the spans and never had trans_a
     assert all(v > 0 for v in kinds["grouped"].values()), kinds
     assert kinds["fuse"]["span"] == 0 and kinds["fuse"]["M & 7 under trans_a"] == 0 and kinds["fuse"]["N & 7"] > 0, kinds
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The grid of tests/gemm_cells.py (tests/test_gemm_cells_gpu.py executes it): it reaches every path it is there for.
+from tests import gemm_cells as GC  # noqa: E402
+
+
+def _cell_desc(gen, shape, layout, dtype, cell):
+    M, N, K, splitk, _ = shape
+    return desc(M, N, K, layout, dtype, splitk=splitk, kernel_variant=GC.VARIANT[gen], flags=cell.flags, out_f32=int(cell.out_f32),
+                bias=0x60000, aux=0x70000, ldaux=N, absmax=0x80000, dropout_p=0.5, dropout_row0=cell.row0, colsum_partial=0x50000)
+
+
+def test_cell_grid_plans_what_its_rows_name():
+    """every cell: the generation of its row, that generation's tile, the tiles, effective split-K and k-tiles per split written
+    beside the shape -- or the refusal code listed for it, with `out` untouched"""
+    n = refused = 0
+    for gen in GC.GENERATIONS:
+        for shape, (tm, tn, splitk, kps) in GC.GRID[gen]:
+            for layout in GC.LAYOUTS:
+                for dtype in (F16, BF16):
+                    for cell in GC.cells_of(shape[3]):
+                        rc, out = plan(_cell_desc(gen, shape, layout, dtype, cell))
+                        want = GC.refusal(gen, shape[3], cell)
+                        n += 1
+                        if want != OK:
+                            refused += 1
+                            assert (rc, out) == (want, UNTOUCHED), (gen, shape, layout, cell)
+                        else:
+                            assert rc == OK and out[:8] == [0, gen, *GC.TILE[gen], tm, tn, splitk, kps] and out[16] == layout, (gen, shape, layout, cell, out)
+    # 20 cells on a shape without split-K, 7 on one with: generation 1 has 3 + 2 shapes, 2 has 2 + 1, 3 and 4 have 3 + 2 each;
+    # refused: 4 of the 20 in generations 1 and 2, 1 in 3 and 4, 1 of the 7 everywhere
+    assert n == ((3 * 20 + 2 * 7) + (2 * 20 + 7) + 2 * (3 * 20 + 2 * 7)) * 8 and refused == (14 + 9 + 5 + 5) * 8
+    # the refusals by their rows: the column sums in generations 1 and 2 (3), with split-K or an fp32 output anywhere (1)
+    sums = [c for c in GC.CELLS if c.flags & COLSUM and not c.out_f32]
+    assert [c.flags for c in sums] == [DGELU | COLSUM, MULAUX | COLSUM, COLSUM | ACCUM]
+    assert [GC.refusal(g, 1, c) for g in GC.GENERATIONS for c in sums] == [ERR_UNSUPPORTED] * 6 + [OK] * 6
+    assert all(GC.refusal(g, 2, GC.Cell(MULAUX | COLSUM)) == ERR_ARG and GC.refusal(g, 1, GC.Cell(MULAUX | COLSUM, out_f32=True)) == ERR_ARG for g in GC.GENERATIONS)
+    assert GC.Cell(MULAUX | COLSUM) in GC.SPLIT_CELLS and GC.Cell(MULAUX | COLSUM, out_f32=True) in GC.CELLS
+
+
+def test_cell_grid_reaches_every_path():
+    """each generation: an edge tile in M and in N (one of 8 rows, one of 8 columns), a full tile, one, two and three or more
+    k-tiles per split, and a split with uneven k-tiles; generation 1 also a ragged K with a tail of 8"""
+    for gen in GC.GENERATIONS:
+        tile_m, tile_n = GC.TILE[gen]
+        shapes = [s for s, _ in GC.GRID[gen]]
+        assert any(M % tile_m == 8 for M, N, K, s, w in shapes) and any(N % tile_n == 8 for M, N, K, s, w in shapes), gen
+        assert any(M >= tile_m and N >= tile_n for M, N, K, s, w in shapes), gen
+        assert any((K + 63) // 64 == 1 for M, N, K, s, w in shapes), gen
+        nk = {(K + 63) // 64 for M, N, K, s, w in shapes}
+        assert {1, 2} <= nk and max(nk) >= 3, (gen, nk)
+        assert any(p[2] > 1 and ((K + 63) // 64) % p[2] != 0 for (M, N, K, s, w), p in GC.GRID[gen]), gen
+        assert all(M % 8 == 0 and N % 8 == 0 and K % 8 == 0 for M, N, K, s, w in shapes)
+    assert any(K % 64 == 8 for (M, N, K, s, w), _ in GC.GRID[1])
+    assert GC.GRID[1][0][0][:2] == (56, 64) and (200, 136, 200, 1, False) in [s for s, _ in GC.GRID[1]]       # 200 = 128 + 72: an edge tile of 72 rows too
+    # the rows of the grid as they were decided, literally
+    assert [s[:4] for s, _ in GC.GRID[1]][:3] == [(56, 64, 72, 1), (200, 136, 200, 1), (136, 264, 328, 2)]
+    assert [s[:4] for s, _ in GC.GRID[2]] == [(64, 64, 64, 1), (264, 136, 128, 1), (520, 264, 192, 2)]
+    for gen in (3, 4):
+        assert [s for s, _ in GC.GRID[gen]] == [(256, 256, 64, 1, False), (264, 520, 128, 1, False), (520, 264, 192, 2, False),
+                                                (520, 520, 192, 1, True), (520, 520, 192, 2, True)]
+    assert GC.GROUP == ((256, 264, 128, ACCUM, 1), (520, 256, 192, 0, 2), (264, 520, 64, ACCUM, 1))
+
+
+def test_cell_flag_sets():
+    """the nine flag sets generations 3 and 4 compile an epilogue for (csrc/gemm_gen3.cuh, gemm_gen4.cuh: the chain of p.flags ==
+    tests), at least five that only the run-time-flag instance serves, and the fp32 output"""
+    compiled = [0, BIAS, ACCUM, BIAS | DROPOUT | ABSMAX, BIAS | GELU, DGELU | COLSUM, DGELU, BIAS | GELU | GELU_DAUX, MULAUX | COLSUM]
+    assert sorted(GC.COMPILED) == sorted(compiled)
+    sixteen_bit = {c.flags for c in GC.CELLS if not c.out_f32}
+    assert set(compiled) <= sixteen_bit
+    outside = sixteen_bit - set(compiled)
+    assert len(outside) >= 5 and {ABSMAX, BIAS | ACCUM, MULAUX, DROPOUT | ACCUM} <= outside and outside == set(GC.RUNTIME_ONLY)
+    assert GC.Cell(BIAS | GELU, aux=True) in GC.CELLS and any(c.row0 == 16 and c.flags & DROPOUT for c in GC.CELLS)
+    assert {c.flags for c in GC.CELLS if c.out_f32} == {0, BIAS | ACCUM, BIAS | DROPOUT | ABSMAX, MULAUX | COLSUM}
+    assert [(c.flags, c.out_f32) for c in GC.SPLIT_CELLS[:6]] == [(0, False), (BIAS, False), (ACCUM, False), (BIAS | DROPOUT | ABSMAX, False),
+                                                                 (BIAS | GELU, False), (ACCUM, True)]
+    assert (GC.BIAS, GC.GELU, GC.DGELU, GC.DROPOUT, GC.ABSMAX, GC.ACCUM, GC.COLSUM, GC.GELU_DAUX, GC.MULAUX) == \
+        (BIAS, GELU, DGELU, DROPOUT, ABSMAX, ACCUM, COLSUM, GELU_DAUX, MULAUX) == \
+        (_lib.EPI_BIAS, _lib.EPI_GELU, _lib.EPI_DGELU, _lib.EPI_DROPOUT, _lib.EPI_ABSMAX, _lib.EPI_ACCUM, _lib.EPI_COLSUM, _lib.EPI_GELU_DAUX, _lib.EPI_MULAUX)
+
+
+def test_cell_grid_item_hand_over():
+    """the 8-workgroup cells: 9 or 18 items on a grid of 8 under the reserve (a workgroup takes a second item), one workgroup per
+    item without it; the grouped launch: 14 items over three problems, the second split in two"""
+    lib = _lib.lib()
+    small = [(gen, s) for gen in (3, 4) for s, _ in GC.GRID[gen] if s[4]]
+    assert len(small) == 4 and all(gen in (3, 4) or not s[4] for gen in GC.GENERATIONS for s, _ in GC.GRID[gen])
+    group = [desc(M, N, K, TN, splitk=s, flags=f) for M, N, K, f, s in GC.GROUP]
+    for gen, s in small:
+        assert plan(_cell_desc(gen, s, NN, BF16, GC.Cell(0)))[1][9:11] == [9 * s[3], 9 * s[3]]
+    assert [o[8:11] for o in plan_group(group)[1][:3]] == [[0, 14, 14], [2, 14, 14], [8, 14, 14]] and GC.GROUP_ITEMS == 14
+    prev = lib.cogv_gemm_reserve_cus(256 - 8)
+    try:
+        for gen, s in small:
+            out = plan(_cell_desc(gen, s, NN, BF16, GC.Cell(0)))[1]
+            assert out[9] == 9 * s[3] and out[10] == 8 < out[9], (gen, s, out)
+        rc, out = plan_group(group)
+        assert rc == OK and [o[8:11] for o in out[:3]] == [[0, 14, 8], [2, 14, 8], [8, 14, 8]] and [o[6:8] for o in out[:3]] == [[1, 2], [2, 2], [1, 1]]
+    finally:
+        lib.cogv_gemm_reserve_cus(prev)
