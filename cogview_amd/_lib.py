@@ -85,6 +85,20 @@ class AttnDecodeDesc(C.Structure):
     ]
 
 
+class AttnDecodeChunkDesc(C.Structure):
+    _fields_ = [
+        ("dtype", C.c_int), ("B", C.c_int), ("H", C.c_int), ("capacity", C.c_int), ("head_dim", C.c_int),
+        ("m", C.c_int),
+        ("scale", C.c_float),
+        ("qkv", C.c_void_p), ("qkv_rs", C.c_longlong),
+        ("cache", C.c_void_p), ("cache_bs", C.c_longlong), ("cache_rs", C.c_int),
+        ("out", C.c_void_p), ("out_rs", C.c_longlong),
+        ("pos", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("skip_combine", C.c_int),
+        ("first", C.c_void_p),
+    ]
+
+
 class AttnDecodeKv8Desc(C.Structure):
     _fields_ = [
         ("dtype", C.c_int), ("B", C.c_int), ("H", C.c_int), ("capacity", C.c_int), ("head_dim", C.c_int),
@@ -183,6 +197,7 @@ SIGNATURES = {
     "cogv_gemv_ln": (_i, [C.POINTER(GemmDesc), C.POINTER(LnPrologue), _vp]),
     "cogv_gemv_attn": (_i, [C.POINTER(GemmDesc), _vp, _i, _i, _vp]),
     "cogv_attention_decode": (_i, [C.POINTER(AttnDecodeDesc), _vp]),
+    "cogv_attention_decode_chunk": (_i, [C.POINTER(AttnDecodeChunkDesc), _vp]),
     "cogv_quantize_rows_e4m3": (_i, [_i, _vp, _i, _i, _i, _vp, _i, _vp, _vp]),
     "cogv_gemm_w8": (_i, [C.POINTER(GemmDesc), C.POINTER(W8Weight), _vp]),
     "cogv_gemv_ln_w8": (_i, [C.POINTER(GemmDesc), C.POINTER(LnPrologue), C.POINTER(W8Weight), _vp]),

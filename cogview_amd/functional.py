@@ -978,10 +978,18 @@ def decode_attention(qkv, slot, heads, combine=True):
     """The decode attention of one layer, chosen by the slot's type: a 16-bit StaticKVSlot (ops.attention_decode on its cache)
     or an 8-bit StaticKV8Slot (ops.attention_decode_kv8 on its bytes and scales); both write the new token's key / value into
     the slot at pos_index.  combine=False: the split partials for gemv_attn / gemv_attn_w8.  A slot that carries `.first` (a
-    ragged decoder: one first attended slot per cache row) hands it on; without one the calls are what they always were."""
+    ragged decoder: one first attended slot per cache row) hands it on; without one the calls are what they always were.
+    qkv [b, m, 3 * heads * 64] with m > 1 (a chunk step: m tokens per cache row, slots pos_index ... pos_index + m - 1) goes to
+    ops.attention_decode_chunk on the 16-bit cache; the 8-bit cache has no such form."""
     kw = {} if combine else {"combine": False}
     if getattr(slot, "first", None) is not None:
         kw["first"] = slot.first
+    if qkv.dim() == 3 and qkv.shape[1] > 1:
+        if getattr(slot, "scale", None) is not None:
+            raise NotImplementedError("the 8-bit key/value cache serves one-token decode steps only: use kv=None for chunk steps")
+        res = ops.attention_decode_chunk(qkv, slot.cache, slot.pos_index, heads, **kw)
+        slot.out = slot.cache
+        return res
     if getattr(slot, "scale", None) is not None:
         res = ops.attention_decode_kv8(qkv, slot, slot.pos_index, heads, **kw)
         slot.out = slot.q
@@ -1050,25 +1058,27 @@ def decode_chain(tr, h0, absmax0, slots, emb_weight, w8=None):
     LN4 + residual, LN1] as prologue | decode attention, key splits (cache append fused) | dense GEMV with the combine as prologue | h->4h GEMV with [LN3 +
     residual, LN2] as prologue and GeLU epilogue | 4h->h GEMV; the last LN4 + residual and the final LayerNorm are the
     prologue of the tied-logits GEMV.  Same arithmetic and rounding points as the layer-by-layer path
-    (mpu/sparse_transformer.py:314-342, 612; model/gpt2_modeling.py:115-118).  h0 [b, 1, h]; slots: StaticKVSlot per
-    layer.  Returns logits [b, 1, V].
+    (mpu/sparse_transformer.py:314-342, 612; model/gpt2_modeling.py:115-118).  h0 [b, m, h]; slots: StaticKVSlot per
+    layer.  Returns logits [b, m, V].  m = 1: one token per cache row.  m > 1 (a chunk step, b * m <= 8 rows): the same
+    launches on b * m rows, rows b * m + j being the tokens of slots pos_index + j (ops.attention_decode_chunk in the attention
+    slot); the Sandwich scale is the abs-max over all b * m rows, as in a multi-token model call.
     w8 (W8Weights): launch for launch the same chain on the 8-bit copies of the weights, each product reading (q, scale) in
     place of the 16-bit matrix (emb_weight is not read)."""
     b, s, h = h0.shape
-    assert s == 1
+    rows = b * s
     if w8 is None:
         gemv_ln, gemm, logits_w = ops.gemv_ln, ops.gemm, emb_weight
         operands = ((l.attention.query_key_value.weight, l.attention.dense.weight, l.mlp.dense_h_to_4h.weight, l.mlp.dense_4h_to_h.weight)
                     for l in tr.layers)
 
         def gemv_attn(parts, npp, cap, w, bias):
-            return ops.gemv_attn(parts, b, npp, cap, w, bias=bias)
+            return ops.gemv_attn(parts, rows, npp, cap, w, bias=bias)
     else:
         gemv_ln, gemm, logits_w, operands = ops.gemv_ln_w8, ops.gemm_w8, w8.emb, w8.layers
 
         def gemv_attn(parts, npp, cap, w, bias):
-            return ops.gemv_attn_w8(parts, b, npp, cap, w, w8.dtype, bias=bias)
-    z, z_absmax, post, res = h0.view(b, h), absmax0, None, None
+            return ops.gemv_attn_w8(parts, rows, npp, cap, w, w8.dtype, bias=bias)
+    z, z_absmax, post, res = h0.view(rows, h), absmax0, None, None
     for layer, slot, (w_qkv, w_dense, w_h4h, w_4hh) in zip(tr.layers, slots, operands):
         att_m, mlp_m = layer.attention, layer.mlp
         eps = layer.input_layernorm.eps
@@ -1084,11 +1094,11 @@ def decode_chain(tr, h0, absmax0, slots, emb_weight, w8=None):
         # burst of same-address atomics
         if hp % 512 == 0 and _decode_fuse_combine():
             # the key splits' partials are combined in the prologue of the attention-output GEMV (one launch less)
-            parts = decode_attention(qkv.view(b, 1, 3 * hp), slot, npp, combine=False)
+            parts = decode_attention(qkv.view(b, s, 3 * hp), slot, npp, combine=False)
             ao = gemv_attn(parts, npp, slot.capacity, w_dense, att_m.dense.bias)
         else:
-            att = decode_attention(qkv.view(b, 1, 3 * hp), slot, npp)
-            ao = gemm(att.view(b, hp), w_dense, bias=att_m.dense.bias)
+            att = decode_attention(qkv.view(b, s, 3 * hp), slot, npp)
+            ao = gemm(att.view(rows, hp), w_dense, bias=att_m.dense.bias)
         g, y = gemv_ln(ao, w_h4h, mlp_m.dense_h_to_4h.bias, layer.post_attention_layernorm.weight,
                        layer.post_attention_layernorm.bias, eps, None,
                        (layer.third_layernorm.weight, layer.third_layernorm.bias), x, want_t=True, gelu=True)
@@ -1096,41 +1106,55 @@ def decode_chain(tr, h0, absmax0, slots, emb_weight, w8=None):
         z, z_absmax, post, res = mo, None, (layer.fourth_layernorm.weight, layer.fourth_layernorm.bias), y
     fl = tr.final_layernorm
     logits, _ = gemv_ln(z, logits_w, None, fl.weight, fl.bias, fl.eps, z_absmax, post, res)
-    return logits.view(b, 1, logits.shape[1])
+    return logits.view(b, s, logits.shape[1])
 
 
-def decode_layers_w8(tr, h0, absmax0, slots, w8):
-    """One decode step layer by layer on the 8-bit weights: _layer_forward's inference chain for one token per row (every
-    Sandwich-LN its own launch, decode attention with its combine, four plain 8-bit products per layer), the final LayerNorm and
-    the tied-logits product.  What the 8-bit decoder runs above COGV_DECODE_CHAIN_MAX_ROWS, and the comparison path of the chain."""
+def decode_layers(tr, h0, absmax0, slots, emb_weight, w8=None):
+    """One decode step layer by layer: _layer_forward's inference chain on b * m <= 8 rows (every Sandwich-LN its own launch,
+    decode attention with its combine, four plain skinny products per layer), the final LayerNorm and the tied-logits product.
+    h0 [b, m, h] -> logits [b, m, V]; m > 1: a chunk step, as in decode_chain.  w8 (W8Weights): the products read the 8-bit copies
+    (emb_weight is not read).  What a decoder runs above COGV_DECODE_CHAIN_MAX_ROWS for the 8-bit weights and for chunk steps, and
+    the comparison path of the chain."""
     b, s, h = h0.shape
-    assert s == 1
+    rows = b * s
     dev = h0.device
+    if w8 is None:
+        gemm, logits_w = ops.gemm, emb_weight
+        operands = ((l.attention.query_key_value.weight, l.attention.dense.weight, l.mlp.dense_h_to_4h.weight, l.mlp.dense_4h_to_h.weight)
+                    for l in tr.layers)
+    else:
+        gemm, logits_w, operands = ops.gemm_w8, w8.emb, w8.layers
     x, absmax_x = (h0 if h0.is_contiguous() else h0.contiguous()), absmax0
-    for layer, slot, (w_qkv, w_dense, w_h4h, w_4hh) in zip(tr.layers, slots, w8.layers):
+    for layer, slot, (w_qkv, w_dense, w_h4h, w_4hh) in zip(tr.layers, slots, operands):
         att_m, mlp_m = layer.attention, layer.mlp
         eps = layer.input_layernorm.eps
         npp = att_m.num_attention_heads_per_partition
         hp = npp * 64
         a, _, _ = ops.sandwich_ln_fwd(x, layer.input_layernorm.weight, layer.input_layernorm.bias, eps, absmax_x, save_stats=False)
-        qkv = ops.gemm_w8(a.view(b, h), w_qkv, bias=att_m.query_key_value.bias).view(b, 1, 3 * hp)
+        qkv = gemm(a.view(rows, h), w_qkv, bias=att_m.query_key_value.bias).view(b, s, 3 * hp)
         att = decode_attention(qkv, slot, npp)
         slot_ao = ops.new_absmax_slot(dev)
-        ao = ops.gemm_w8(att.view(b, hp), w_dense, bias=att_m.dense.bias, absmax=slot_ao)
+        ao = gemm(att.view(rows, hp), w_dense, bias=att_m.dense.bias, absmax=slot_ao)
         slot_y = ops.new_absmax_slot(dev)
-        y, _, _ = ops.sandwich_ln_fwd(ao.view(b, 1, h), layer.third_layernorm.weight, layer.third_layernorm.bias, eps, slot_ao,
+        y, _, _ = ops.sandwich_ln_fwd(ao.view(b, s, h), layer.third_layernorm.weight, layer.third_layernorm.bias, eps, slot_ao,
                                       residual=x, absmax_out=slot_y, save_stats=False)
         c, _, _ = ops.sandwich_ln_fwd(y, layer.post_attention_layernorm.weight, layer.post_attention_layernorm.bias, eps, slot_y,
                                       save_stats=False)
-        g = ops.gemm_w8(c.view(b, h), w_h4h, bias=mlp_m.dense_h_to_4h.bias, gelu=True)
+        g = gemm(c.view(rows, h), w_h4h, bias=mlp_m.dense_h_to_4h.bias, gelu=True)
         slot_mo = ops.new_absmax_slot(dev)
-        mo = ops.gemm_w8(g, w_4hh, bias=mlp_m.dense_4h_to_h.bias, absmax=slot_mo)
+        mo = gemm(g, w_4hh, bias=mlp_m.dense_4h_to_h.bias, absmax=slot_mo)
         absmax_x = ops.new_absmax_slot(dev)
-        x, _, _ = ops.sandwich_ln_fwd(mo.view(b, 1, h), layer.fourth_layernorm.weight, layer.fourth_layernorm.bias, eps, slot_mo,
+        x, _, _ = ops.sandwich_ln_fwd(mo.view(b, s, h), layer.fourth_layernorm.weight, layer.fourth_layernorm.bias, eps, slot_mo,
                                       residual=y, absmax_out=absmax_x, save_stats=False)
     fl = tr.final_layernorm
     out, _, _ = ops.sandwich_ln_fwd(x, fl.weight, fl.bias, fl.eps, absmax_x, save_stats=False)
-    return ops.gemm_w8(out.view(b, h), w8.emb).view(b, 1, w8.emb[0].shape[0])
+    logits = gemm(out.view(rows, h), logits_w)
+    return logits.view(b, s, logits.shape[1])
+
+
+def decode_layers_w8(tr, h0, absmax0, slots, w8):
+    """decode_layers on the 8-bit weights: what the 8-bit decoder runs above COGV_DECODE_CHAIN_MAX_ROWS."""
+    return decode_layers(tr, h0, absmax0, slots, None, w8=w8)
 
 
 def transformer_layer_kv(layer, x, absmax_x, sep, kv_slot, mask=None):

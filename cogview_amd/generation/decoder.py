@@ -26,9 +26,13 @@ def unwrap(model):
     return model
 
 
-def refuse_unsupported(weights=None, kv=None, ragged=False, args=None, model=None, batch=None, use=None):
+MAX_STEP_ROWS = 8          # rows of one decode step: what the skinny products and the chunk attention take
+
+
+def refuse_unsupported(weights=None, kv=None, ragged=False, args=None, model=None, batch=None, use=None, chunk=0):
     """The one rule for what the decode step's options do not cover, applied before anything is allocated or quantized.
-    Asked for: weights= / kv= (formats) and ragged=True.  Known, each optional: `args` (a caller's .is_sparse), `model` (its storage
+    Asked for: weights= / kv= (formats), ragged=True and chunk=C (a second step of C tokens per cache row: 2 <= C <= 8 and
+    batch * C <= 8 rows, on the 16-bit cache).  Known, each optional: `args` (a caller's .is_sparse), `model` (its storage
     type), `batch` (the decoder's rows; with it the 8-bit weight stream is put to the kernels' launch plan).  `use`: what the message
     advises instead (a caller's host form; default: the decoder's own plain options).  Sparse generation and model parallelism > 1
     are refused for every caller that hands in `args`, with or without options; a plain decoder refuses nothing."""
@@ -37,10 +41,20 @@ def refuse_unsupported(weights=None, kv=None, ragged=False, args=None, model=Non
         raise ValueError(f"weights={weights!r}: None (16-bit) or one of {WEIGHT_FORMATS}")
     if kv is not None and kv not in KV_FORMATS:
         raise ValueError(f"kv={kv!r}: None (16-bit cache) or one of {KV_FORMATS}")
-    asked = {name: value for name, value in (("weights", weights), ("kv", kv), ("ragged", ragged or None)) if value is not None}
+    if chunk:
+        rows = (batch if batch is not None else 1) * chunk
+        if not isinstance(chunk, int) or not 2 <= chunk <= MAX_STEP_ROWS or rows > MAX_STEP_ROWS:
+            raise ValueError(f"chunk={chunk!r}: 0 (one-token steps only) or 2 ... {MAX_STEP_ROWS} tokens per cache row with batch * chunk <= "
+                             f"{MAX_STEP_ROWS} rows" + (f" (batch {batch})" if batch is not None else ""))
+    asked = {name: value for name, value in (("weights", weights), ("kv", kv), ("ragged", ragged or None), ("chunk", chunk or None))
+             if value is not None}
     what = " with " + ", ".join(f"{name}={value!r}" for name, value in asked.items()) if asked else ""
     if use is None:
-        use = ", ".join(f"{name}={False if name == 'ragged' else None}" for name in asked)
+        off = {"ragged": False, "chunk": 0}
+        use = ", ".join(f"{name}={off.get(name)}" for name in asked)
+    if chunk and kv is not None:
+        raise NotImplementedError(f"chunk={chunk} with kv={kv!r}: the 8-bit cache quantizes a key before it is attended, so it serves "
+                                  f"one-token steps only -- use kv=None")
     if args is not None:
         if args.is_sparse == 2:
             raise NotImplementedError(f"sparse generation (is_sparse = 2){what}: use {use}")
@@ -53,19 +67,20 @@ def refuse_unsupported(weights=None, kv=None, ragged=False, args=None, model=Non
     gpt = unwrap(model)
     dt = gpt.word_embeddings.weight.dtype
     # (a caller without the decoder's row count leaves weights= to the decoder, where the transformer is looked at anyway)
-    if dt not in (torch.float16, torch.bfloat16) and (kv is not None or ragged or batch is not None):
-        raise NotImplementedError(f"a {dt} model{what}: the 8-bit formats and the per-row `first` slot are the fp16 / bf16 decode "
-                                  f"step's -- use {use}")
+    if dt not in (torch.float16, torch.bfloat16) and (kv is not None or ragged or chunk or batch is not None):
+        raise NotImplementedError(f"a {dt} model{what}: the 8-bit formats, the per-row `first` slot and the chunk step are the fp16 / bf16 "
+                                  f"decode step's -- use {use}")
     if weights is not None and batch is not None:
         if gpt.word_embeddings.weight.shape[0] % 8:
             raise NotImplementedError(f"weights={weights!r}: a vocabulary of {gpt.word_embeddings.weight.shape[0]} rows (not a multiple of 8)")
-        why = F_.w8_decode_supported(gpt.transformer, batch)
-        if why is not None:
-            raise NotImplementedError(f"weights={weights!r}: {why}")
+        for rows in (batch, batch * chunk) if chunk else (batch,):
+            why = F_.w8_decode_supported(gpt.transformer, rows)
+            if why is not None:
+                raise NotImplementedError(f"weights={weights!r}: {why}")
 
 
 class GraphDecoder:
-    def __init__(self, model, batch=1, capacity=1152, weights=None, kv=None, ragged=False):
+    def __init__(self, model, batch=1, capacity=1152, weights=None, kv=None, ragged=False, chunk=0):
         """model: GPT2Model (optionally inside FP16_Module) in eval mode, dense attention; capacity: slots per cache
         (<= 4096, the gathered form's limit).
         weights="e4m3": the decode step streams 8-bit copies of the weights (OCP E4M3 bytes with one fp32 scale per row,
@@ -85,12 +100,18 @@ class GraphDecoder:
         [0, P - n_g) are padding, and every row writes the same slot *pos_index = P, P + 1, ... -- so the sampler's
         bookkeeping stays shared.  The one new piece of device data is self.first (int32 [batch], zeros): row b attends slots
         [first[b], *pos_index] (cogv_attn_decode_desc.first).  Its address is baked into a capture, so the choice is made
-        here.  One model-parallel partition, fp16 / bf16.  False (default): nothing is allocated, the step is what it was."""
+        here.  One model-parallel partition, fp16 / bf16.  False (default): nothing is allocated, the step is what it was.
+        chunk=C (2 <= C <= 8, batch * C <= 8): a SECOND step, of C tokens per cache row (step_chunk): rows b * C + j are the tokens
+        of slots *pos_index + j, appended to and attended over the same caches by ops.attention_decode_chunk; capture() captures
+        it as a second graph.  The Sandwich-LN scale of a chunk step is the abs-max over all its rows, as in a multi-token model
+        call, so its logits are not bit-equal to C one-token steps'.  Composes with weights= and ragged=; the 16-bit cache only.
+        0 (default): nothing is allocated or captured, the decoder is what it was."""
         m = unwrap(model)
         self.gpt, tr = m, m.transformer
         assert capacity <= 4096
         self.w8, self.kv, self.first = None, kv, None
-        refuse_unsupported(weights, kv, ragged, model=m, batch=batch)
+        refuse_unsupported(weights, kv, ragged, model=m, batch=batch, chunk=chunk)
+        self.chunk = int(chunk)
         if weights is not None:
             with torch.no_grad():
                 self.w8 = F_.W8Weights(tr, m.word_embeddings.weight)
@@ -116,6 +137,11 @@ class GraphDecoder:
         self.slab = torch.zeros(8 * len(tr.layers) + 16, dtype=torch.float32, device=dev)
         self.graph, self.logits = None, None
         self.fused = True            # False: layer-by-layer path (every LayerNorm its own launch) -- kept for comparison
+        if self.chunk:
+            self.tok_chunk = torch.zeros((batch, self.chunk), dtype=torch.long, device=dev)
+            self.pos_chunk = torch.zeros((batch, self.chunk), dtype=torch.long, device=dev)
+            self.chunk_j = torch.arange(self.chunk, dtype=torch.long, device=dev)
+            self.graph_chunk, self.logits_chunk = None, None
 
     # ------------------------------------------------------------------ one decode step, eager (also what gets captured)
     def _step(self):
@@ -134,6 +160,17 @@ class GraphDecoder:
             out = tr.final_layernorm(h)
             return F_.tied_logits(out, self.gpt.word_embeddings.weight)
 
+    def _step_chunk(self):
+        """One step of `chunk` tokens per cache row, eager (also what gets captured): the chain up to
+        COGV_DECODE_CHAIN_MAX_ROWS rows, above it layer by layer.  Returns logits [batch, chunk, vocab]."""
+        tr = self.gpt.transformer
+        self.slab.zero_()
+        with ops.scalar_slab(self.slab):
+            h = tr.embed(self.tok_chunk, self.pos_chunk, self.gpt.word_embeddings)
+            if self.fused and F_.decode_chain_supported(tr, self.batch * self.chunk):
+                return F_.decode_chain(tr, h, h._cogv_absmax, self.slots, self.gpt.word_embeddings.weight, w8=self.w8)
+            return F_.decode_layers(tr, h, h._cogv_absmax, self.slots, self.gpt.word_embeddings.weight, w8=self.w8)
+
     def capture(self):
         """Warm up on a side stream (first-use allocations inside the library and the caching allocator), then capture."""
         assert 0 < self.length < self.cap, "prefill first: the warm-up steps write at the current position"
@@ -147,6 +184,21 @@ class GraphDecoder:
         self.graph = torch.cuda.CUDAGraph()
         with torch.no_grad(), torch.cuda.graph(self.graph):
             self.logits = self._step()
+        if self.chunk:
+            self._capture_chunk()
+
+    def _capture_chunk(self):
+        """The chunk step as a second graph (its warm-up and capture runs scribble on the next `chunk` slots, none past the capacity)."""
+        self.pos_index.fill_(self.length)
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s), torch.no_grad():
+            for _ in range(3):
+                self._step_chunk()
+        torch.cuda.current_stream().wait_stream(s)
+        self.graph_chunk = torch.cuda.CUDAGraph()
+        with torch.no_grad(), torch.cuda.graph(self.graph_chunk):
+            self.logits_chunk = self._step_chunk()
 
     # ------------------------------------------------------------------ cache management (outside the graph)
     @torch.no_grad()
@@ -217,6 +269,27 @@ class GraphDecoder:
         self.length += 1
         return logits
 
+    def _replay_or_step_chunk(self):
+        if self.graph_chunk is None:
+            return self._step_chunk()
+        self.graph_chunk.replay()
+        return self.logits_chunk
+
+    @torch.no_grad()
+    def step_chunk(self, tokens, positions):
+        """tokens, positions: [batch, chunk] device tensors -- the next `chunk` inputs of every row.  Returns logits [batch, chunk,
+        vocab] (a static buffer when captured): row j's are those of the one-token step that fed tokens[:, j]."""
+        assert self.chunk, "built without chunk="
+        C = self.chunk
+        assert self.length + C <= self.cap, "key/value cache capacity exhausted"
+        self.tok_chunk.copy_(tokens.view(self.batch, C))
+        self.pos_chunk.copy_(positions.view(self.batch, C))
+        self.pos_index.fill_(self.length)
+        self.table[:, self.length:self.length + C] = torch.arange(self.length, self.length + C, dtype=torch.int32, device=self.table.device)
+        logits = self._replay_or_step_chunk()
+        self.length += C
+        return logits
+
 
 class SamplingDecoder(GraphDecoder):
     """A GraphDecoder whose step ends with the token sampler (ops.sample_logits, cogv_sample_logits): the drawn ids go
@@ -225,9 +298,11 @@ class SamplingDecoder(GraphDecoder):
     and a run of them needs no host work.  Reference path: generation/sampling.py:139-186 (model call, filter, multinomial,
     beam score) once per token.  Use start() + generate() (step() feeds tokens from the host and is not for this mode)."""
 
-    def __init__(self, model, batch=1, capacity=1152, weights=None, kv=None, ragged=False):
-        super().__init__(model, batch, capacity, weights=weights, kv=kv, ragged=ragged)
+    def __init__(self, model, batch=1, capacity=1152, weights=None, kv=None, ragged=False, chunk=0):
+        """chunk=C: generate(n, widths=...) may feed runs of given ids as chunk steps (GraphDecoder's `chunk`; _step_chunk below)."""
+        super().__init__(model, batch, capacity, weights=weights, kv=kv, ragged=ragged, chunk=chunk)
         self.sampling = None
+        self.chunk_steps = 0         # chunk steps run by generate() so far
 
     def enable_sampling(self, temperature=1.0, top_k=0, top_p=0.0, allow=None, seed=0, out_tokens=None, out_base=0,
                         given=None):
@@ -256,6 +331,37 @@ class SamplingDecoder(GraphDecoder):
         logits = super()._step()
         if self.sampling is not None:
             self._sample(logits)
+        return logits
+
+    def _step_chunk(self):
+        """A chunk step inside a sampling run, all on the device: row 0 is the token the previous step published, rows 1 ... C - 1 are
+        the given ids of the next C - 1 positions (the plan guarantees they are set; the clamps only keep a warm-up run at the end
+        of the cache inside the tables).  After the layers the decoder state is advanced by C - 1 -- what C - 1 one-token steps that
+        fed a given id would have left: write slot, positions, generator offset (one per position in both modes), the visible
+        slots, the output columns -- and the unchanged sampler runs on the last row's logits, exactly as if the one-token step at
+        that position had just run."""
+        if self.sampling is None:
+            return super()._step_chunk()
+        assert self.given is not None, "chunk steps inside a sampling run feed given ids: enable_sampling(given=...)"
+        C, j = self.chunk, self.chunk_j
+        at = self.pos_index + j                                                            # sequence positions of the chunk's rows
+        self.tok_chunk[:, :1].copy_(self.tok)
+        self.tok_chunk[:, 1:].copy_(self.given.index_select(0, at[1:].clamp(max=self.cap - 1)).clamp(min=0).unsqueeze(0).expand(self.batch, C - 1))
+        max_pos = self.gpt.transformer.position_embeddings.weight.shape[0] - 1
+        self.pos_chunk.copy_((self.pos + j).clamp(max=max_pos))
+        logits = super()._step_chunk()
+        p0 = self.pos_index.clone()
+        slots = torch.arange(self.cap, dtype=torch.long, device=p0.device)
+        new = (slots > p0) & (slots < p0 + C)                                              # positions p0 + 1 ... p0 + C - 1
+        self.table.copy_(torch.where(new.unsqueeze(0), slots.to(torch.int32).unsqueeze(0), self.table))
+        if self.out_tokens is not None:
+            cols = torch.arange(self.out_tokens.shape[1], dtype=torch.long, device=p0.device) + self.out_base
+            fed = self.given.index_select(0, cols.clamp(0, self.cap - 1))
+            self.out_tokens.copy_(torch.where(((cols > p0) & (cols < p0 + C)).unsqueeze(0), fed.unsqueeze(0), self.out_tokens))
+        self.pos_index.add_(C - 1)
+        self.pos.add_(C - 1)
+        self.offset.add_(C - 1)
+        self._sample(logits[:, -1])
         return logits
 
     def _first_draw(self, last_pos, last_logits, rows=None):
@@ -301,11 +407,22 @@ class SamplingDecoder(GraphDecoder):
         return st + ([self.out_tokens] if self.out_tokens is not None else [])
 
     @torch.no_grad()
-    def generate(self, n):
+    def generate(self, n, widths=None):
         """n decode steps back to back (graph replays when captured, else the same launches eagerly): n more tokens per
-        row.  Returns (out_tokens, scores) -- device tensors; nothing is read back on the way."""
+        row.  Returns (out_tokens, scores) -- device tensors; nothing is read back on the way.
+        widths (plan_chunk_steps; a decoder built with chunk=C): the n positions as model calls of width 1 (the one-token step) or
+        C (the chunk step: its C - 1 later inputs are given ids); they sum to n."""
         assert self.sampling is not None and self.length + n <= self.cap, "key/value cache capacity exhausted"
-        for _ in range(n):
-            self._replay_or_step()
+        if widths is None:
+            for _ in range(n):
+                self._replay_or_step()
+        else:
+            assert sum(widths) == n and all(w == 1 or (self.chunk and w == self.chunk) for w in widths)
+            for w in widths:
+                if w == 1:
+                    self._replay_or_step()
+                else:
+                    self._replay_or_step_chunk()
+                    self.chunk_steps += 1
         self.length += n
         return self.out_tokens, self.scores

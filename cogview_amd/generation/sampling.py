@@ -399,6 +399,20 @@ def plan_device_fill(seq_l, tokenizer, vocab):
                 capacity=_plan_capacity(len(seq_l)))
 
 
+def plan_chunk_steps(given, context, replays, C):
+    """The `replays` decode steps of a DeviceFiller call (plan_device_fill's given / context / replays) as model calls of width 1
+    or C, for a decoder with a chunk step of C tokens (GraphDecoder(chunk=C)).  Step k of the plain run feeds the id of sequence
+    position context + k.  Greedy from the first replay: at input position i a chunk of C is taken when the C - 1 positions after
+    it are all given (they are fed from the table, nothing is drawn for them) and the chunk ends inside the run,
+    i + C <= context + replays; otherwise one step.  Returns the list of widths; they sum to `replays`.  C = 0 or 1: all ones."""
+    widths, i, end = [], context, context + replays
+    while i < end:
+        w = C if C > 1 and i + C <= end and all(t >= 0 for t in given[i + 1:i + C]) else 1
+        widths.append(w)
+        i += w
+    return widths
+
+
 class _DeviceRun:
     """What the device entry points share: the refusals, ONE lazily built SamplingDecoder with its format keywords, the sampler
     armed for (temperature, top_k, top_p, allow) -- baked into a capture, so other values re-arm it and drop the graph, while the
@@ -408,14 +422,16 @@ class _DeviceRun:
     given table."""
     given = None
 
-    def __init__(self, model, args, seed=0, capture=True, weights=None, kv=None, ragged=False):
-        decoder.refuse_unsupported(weights, kv, ragged, args=args, model=model, use="filling_sequence")
-        self.model, self.seed, self.capture, self.ragged = model, int(seed), capture, ragged
+    def __init__(self, model, args, seed=0, capture=True, weights=None, kv=None, ragged=False, chunk=0):
+        decoder.refuse_unsupported(weights, kv, ragged, args=args, model=model, use="filling_sequence", chunk=chunk)
+        self.model, self.seed, self.capture, self.ragged, self.chunk = model, int(seed), capture, ragged, int(chunk)
         self.formats = {"weights": weights}           # only the keywords that are set: a default build issues the call it always did
         if kv is not None:
             self.formats["kv"] = kv
         if ragged:
             self.formats["ragged"] = True
+        if chunk:
+            self.formats["chunk"] = self.chunk
         self.dec, self.key, self.out = None, None, None
 
     def size(self, batch, capacity, width=None, out_base=0):
@@ -442,17 +458,23 @@ class _DeviceRun:
             if offset is not None:
                 self.dec.offset.copy_(offset)
             self.dec.graph, self.key = None, key
+            if self.chunk:
+                self.dec.graph_chunk = None
         return self.dec
 
-    def run(self, steps, *context):
-        """start / start_ragged on `context`, then `steps` decode steps on the graph (captured now unless an earlier call did)."""
+    def run(self, steps, *context, widths=None):
+        """start / start_ragged on `context`, then `steps` decode steps on the graph (captured now unless an earlier call did).
+        widths (a run driver with chunk=C): the steps as model calls of width 1 or C (plan_chunk_steps)."""
         dec = self.dec
         with torch.no_grad():
             (dec.start_ragged if self.ragged else dec.start)(*context)
             if steps:
                 if self.capture and dec.graph is None:
                     dec.capture()
-                dec.generate(steps)
+                if widths is None:
+                    dec.generate(steps)
+                else:
+                    dec.generate(steps, widths=widths)
         return dec.scores.clone()
 
 
@@ -580,12 +602,18 @@ class DeviceFiller(_DeviceRun):
     attention, one model-parallel partition, <= capacity positions (1408: the reference's MAXSEQLEN 1345 rounded up to 64).
     capture=False runs the same launches eagerly.  After a call, .scores is [1] fp32: the summed log-probability of the
     drawn ids (given ids add nothing).  weights="e4m3": the decode steps stream 8-bit copies of the weights (GraphDecoder's
-    `weights`), made when the first call builds the decoder.  kv="e4m3": 8-bit key/value caches (GraphDecoder's `kv`)."""
+    `weights`), made when the first call builds the decoder.  kv="e4m3": 8-bit key/value caches (GraphDecoder's `kv`).
+    chunk=C (2 ... 8; GraphDecoder's `chunk`, 16-bit cache only): runs of given ids inside the run are fed as chunk steps of C
+    tokens -- one model call in place of C replays, planned per call by plan_chunk_steps; a second graph is captured next to
+    the one-token one.  The draws keep their generator counters (one per position), but a chunk step's logits differ in the last
+    bits from one-token steps' (the Sandwich-LN scale spans the chunk's rows), so a draw can differ from the chunk=0 filler's
+    where two ids are about equally likely.  .model_calls: the decode steps of the last call.  0 (default): nothing changes."""
 
-    def __init__(self, model, args, seed=0, capacity=1408, capture=True, weights=None, kv=None):
-        super().__init__(model, args, seed, capture, weights, kv)
+    def __init__(self, model, args, seed=0, capacity=1408, capture=True, weights=None, kv=None, chunk=0):
+        super().__init__(model, args, seed, capture, weights, kv, chunk=chunk)
         self.size(1, capacity)
         self.scores = None
+        self.model_calls = 0
 
     def _buffers(self, dev):
         super()._buffers(dev)
@@ -611,7 +639,13 @@ class DeviceFiller(_DeviceRun):
         table = torch.full((self.capacity,), -1, dtype=torch.long)
         table[:len(seq_l)] = torch.tensor(plan["given"], dtype=torch.long)
         self.given.copy_(table)                       # before start(): its draw reads the entry of position n (-1)
-        self.scores = self.run(replays, tokens, position_ids, attention_mask)
+        if self.chunk:
+            widths = plan_chunk_steps(plan["given"], n, replays, self.chunk)
+            self.model_calls = len(widths)
+            self.scores = self.run(replays, tokens, position_ids, attention_mask, widths=widths)
+        else:
+            self.model_calls = replays
+            self.scores = self.run(replays, tokens, position_ids, attention_mask)
         out = seq.clone()
         out[n:n + replays + 1] = self.out[0, n:n + replays + 1].to(seq.device)
         return out.unsqueeze(0)

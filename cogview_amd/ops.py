@@ -687,6 +687,38 @@ def attention_decode(qkv, cache, pos_index, heads, combine=True, first=None):
     return out if combine else ws
 
 
+def attention_decode_chunk(qkv, cache, pos_index, heads, combine=True, first=None):
+    """attention_decode for m tokens per cache row (cogv_attention_decode_chunk): qkv [b, m, 3 * heads * 64] with 1 <= m <= 8
+    (rows r = b * m + j, as the QKV projection of [b * m, h] hidden rows leaves them), cache and pos_index as there.  Row
+    (b, j) is the token of slot pos + j and attends slots [first[b], pos + j]; the m keys / values are written into slots
+    [pos, pos + m) (none at or past the capacity).  Returns out [b, m, heads * 64], or with combine=False the partials of b * m
+    rows for gemv_attn(partials, b * m, ...).  Bit-identical to m attention_decode calls at pos, pos + 1, ..."""
+    _need_gpu(qkv, cache, pos_index)
+    b, cap = cache.shape[0], cache.shape[1]
+    hp = heads * 64
+    assert qkv.dim() == 3 and qkv.shape[0] == b and qkv.shape[2] == 3 * hp and cache.shape[2] == 2 * hp
+    m = qkv.shape[1]
+    assert qkv.stride(2) == 1 and (b == 1 or qkv.stride(0) == m * qkv.stride(1)), "rows b * m + j one stride apart"
+    assert cache.stride(2) == 1 and pos_index.dtype == torch.int64
+    rows = b * m
+    key = (qkv.device.index, rows, heads, cap)
+    ws = _DECODE_WS.get(key)
+    if ws is None:
+        ws = _DECODE_WS[key] = torch.zeros(L.lib().cogv_attention_decode_workspace_bytes(rows, heads, cap), dtype=torch.uint8, device=qkv.device)
+    out = torch.empty((b, m, hp), dtype=qkv.dtype, device=qkv.device) if combine else None
+    d = L.AttnDecodeChunkDesc()
+    d.dtype, d.B, d.H, d.capacity, d.head_dim, d.m, d.scale = dt_code(qkv), b, heads, cap, 64, m, 0.125
+    d.qkv, d.qkv_rs = qkv.data_ptr(), qkv.stride(1)
+    d.cache, d.cache_bs, d.cache_rs = cache.data_ptr(), cache.stride(0), cache.stride(1)
+    d.out, d.out_rs = (out.data_ptr(), hp) if combine else (None, hp)
+    d.pos = pos_index.data_ptr()
+    d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
+    d.skip_combine = 0 if combine else 1
+    d.first = _decode_first(first, b, qkv.device)
+    L.check(L.lib().cogv_attention_decode_chunk(C.byref(d), _stream()), "cogv_attention_decode_chunk")
+    return out if combine else ws
+
+
 def kv_quantize_e4m3(kv, q, scale, slot0=0):
     """cogv_kv_quantize_e4m3: the 16-bit K | V rows a prefill leaves, kv [b, n, 2 * heads * 64] (batch and row strides free),
     into slots [slot0, slot0 + n) of an 8-bit cache: q [b, 2, heads, capacity, 64] uint8 (OCP E4M3 bytes; plane 0 keys, plane 1

@@ -333,6 +333,33 @@ typedef struct cogv_attn_decode_desc {
 } cogv_attn_decode_desc;
 size_t cogv_attention_decode_workspace_bytes(int B, int H, int capacity);
 int cogv_attention_decode(const cogv_attn_decode_desc* d, void* stream);
+/* Decode step of m tokens per cache row (generation/sampling.py:139-148 makes one model call per token, also for a token that
+ * is already known; a run of m known tokens is one call here).  Rows r = b * m + j, j = 0 ... m - 1, as the QKV projection of
+ * [B * m] hidden rows leaves them: qkv [B * m][3 * H * 64] (qkv_rs elements between consecutive rows), out [B * m][H * 64]
+ * (out_rs).  Row (b, j) is the token in slot *pos + j of cache row b and attends slots [first[b], *pos + j]; the keys / values
+ * of slots [*pos, *pos + j] are the chunk's own rows, taken from qkv, and all m of them are WRITTEN into slots [*pos, *pos + m).
+ * A slot at or past `capacity` is neither written nor attended, whatever *pos holds.  first: as in cogv_attn_decode_desc, per
+ * row (b, j) against its own slot (NULL: 0; negative: 0; beyond *pos + j: that slot only).  *pos stays device data and the
+ * cache loads are issued before it is read.  Grid, the 128 keys per split and the 66-float partials are those of
+ * cogv_attention_decode with B * m rows -- workspace: cogv_attention_decode_workspace_bytes(B * m, H, capacity); skip_combine,
+ * cogv_gemv_attn and cogv_gemv_attn_w8 (M = B * m) as there -- but a workgroup loads its 128 keys and values ONCE for the m
+ * queries.  Output, partials and cache are bit-identical to m successive cogv_attention_decode calls at *pos, *pos + 1, ...;
+ * m = 1 is that call.  The 8-bit cache has no such form.
+ * 1 (bad argument): m outside [1, 8], misaligned qkv / cache (16 B) / first (4 B), strides % 8, short workspace; 3
+ * (unsupported): other dtypes, head_dim != 64. */
+typedef struct cogv_attn_decode_chunk_desc {
+  int dtype; int B, H, capacity, head_dim;
+  int m;                             /* tokens per cache row, 1 ... 8 */
+  float scale;                       /* 1/sqrt(head_dim) */
+  const void* qkv; long long qkv_rs;
+  void* cache; long long cache_bs; int cache_rs;
+  void* out; long long out_rs;
+  const long long* pos;
+  void* workspace; size_t workspace_bytes;
+  int skip_combine;
+  const int* first;                  /* NULL, or int32 [B] */
+} cogv_attn_decode_chunk_desc;
+int cogv_attention_decode_chunk(const cogv_attn_decode_chunk_desc* d, void* stream);
 /* ------------------------------------------------------------------ 8-bit key/value cache for the decode step (OCP E4M3, one scale per head)
  * The decode attention requests every slot of the fixed-capacity cache on every step (generation/sampling.py:139-148: one
  * model call per generated token), so a step streams the whole cache.  Here the cache holds E4M3 bytes with one fp32 scale per

@@ -10,7 +10,9 @@ reference's three stages joined on the device -- eight candidates from generate_
 difference, peak allocated memory of each), ranked by rerank_generated, the best one magnified with fill=DeviceFiller.
 `--weights e4m3` (text -> image and `--super-resolution` legs): the device forms also run with the decode steps on 8-bit copies
 of the weights (generate_on_device / DeviceFiller `weights=`), timed next to the 16-bit ones.  `--kv e4m3`: the same legs with the
-8-bit key/value cache (`kv=`), alone or together with `--weights`.
+8-bit key/value cache (`kv=`), alone or together with `--weights`.  `--chunk C` (`--super-resolution` leg): the same image again in
+the same process with DeviceFiller(chunk=C) -- runs of given ids fed as chunk steps of C tokens -- next to the chunk=0 leg above:
+seconds per image, model calls, and ms per replay of the one-token and of the chunk graph.
 `--prompts G [--nb N]` (comma lists run several settings in one process: `--prompts 8,2 --nb 1,4`): G prompts of different text
 lengths x N candidates each (default 1) for one 1024-code image per row, on ONE decode graph (generate_batch_on_device) against
 the same prompts through generate_on_device one after another, in the same process; ms per generated token per prompt for each.
@@ -47,6 +49,7 @@ SR = "--super-resolution" in sys.argv
 SKIP_HOST = os.environ.get("MB_GENERATE_SKIP_HOST") == "1"
 W8 = sys.argv[sys.argv.index("--weights") + 1] if "--weights" in sys.argv else None
 KV8 = sys.argv[sys.argv.index("--kv") + 1] if "--kv" in sys.argv else None
+CHUNK = int(sys.argv[sys.argv.index("--chunk") + 1]) if "--chunk" in sys.argv else 0
 ids = IdSpace()
 # super-resolution windows reach 1305 positions: filling_sequence's memory must hold them all, as the decode graph does
 max_mem = 1408 if SR else 1089
@@ -88,6 +91,33 @@ if SR:
         assert big8.shape == (1, 4096) and int(big8.max()) < 8192
         print(f"DeviceFiller weights={W8} kv={KV8}: {t_w8:.2f} s (quantization + prefills + capture included), "
               f"{t_w8 / (replays + len(plans)) * 1e3:.2f} ms per model call; {t_dev / t_w8:.2f}x the 16-bit device form", flush=True)
+    if CHUNK:
+        filler_c = DeviceFiller(model, args, seed=1, chunk=CHUNK)
+        calls = []
+
+        def fill_c(model_, seq, args_, invalid_slices=None, tokenizer=None):
+            out = filler_c(model_, seq, args_, invalid_slices, tokenizer)
+            calls.append(filler_c.model_calls)
+            return out
+
+        torch.cuda.synchronize(); t0 = time.time()
+        big_c = magnify(model, ids, code, text_t, args, fill=fill_c)
+        torch.cuda.synchronize(); t_c = time.time() - t0
+        assert big_c.shape == (1, 4096) and int(big_c.max()) < 8192
+        dec = filler_c.dec
+
+        def replay_ms(graph, n=20):
+            dec.pos_index.fill_(1000)                   # replays scribble on slots past every window's run; none past the capacity
+            torch.cuda.synchronize(); t0 = time.time()
+            for _ in range(n):
+                graph.replay()
+            torch.cuda.synchronize()
+            return (time.time() - t0) / n * 1e3
+
+        print(f"DeviceFiller chunk={CHUNK}: {t_c:.2f} s per image (prefills + capture of both graphs included) against "
+              f"{t_dev:.2f} s with chunk=0 in this process ({t_dev / t_c:.3f}x); {sum(calls)} decode calls of which {dec.chunk_steps} "
+              f"chunk steps, against {replays}; one-token replay {replay_ms(dec.graph):.2f} ms, chunk replay "
+              f"{replay_ms(dec.graph_chunk):.2f} ms", flush=True)
     sys.exit(0)
 args = types.SimpleNamespace(temperature=1.0, top_k=200, top_p=0.0, is_sparse=0)
 
