@@ -203,6 +203,8 @@ SIGNATURES = {
     "cogv_gemv_ln_w8": (_i, [C.POINTER(GemmDesc), C.POINTER(LnPrologue), C.POINTER(W8Weight), _vp]),
     "cogv_gemv_attn_w8": (_i, [C.POINTER(GemmDesc), C.POINTER(W8Weight), _vp, _i, _i, _vp]),
     "cogv_gemv_plan": (_i, [_i, C.POINTER(GemmDesc), C.POINTER(W8Weight), _i, C.POINTER(C.c_int)]),
+    "cogv_gemm_rows": (_i, [C.POINTER(GemmDesc), _vp]),
+    "cogv_gemm_rows_plan": (_i, [C.POINTER(GemmDesc), C.POINTER(C.c_int)]),
     "cogv_kv_quantize_e4m3": (_i, [_i, _vp, _i64, _i64, _i, _i, _i, _vp, _i64, _vp, _i64, _i, _i, _vp]),
     "cogv_attention_decode_kv8": (_i, [C.POINTER(AttnDecodeKv8Desc), _vp]),
     "cogv_attention_decode_workspace_bytes": (_sz, [_i, _i, _i]),
@@ -292,4 +294,21 @@ def gemv_plan(kind, dtype, M, N, K, w8=False, nsplit=1, ldb=None):
         w.q, w.ldq, w.scale = d.B, d.ldb, 0x4000
     out = (C.c_int * GEMV_PLAN_INTS)(*([-1] * GEMV_PLAN_INTS))
     rc = lib().cogv_gemv_plan(kind, C.byref(d), C.byref(w) if w8 else None, nsplit, out)
+    return rc, list(out)
+
+
+GEMM_ROWS_PLAN_INTS = 10
+GEMM_ROWS_PLAN_FIELDS = ("row_groups", "waves_per_tile", "tiles", "weight_loads", "guarded", "x_staged", "threads", "grid", "lds", "pairs_in_flight")
+
+
+def gemm_rows_plan(dtype, M, N, K, desc=None):
+    """cogv_gemm_rows_plan for a contiguous product (or for the GemmDesc `desc` as it stands): (error code, the integers of
+    GEMM_ROWS_PLAN_FIELDS; all -1 where the call is refused).  Host only: the pointers are aligned stand-ins that nothing reads."""
+    d = desc
+    if d is None:
+        d = GemmDesc()
+        d.dtype, d.M, d.N, d.K, d.lda, d.ldb, d.ldc, d.splitk = dtype, M, N, K, K, K, N, 1
+        d.A, d.B, d.C = 0x1000, 0x2000, 0x3000
+    out = (C.c_int * GEMM_ROWS_PLAN_INTS)(*([-1] * GEMM_ROWS_PLAN_INTS))
+    rc = lib().cogv_gemm_rows_plan(C.byref(d), out)
     return rc, list(out)

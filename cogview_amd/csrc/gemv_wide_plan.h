@@ -1,0 +1,72 @@
+// Wide products of the decode step (1 .. 64 rows on 16-bit weights): the ONE class list and the ONE launch plan of
+// csrc/gemv_wide.hip's kernel.  Host code only.  cogv_gemm_rows asks gw_plan() before its launch, cogv_gemm_rows_plan answers from
+// the same function, and a unit of gemv_wide.hip turns the plan into its template instantiation by expanding the same list.
+#pragma once
+
+// The classes.  A product takes the FIRST row whose K range holds K: the class depends on K ALONE, so the association of a
+// column's sum -- which contraction slots a wave adds up, and the order the waves' partial tiles are summed in -- does not depend
+// on the row count, and a row's bits do not depend on the rows next to it.
+//   X(name, K from, K to, NWK, LP, guarded)
+//   NWK waves share a 16-column tile: wave kw takes the load PAIRS q = kw, kw + NWK, .. (a pair: contraction elements 64 q .. 64 q
+//   + 63, one 128-byte line of each weight row), LP of them at most;  guarded: K below the class's maximum (pairs past K are loaded
+//   from a clamped address and not multiplied).
+// Exact classes for the widths of the model family (h = 1024: K = 1024 / 4096; h = 2560: K = 2560 / 10240), guarded ones for any
+// other multiple of 512.
+#define GW_CLASSES(X)                      \
+  X(K1024,  1024,  1024,  4,  4,  false)   \
+  X(K2560,  2560,  2560,  8,  5,  false)   \
+  X(K4096,  4096,  4096,  16, 4,  false)   \
+  X(K10240, 10240, 10240, 16, 10, false)   \
+  X(G4,     512,   1024,  4,  4,  true)    \
+  X(G8,     512,   2560,  8,  5,  true)    \
+  X(G16,    512,   10240, 16, 10, true)
+
+#define GW_ENUM_ROW(NAME, ...) GWC_##NAME,
+enum GwClassId { GW_CLASSES(GW_ENUM_ROW) GWC_COUNT };
+#undef GW_ENUM_ROW
+
+struct GwClass { int k_from, k_to, nwk, lp, guard; };
+#define GW_ROW(NAME, KF, KT, NWK, LP, G) {KF, KT, NWK, LP, G},
+constexpr GwClass GW_CLASS_TABLE[GWC_COUNT] = {GW_CLASSES(GW_ROW)};
+#undef GW_ROW
+
+constexpr int GW_MAX_M = 64, GW_MIN_K = 512, GW_MAX_K = 10240;
+// Column tiles per workgroup.  The x rows are read straight from L2 as MFMA fragments, RG * 16 rows per 16 weight rows: with one
+// tile a workgroup of 4 row groups reads four times as many x bytes as weight bytes.  With two tiles a wave feeds one x fragment to
+// both, and the ratio halves -- taken from 2 row groups on wherever that still leaves 128 workgroups (N >= 4096: the QKV, h -> 4h
+// and logits products of the model family; their N = h products keep one tile and N / 16 workgroups).
+constexpr int GW_CT2_MIN_N = 4096;
+constexpr int gw_rg(int M) { return (M + 15) / 16; }
+constexpr int gw_ct(int rg, int N) { return rg >= 2 && N >= GW_CT2_MIN_N ? 2 : 1; }
+// Load pairs a wave keeps in flight.  A pair is 2 * (RG + CT) loads of 16 bytes per lane = 8 (RG + CT) registers; a wave of a
+// 16-wave workgroup has 128 registers, of an 8- or 4-wave one 256 (two workgroups of 4 waves per CU).  What is left after the
+// RG * CT accumulators of 4 registers and 40 for addresses and the epilogue goes to the ring, up to all LP pairs (then every load
+// of the wave is requested at the top, as in gemv.hip).
+constexpr int gw_depth(int nwk, int rg, int ct, int lp) {
+  const int d = ((nwk == 16 ? 128 : 256) - 4 * rg * ct - 40) / (8 * (rg + ct));
+  return d < 1 ? 1 : d > lp ? lp : d;
+}
+// Accumulator tiles summed per round of the tail: every wave writes that many partial tiles (1 KB each) to LDS, the first R waves
+// sum one tile each in wave order and finish it.  R <= NWK, at most 32 KB of partials; even wherever CT = 2 (a finishing wave
+// keeps one column tile through all rounds).
+constexpr int gw_round(int nwk, int tiles) {
+  const int cap = nwk < 32 / nwk ? nwk : 32 / nwk;
+  return tiles < cap ? tiles : cap;
+}
+constexpr int gw_lds(int nwk, int tiles) { return gw_round(nwk, tiles) * (nwk + 1) * 1024; }
+
+// The plan of one launch: cls and (rg, ct) name the instantiation.
+struct GwPlan { int rg, nwk, ct, lp, guard, depth, threads, grid, lds, cls; };
+
+// false: the wide kernel does not take the product (unsupported)
+inline bool gw_plan(int M, int N, int K, GwPlan& pl) {
+  if (M < 1 || M > GW_MAX_M || N < 8 || (N & 7) || K < GW_MIN_K || K > GW_MAX_K || (K & 511)) return false;
+  for (int i = 0; i < GWC_COUNT; ++i) {
+    const GwClass& c = GW_CLASS_TABLE[i];
+    if (K < c.k_from || K > c.k_to) continue;
+    const int rg = gw_rg(M), ct = gw_ct(rg, N), cols = 16 * ct;
+    pl = GwPlan{rg, c.nwk, ct, c.lp, c.guard, gw_depth(c.nwk, rg, ct, c.lp), 64 * c.nwk, (N + cols - 1) / cols, gw_lds(c.nwk, rg * ct), i};
+    return true;
+  }
+  return false;
+}

@@ -1052,6 +1052,36 @@ def w8_decode_supported(tr, batch):
     return None
 
 
+# The wide decode step (decode_layers(wide=True): 9 .. 64 rows, the five products as weight streams, ops.gemm_rows).  Read once:
+# COGV_DECODE_WIDE=0 keeps the step above 8 rows what it was (the tile kernels of ops.gemm) -- the other leg of tools/mb_decode.py.
+_DECODE_WIDE = _os.environ.get("COGV_DECODE_WIDE", "1") != "0"
+# The kernel takes 1 .. 64 rows; the step takes it from 9 rows up to _DECODE_WIDE_MAX_ROWS, the largest row count at which the
+# captured 4B step was measured faster than the switched-off step of the same process by more than the +-1 % spread in every run
+# (1.19x at 12 rows, 1.14x at 16, 1.04x at 24, 1.00x at 32, 0.94x at 64 -- with more row groups a workgroup pulls
+# several bytes of x fragments through its CU's L1 per weight byte).  COGV_DECODE_WIDE_MAX_ROWS (read once, at most 64) moves the bound.
+DECODE_WIDE_MIN_ROWS, DECODE_WIDE_KERNEL_ROWS = 9, 64
+_DECODE_WIDE_MAX_ROWS = min(DECODE_WIDE_KERNEL_ROWS, int(_os.environ.get("COGV_DECODE_WIDE_MAX_ROWS", "24")))
+
+
+def decode_wide_supported(tr, rows):
+    """The wide decode step at this row count: 16-bit weights on one model-parallel partition, 9 .. _DECODE_WIDE_MAX_ROWS rows, the
+    switch on, and every product the step issues (QKV, attention output, h -> 4h, 4h -> h, logits) taken by the library's own
+    launch plan (cogv_gemm_rows_plan: host only, nothing is touched).  The tied-logits product is asked with h columns: N decides
+    a grid, never whether a class takes the product."""
+    from . import _lib
+    if not _DECODE_WIDE or mp_world_size_or_1() != 1 or not DECODE_WIDE_MIN_ROWS <= rows <= _DECODE_WIDE_MAX_ROWS:
+        return False
+    att = tr.layers[0].attention
+    dt = att.query_key_value.weight.dtype
+    if dt not in (torch.float16, torch.bfloat16):
+        return False
+    h = tr.layers[0].input_layernorm.weight.shape[0]
+    f = tr.layers[0].mlp.dense_h_to_4h.weight.shape[0]
+    hp = att.num_attention_heads_per_partition * 64
+    code = _lib.BF16 if dt == torch.bfloat16 else _lib.F16
+    return all(_lib.gemm_rows_plan(code, rows, n, k)[0] == _lib.OK for n, k in ((3 * hp, h), (h, hp), (f, h), (h, f), (h, h)))
+
+
 def decode_chain(tr, h0, absmax0, slots, emb_weight, w8=None):
     """One decode step through all layers with FIVE launches per layer (round 3: the split-combine of the decode attention
     rides in the dense GEMV's prologue): QKV GEMV with [previous layer's
@@ -1109,20 +1139,22 @@ def decode_chain(tr, h0, absmax0, slots, emb_weight, w8=None):
     return logits.view(b, s, logits.shape[1])
 
 
-def decode_layers(tr, h0, absmax0, slots, emb_weight, w8=None):
+def decode_layers(tr, h0, absmax0, slots, emb_weight, w8=None, wide=False):
     """One decode step layer by layer: _layer_forward's inference chain on b * m <= 8 rows (every Sandwich-LN its own launch,
     decode attention with its combine, four plain skinny products per layer), the final LayerNorm and the tied-logits product.
     h0 [b, m, h] -> logits [b, m, V]; m > 1: a chunk step, as in decode_chain.  w8 (W8Weights): the products read the 8-bit copies
     (emb_weight is not read).  What a decoder runs above COGV_DECODE_CHAIN_MAX_ROWS for the 8-bit weights and for chunk steps, and
-    the comparison path of the chain."""
+    the comparison path of the chain.  wide=True (16-bit weights, up to 64 rows; decode_wide_supported): the five products go to
+    ops.gemm_rows, the weight-streaming form above 8 rows; nothing else changes."""
     b, s, h = h0.shape
     rows = b * s
     dev = h0.device
     if w8 is None:
-        gemm, logits_w = ops.gemm, emb_weight
+        gemm, logits_w = (ops.gemm_rows if wide else ops.gemm), emb_weight
         operands = ((l.attention.query_key_value.weight, l.attention.dense.weight, l.mlp.dense_h_to_4h.weight, l.mlp.dense_4h_to_h.weight)
                     for l in tr.layers)
     else:
+        assert not wide, "the wide step streams the 16-bit weights"
         gemm, logits_w, operands = ops.gemm_w8, w8.emb, w8.layers
     x, absmax_x = (h0 if h0.is_contiguous() else h0.contiguous()), absmax0
     for layer, slot, (w_qkv, w_dense, w_h4h, w_4hh) in zip(tr.layers, slots, operands):

@@ -155,6 +155,9 @@ class GraphDecoder:
                 return F_.decode_chain(tr, h, h._cogv_absmax, self.slots, self.gpt.word_embeddings.weight, w8=self.w8)
             if self.w8 is not None:
                 return F_.decode_layers_w8(tr, h, h._cogv_absmax, self.slots, self.w8)
+            if F_.decode_wide_supported(tr, self.batch):
+                # 9 .. 64 rows on the 16-bit weights: layer by layer, the five products as weight streams (ops.gemm_rows)
+                return F_.decode_layers(tr, h, h._cogv_absmax, self.slots, self.gpt.word_embeddings.weight, wide=True)
             for layer, slot in zip(tr.layers, self.slots):
                 h = layer(h, 0, mem=slot)
             out = tr.final_layernorm(h)

@@ -338,6 +338,27 @@ def _skinny_desc(out, K, bias, gelu, absmax):
     return d
 
 
+def gemm_rows(a, w, bias=None, gelu=False, absmax=None, out=None):
+    """The wide product of a decode step (cogv_gemm_rows): out [M, N] = epilogue(a [M, K] . w [N, K]^T + bias) for 1 <= M <= 64
+    rows on a 16-bit weight, streamed once like gemm's skinny case (N % 8 == 0, 512 <= K <= 10240, K % 512 == 0).  Rows of a, w
+    and a given `out` may be strided.  Shapes outside raise: there is no other kernel behind this one."""
+    _need_gpu(a, w)
+    assert a.dim() == 2 and w.dim() == 2 and a.stride(1) == 1 and w.stride(1) == 1 and a.dtype == w.dtype
+    M, K = a.shape
+    N, Kw = w.shape
+    assert K == Kw, f"contraction mismatch {K} vs {Kw}"
+    assert bias is None or bias.dtype == a.dtype
+    if out is None:
+        out = torch.empty((M, N), dtype=a.dtype, device=a.device)
+    assert out.shape == (M, N) and out.dtype == a.dtype and out.stride(1) == 1
+    d = _skinny_desc(out, K, bias, gelu, absmax)
+    d.ldc = out.stride(0)
+    d.A, d.lda = a.data_ptr(), a.stride(0)
+    d.B, d.ldb = w.data_ptr(), w.stride(0)
+    L.check(L.lib().cogv_gemm_rows(C.byref(d), _stream()), "cogv_gemm_rows")
+    return out
+
+
 def _ln_prologue(z, gamma, beta, eps, z_absmax, post, residual, want_t):
     """(cogv_ln_prologue, t [M, K] or None) of gemv_ln / gemv_ln_w8; z and (post-LN form) gamma share the product's 16-bit type."""
     # fp32 residual stream (see sandwich_ln_fwd): the residual of the post-LN form, or z itself in the plain-input form

@@ -189,6 +189,24 @@ int cogv_gemv_attn_w8(const cogv_gemm_desc* d, const cogv_w8_weight* w, const vo
 #define COGV_GEMV_PLAN_INTS 11
 int cogv_gemv_plan(int kind, const cogv_gemm_desc* d, const cogv_w8_weight* w, int nsplit, int out[COGV_GEMV_PLAN_INTS]);
 
+/* Wide decode step: F.linear at mpu/layers.py:243,319 and the tied logits model/gpt2_modeling.py:117 inside a decode step of up
+ * to 64 rows (9 and more: the reference's --max-inference-batch-size defaults to 12), as a weight stream like cogv_gemm's skinny
+ * case: every byte of B is requested once, by one workgroup.  C[M][N] = epilogue(A[M][K] . B[N][K]^T) on 16-bit weights with
+ * 1 <= M <= 64, N >= 8, N % 8 == 0, 512 <= K <= 10240, K % 512 == 0, trans_a = trans_b = 0, flags BIAS | GELU | ABSMAX (the skinny
+ * case's epilogue, rounding point for rounding point), no aux, 16-bit C.  1 (bad argument) as cogv_gemm reports it, and for a
+ * leading dimension shorter than its row; 3 (unsupported) for every other descriptor: this entry point has no other kernel.
+ * Deterministic; a row's bits do not depend on the other rows of the call; no floating-point atomics. */
+int cogv_gemm_rows(const cogv_gemm_desc* d, void* stream);
+/* Host-only query (no device is touched, no pointer of d is dereferenced): what cogv_gemm_rows would launch for this descriptor,
+ * from the function the launch uses (csrc/gemv_wide_plan.h), and exactly the error it would return (out is left untouched then).
+ * out = { row groups RG = ceil(M / 16) (accumulator tiles per column tile), waves per 16-column tile NWK (they split the
+ * contraction), column tiles per workgroup (1 | 2), weight loads of 16 bytes per lane, guarded (1: a class for every K up to its
+ * maximum), contraction elements of x staged in LDS per phase (0: x is read from L2 as MFMA fragments, never staged), threads per
+ * workgroup, workgroups, dynamic LDS bytes (the partial tiles of the tail), load pairs a wave keeps in flight (= weight loads / (2 *
+ * tiles): every load is requested at the top) }. */
+#define COGV_GEMM_ROWS_PLAN_INTS 10
+int cogv_gemm_rows_plan(const cogv_gemm_desc* d, int out[COGV_GEMM_ROWS_PLAN_INTS]);
+
 /* ------------------------------------------------------------------ Sandwich-LN
  * y = [residual +] LayerNorm_{eps*(amax/8)^2}(x) * gamma + beta ; amax = *absmax_in (NULL: plain LN).
  * replaces mpu/sparse_transformer.py:40-44 (LayerNorm = FusedLayerNorm(x / (x.abs().max()/8))) and the

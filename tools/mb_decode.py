@@ -4,7 +4,10 @@ step re-projects K and V of the whole memory).  `--weights e4m3`: in the same ru
 weights (GraphDecoder(weights="e4m3")) next to the 16-bit one -- ms per token of each, and the relative L2 / largest difference
 of their logits on the step that was timed.  `--kv e4m3`: the same comparison for the 8-bit key/value cache
 (GraphDecoder(kv="e4m3")) against the 16-bit cache, both on the weights `--weights` names (default: 16-bit).  MB_DECODE_SKIP_EAGER=1
-skips the eager timing of the first decoder."""
+skips the eager timing of the first decoder.  MB_DECODE_BATCH=b: b rows (up to 64).  From 9 rows on, three captured steps are timed
+in turn in this process, on the cache `--kv` names: the wide step (ops.gemm_rows), the step with the switch off (what
+COGV_DECODE_WIDE=0 runs: the tile kernels) and the 8-row step -- ms per step and per row of each, and the relative L2 / largest
+difference of the first two's logits on the timed step."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 os.environ.setdefault("MASTER_ADDR", "127.0.0.1"); os.environ.setdefault("MASTER_PORT", "29589")
@@ -21,6 +24,9 @@ pos = torch.arange(pre + steps, device="cuda").unsqueeze(0)
 from cogview_amd.generation import GraphDecoder
 model = FP16_Module(GPT2Model(L, V, h, heads, 0.1, 0.1, 0.1, 1089, 1089, False).cuda(), dtype=torch.bfloat16, keep_half_outputs=True).eval()
 B = int(os.environ.get("MB_DECODE_BATCH", "1"))
+if B >= 9:       # the wide step is measured at every row count its kernel takes, not only where the decoder takes it by default
+    from cogview_amd import functional as F_
+    F_._DECODE_WIDE_MAX_ROWS = F_.DECODE_WIDE_KERNEL_ROWS
 tokens, pos = tokens.expand(B, -1).contiguous(), pos.expand(B, -1).contiguous()
 dec = GraphDecoder(model, batch=B, capacity=1152)
 with torch.no_grad():
@@ -69,6 +75,73 @@ def _report(ms, last, a, b, what, tail=""):
           f"max |difference| {(lg8 - lg16).abs().max().item():.3e} (max |logit| {lg16.abs().max().item():.3f})", flush=True)
 
 
+def _captured(d, wide):
+    """the prefilled decoder d captured and brought to the first decoder's history; wide=False: captured with
+    functional._DECODE_WIDE off, i.e. the step a process started under COGV_DECODE_WIDE=0 runs (above 8 rows: the tile kernels of
+    ops.gemm)"""
+    from cogview_amd import functional as F_
+    saved = F_._DECODE_WIDE
+    F_._DECODE_WIDE = bool(wide) and saved
+    try:
+        with torch.no_grad():
+            d.capture()
+            for t in range(dec.length - d.length):
+                d.step(tokens[:d.batch, pre:pre + 1], pos[:d.batch, pre:pre + 1])
+    finally:
+        F_._DECODE_WIDE = saved
+    return d
+
+
+def _prefilled(batch, kv):
+    d = GraphDecoder(model, batch=batch, capacity=1152, kv=kv)
+    with torch.no_grad():
+        d.prefill(tokens[:batch, :pre], pos[:batch, :pre])
+    return d
+
+
+def _time_legs(legs):
+    """the captured decoders of `legs` (name -> decoder), timed in turn, twice.  Returns (ms per step, last logits) by name."""
+    ms, last = {}, {}
+    for rep in range(2):
+        for name, d in legs.items():
+            tk, ps = tokens[:d.batch, pre:pre + 1], pos[:d.batch, pre:pre + 1]
+            d.length -= 24
+            for t in range(4):
+                d.step(tk, ps)
+            torch.cuda.synchronize(); t0 = time.time()
+            for t in range(20):
+                lg = d.step(tk, ps)
+                nxt = lg[:, -1].float().argmax(-1)
+            torch.cuda.synchronize()
+            ms.setdefault(name, []).append((time.time() - t0) / 20 * 1e3)
+            last[name] = lg.float().clone()
+    return ms, last
+
+
+if B >= 9:
+    # the wide step (9 .. 64 rows: the five products of a layer as weight streams, ops.gemm_rows) against the step with the switch
+    # off and against the 8-row step, all captured, in this process; on the cache format --kv names
+    from cogview_amd import functional as F_
+    wide_on = F_.decode_wide_supported(model.module.transformer, B)
+    # Every prefill BEFORE the captures: above 8 rows the switched-off step runs split-K tile kernels, whose shared workspace
+    # (ops.workspace, regrown on demand) is baked into its graph -- a later prefill that needs a larger one (8 x 1024 rows: 252 MB
+    # for the 4h -> h product) would replace the buffer under the captured graph.
+    made = [_prefilled(B, KVFMT) if KVFMT is not None else dec, _prefilled(B, KVFMT), _prefilled(8, KVFMT)]
+    legs = {"wide": _captured(made[0], True) if KVFMT is not None else dec, "COGV_DECODE_WIDE=0": _captured(made[1], False),
+            "8 rows": _captured(made[2], True)}
+    del made
+    with torch.no_grad():
+        ms, last = _time_legs(legs)
+    cache = f"{KVFMT or '16-bit'} cache"
+    w, n, e = (min(ms[k]) for k in ("wide", "COGV_DECODE_WIDE=0", "8 rows"))
+    print(f"captured graph, {B} rows, {cache}: wide step {w:.2f} ms ({'gemm_rows' if wide_on else 'NOT taken: the step of the other leg'}); "
+          f"COGV_DECODE_WIDE=0 step {n:.2f} ms ({n / w:.2f}x); 8-row step {e:.2f} ms; per row {w / B:.3f} / {n / B:.3f} / {e / 8:.3f} ms "
+          f"(runs {['%.2f' % v for v in ms['wide']]} / {['%.2f' % v for v in ms['COGV_DECODE_WIDE=0']]} / {['%.2f' % v for v in ms['8 rows']]})", flush=True)
+    a, b = last["COGV_DECODE_WIDE=0"], last["wide"]
+    print(f"logits wide vs COGV_DECODE_WIDE=0 on the timed step: rel-L2 {((b - a).norm() / a.norm()).item():.3e}, "
+          f"max |difference| {(b - a).abs().max().item():.3e} (max |logit| {a.abs().max().item():.3f})", flush=True)
+    del legs, last
+    torch.cuda.empty_cache()
 if WFMT is not None:
     dec8 = GraphDecoder(model, batch=B, capacity=1152, weights=WFMT)
     with torch.no_grad():

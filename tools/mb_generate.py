@@ -182,7 +182,8 @@ if "--prompts" in sys.argv:
               f"{t_seq / t_batch:.2f}x", flush=True)
     sys.exit(0)
 
-for nb in (1, 8):
+# (`--nb 16,32,64` without `--prompts`: this leg at those row counts -- above 8 rows the decode graph holds the wide step)
+for nb in ([int(x) for x in sys.argv[sys.argv.index("--nb") + 1].split(",")] if "--nb" in sys.argv else (1, 8)):
     seq = text + [ids["[BASE]"], ids["[BOI1]"]] + [-1] * 1024
     add_interlacing_beam_marks(seq, nb=nb, period=3000)
     seq = torch.tensor(seq, device="cuda")
@@ -195,7 +196,7 @@ for nb in (1, 8):
     ref = out if SKIP_HOST else filling_sequence(model, seq.clone(), args)
     torch.cuda.synchronize(); t_host = float("nan") if SKIP_HOST else time.time() - t0
     assert ref.shape == out.shape
-    print(f"batch {nb}: generate_on_device {t_dev:.2f} s = {t_dev / 1024 * 1e3:.2f} ms/token (prefill + capture included); "
+    print(f"batch {nb}: generate_on_device {t_dev:.2f} s = {t_dev / 1024 * 1e3:.2f} ms/token = {t_dev / nb:.3f} s per image (prefill + capture included); "
           f"filling_sequence kv_cache=True {t_host:.2f} s = {t_host / 1024 * 1e3:.2f} ms/token; speed-up {t_host / t_dev:.1f}x",
           flush=True)
     if W8 or KV8:
