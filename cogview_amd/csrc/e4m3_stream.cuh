@@ -1,4 +1,4 @@
-// The 8-bit format of the decode step (weights: quantize.hip, gemv.hip; key/value cache: attention_kv8.hip) and the load its
+// The 8-bit format of the decode step (weights: quantize.hip, gemv.hip; key/value cache: attention_decode.hip) and the load its
 // streams are read with.  One place for both: the producers and the consumers below agree to the bit because they call these.
 //
 // THE E4M3 RULE.  A group of elements (a weight row; the 64 elements of one head of one cache slot) becomes OCP E4M3 bytes

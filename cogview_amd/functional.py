@@ -984,18 +984,15 @@ def decode_attention(qkv, slot, heads, combine=True):
     kw = {} if combine else {"combine": False}
     if getattr(slot, "first", None) is not None:
         kw["first"] = slot.first
+    kv8 = getattr(slot, "scale", None) is not None
     if qkv.dim() == 3 and qkv.shape[1] > 1:
-        if getattr(slot, "scale", None) is not None:
+        if kv8:
             raise NotImplementedError("the 8-bit key/value cache serves one-token decode steps only: use kv=None for chunk steps")
-        res = ops.attention_decode_chunk(qkv, slot.cache, slot.pos_index, heads, **kw)
-        slot.out = slot.cache
-        return res
-    if getattr(slot, "scale", None) is not None:
-        res = ops.attention_decode_kv8(qkv, slot, slot.pos_index, heads, **kw)
-        slot.out = slot.q
-        return res
-    res = ops.attention_decode(qkv, slot.cache, slot.pos_index, heads, **kw)
-    slot.out = slot.cache
+        op = ops.attention_decode_chunk
+    else:
+        op = ops.attention_decode_kv8 if kv8 else ops.attention_decode
+    res = op(qkv, slot if kv8 else slot.cache, slot.pos_index, heads, **kw)
+    slot.out = slot.q if kv8 else slot.cache
     return res
 
 

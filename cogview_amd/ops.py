@@ -669,19 +669,21 @@ def _decode_first(first, b, dev):
     return first.data_ptr()
 
 
-def _decode_desc(d, qkv, pos_index, b, heads, cap, combine, first):
-    """What the two decode attentions share: (descriptor with every field but the cache's, out or None, workspace).  The
-    workspace (partial results of the key splits) is kept per (device, shape): fixed addresses, so the call is replayable
-    inside a captured graph."""
+def _decode_desc(d, qkv, pos_index, b, heads, cap, combine, first, rows=None, out_shape=None):
+    """What the decode attentions share: (descriptor with every field but the cache's, out or None, workspace).  The
+    workspace (partial results of the key splits) is kept per (device, rows, heads, capacity): fixed addresses, so the call is
+    replayable inside a captured graph.  rows, out_shape: of a chunk step (b * m rows, out [b, m, heads * 64]; the caller sets
+    m and the row strides); None: one row per cache row."""
     hp = heads * 64
-    key = (qkv.device.index, b, heads, cap)
+    key = (qkv.device.index, rows or b, heads, cap)
     ws = _DECODE_WS.get(key)
     if ws is None:
-        ws = _DECODE_WS[key] = torch.zeros(L.lib().cogv_attention_decode_workspace_bytes(b, heads, cap), dtype=torch.uint8, device=qkv.device)
-    out = torch.empty((b, 1, hp), dtype=qkv.dtype, device=qkv.device) if combine else None
+        ws = _DECODE_WS[key] = torch.zeros(L.lib().cogv_attention_decode_workspace_bytes(rows or b, heads, cap), dtype=torch.uint8, device=qkv.device)
+    out = torch.empty(out_shape or (b, 1, hp), dtype=qkv.dtype, device=qkv.device) if combine else None
     d.dtype, d.B, d.H, d.capacity, d.head_dim, d.scale = dt_code(qkv), b, heads, cap, 64, 0.125
-    d.qkv, d.qkv_bs = qkv.data_ptr(), qkv.stride(0)
-    d.out, d.out_bs = (out.data_ptr(), out.stride(0)) if combine else (None, hp)
+    d.qkv, d.out = qkv.data_ptr(), out.data_ptr() if combine else None
+    if out_shape is None:
+        d.qkv_bs, d.out_bs = qkv.stride(0), hp
     d.pos = pos_index.data_ptr()
     d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
     d.skip_combine = 0 if combine else 1
@@ -721,21 +723,9 @@ def attention_decode_chunk(qkv, cache, pos_index, heads, combine=True, first=Non
     m = qkv.shape[1]
     assert qkv.stride(2) == 1 and (b == 1 or qkv.stride(0) == m * qkv.stride(1)), "rows b * m + j one stride apart"
     assert cache.stride(2) == 1 and pos_index.dtype == torch.int64
-    rows = b * m
-    key = (qkv.device.index, rows, heads, cap)
-    ws = _DECODE_WS.get(key)
-    if ws is None:
-        ws = _DECODE_WS[key] = torch.zeros(L.lib().cogv_attention_decode_workspace_bytes(rows, heads, cap), dtype=torch.uint8, device=qkv.device)
-    out = torch.empty((b, m, hp), dtype=qkv.dtype, device=qkv.device) if combine else None
-    d = L.AttnDecodeChunkDesc()
-    d.dtype, d.B, d.H, d.capacity, d.head_dim, d.m, d.scale = dt_code(qkv), b, heads, cap, 64, m, 0.125
-    d.qkv, d.qkv_rs = qkv.data_ptr(), qkv.stride(1)
+    d, out, ws = _decode_desc(L.AttnDecodeChunkDesc(), qkv, pos_index, b, heads, cap, combine, first, rows=b * m, out_shape=(b, m, hp))
+    d.m, d.qkv_rs, d.out_rs = m, qkv.stride(1), hp
     d.cache, d.cache_bs, d.cache_rs = cache.data_ptr(), cache.stride(0), cache.stride(1)
-    d.out, d.out_rs = (out.data_ptr(), hp) if combine else (None, hp)
-    d.pos = pos_index.data_ptr()
-    d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
-    d.skip_combine = 0 if combine else 1
-    d.first = _decode_first(first, b, qkv.device)
     L.check(L.lib().cogv_attention_decode_chunk(C.byref(d), _stream()), "cogv_attention_decode_chunk")
     return out if combine else ws
 

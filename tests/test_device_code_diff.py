@@ -90,3 +90,18 @@ def test_resource_usage_remarks_lose_their_location():
          "remark: csrc/gemv.hip:389:0:     TotalSGPRs: 34 [-Rpass-analysis=kernel-resource-usage]\n"
          "remark: csrc/gemv.hip:389:0:     LDS Size [bytes/block]: 5120 [-Rpass-analysis=kernel-resource-usage]\n")
     assert D.parse_remarks(a) == D.parse_remarks(b) == {"_Z1kv": "TotalSGPRs: 34; LDS Size [bytes/block]: 5120"}
+
+
+def test_pooled_units_pair_a_kernel_that_moved_to_another_unit():
+    # --rev-unit / --tree-unit: three units of the revision against two of the tree; the kernel is paired by name wherever it lives
+    dem = {"_Z1kv": "void (anonymous namespace)::k()", "_Z1jv": "void (anonymous namespace)::j()"}
+    k, j = D.split_functions(OLD.splitlines()), D.split_functions(NEW.replace("_Z1kv", "_Z1jv").splitlines())
+    old = D._pooled([(k, {}, dem), ({}, {}, {}), (j, {}, dem)], ())
+    new = D._pooled([({}, {}, {}), ({**k, **j}, {}, dem)], ())
+    assert sorted(old) == sorted(new) == ["void j()", "void k()"]
+    res = D.compare(old, new)
+    assert res["common"] == ["void j()", "void k()"] and not (res["only_old"] or res["only_new"] or res["text"] or res["desc"] or res["remark"])
+    # a name that two units of one side define has no single partner
+    import pytest
+    with pytest.raises(SystemExit):
+        D._pooled([(k, {}, dem), (k, {}, dem)], ())

@@ -1,6 +1,7 @@
 """Is the device code of a revision and of the working tree the same?  (host Python only: cross-compiles, needs no GPU)
 
     python tools/device_code_diff.py REV [unit ...] [--map 'REGEX=REPL' ...]
+    python tools/device_code_diff.py REV --rev-unit U [--rev-unit U ...] --tree-unit U [--tree-unit U ...]
 
 Compiles the named units of build.units() (object names without .o: gemv_0, gemm, quantize ..; default: all) twice -- from
 `git archive REV` and from the working tree -- with build.FLAGS plus -Rpass-analysis=kernel-resource-usage -save-temps=obj, and
@@ -10,6 +11,8 @@ appearance: the kernels of a unit come out in another order when a template chan
 name without "(anonymous namespace)::"; --map rewrites REV's names first (re.sub, repeatable, applied in order) when a change
 renames what the kernels are instantiated on.  Unpaired symbols are listed; a differing kernel is shown with the difference
 of its per-opcode counts (none: register naming or instruction order only).  Exit status 1 if anything differs.
+--rev-unit / --tree-unit (repeatable; units of plain .hip sources, which need not exist on the other side) pool the kernels of
+the units named per side and pair across the pool: for kernels that moved between units.  The report is then one section.
 """
 import argparse
 import collections
@@ -174,22 +177,67 @@ def _table(funcs, remarks, dem, maps):
     return out
 
 
+def _report(title, old, new, rev):
+    """prints one section: the tables old / new of _table() compared.  -> True if anything differs"""
+    res = compare(old, new)
+    nk = [sum(1 for v in t.values() if v[1] is not None) for t in (old, new)]
+    nlines = sum(len(old[k][0]) for k in res["common"])
+    sha = [hashlib.sha256("\n".join(k + "\n" + "\n".join(t[k][0]) for k in res["common"]).encode()).hexdigest()[:16] for t in (old, new)]
+    print("== %s" % title)
+    print("   kernels: %s %d, working tree %d; functions in all: %d, %d; paired: %d" % (rev, nk[0], nk[1], len(old), len(new), len(res["common"])))
+    print("   only in %s: %s" % (rev, res["only_old"]))
+    print("   only in the working tree: %s" % res["only_new"])
+    norem = [k for k in res["common"] if old[k][1] is not None and (old[k][2] is None or new[k][2] is None)]
+    print("   kernels whose resource-usage remark differs: %d%s" % (len(res["remark"]), "; WITHOUT a remark: %s" % norem if norem else ""))
+    print("   kernels whose .amdhsa descriptor differs: %d" % len(res["desc"]))
+    print("   kernels whose instruction text differs (%d instruction lines compared per symbol, labels renumbered): %d" % (nlines, len(res["text"])))
+    print("   sha256 of the paired per-symbol text: %s %s  working tree %s" % (rev, sha[0], sha[1]))
+    for k in res["common"][:1]:
+        print("   e.g. %s | %s" % (k, new[k][2]))
+    for k in res["remark"]:
+        print("   remark  %s\n      %s: %s\n      tree: %s" % (k, rev, old[k][2], new[k][2]))
+    for k in res["desc"]:
+        d0, d1 = old[k][1] or [], new[k][1] or []
+        print("   descriptor  %s\n      %s" % (k, "\n      ".join("%s -> %s" % p for p in zip(d0, d1) if p[0] != p[1])))
+    for k, dc in res["text"]:
+        print("   text  %s\n      opcode counts (tree - %s): %s" % (k, rev, dc or "equal (register naming or order only)"))
+    return bool(res["only_old"] or res["only_new"] or res["remark"] or res["desc"] or res["text"] or norem or nk[0] != nk[1])
+
+
+def _pooled(built, maps):
+    """one table of several units' kernels; a pair name that two units of a side define cannot be paired"""
+    out = {}
+    for b in built:
+        t = _table(*b, maps)
+        dup = sorted(set(out) & set(t))
+        if dup:
+            raise SystemExit("defined in two units of one side: %s" % dup)
+        out.update(t)
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("rev")
     ap.add_argument("units", nargs="*")
     ap.add_argument("--map", action="append", default=[], metavar="REGEX=REPL", help="rewrite REV's demangled kernel names (re.sub)")
+    ap.add_argument("--rev-unit", action="append", default=[], metavar="UNIT", help="pooled form: a unit of REV (repeatable)")
+    ap.add_argument("--tree-unit", action="append", default=[], metavar="UNIT", help="pooled form: a unit of the working tree (repeatable)")
     a = ap.parse_args(argv)
     sys.path.insert(0, ROOT)
     from cogview_amd.csrc import build as B
     maps = [parse_map(m) for m in a.map]
     units = [(src, os.path.basename(obj)[:-2], extra) for src, obj, extra in B.units()]
+    pooled = bool(a.rev_unit or a.tree_unit)
+    if pooled and (a.units or not (a.rev_unit and a.tree_unit)):
+        raise SystemExit("the pooled form wants --rev-unit and --tree-unit, and no positional units")
     names = a.units or [u for _, u, _ in units]
-    unknown = sorted(set(names) - {u for _, u, _ in units})
+    unknown = sorted(set(a.tree_unit if pooled else names) - {u for _, u, _ in units})
     if unknown:
         raise SystemExit("no such unit: %s (units: %s)" % (" ".join(unknown), " ".join(u for _, u, _ in units)))
     rev = subprocess.run(["git", "rev-parse", "--short", a.rev], cwd=ROOT, capture_output=True, text=True, check=True).stdout.strip()
     csrc_rel, inc_rel = os.path.relpath(B.HERE, ROOT), os.path.relpath(B.INCLUDE, ROOT)
+    by_name = {u: (src, extra) for src, u, extra in units}
     with tempfile.TemporaryDirectory() as td:
         old_root = os.path.join(td, "rev")
         os.makedirs(old_root)
@@ -197,45 +245,37 @@ def main(argv=None):
         subprocess.run(["tar", "-x", "-C", old_root], input=tar, check=True)
         old_flags = [{"-I" + B.HERE: "-I" + os.path.join(old_root, csrc_rel), "-I" + B.INCLUDE: "-I" + os.path.join(old_root, inc_rel)}.get(f, f)
                      for f in B.FLAGS]
-        jobs = []
-        for src, unit, extra in units:
-            if unit in names:
-                jobs.append((os.path.join(old_root, os.path.relpath(src, ROOT)), old_flags, extra, os.path.join(td, "old_" + unit)))
-                jobs.append((src, B.FLAGS, extra, os.path.join(td, "new_" + unit)))
+
+        def old_job(unit):
+            # a unit the working tree no longer has is a plain source of REV: UNIT.hip, no extra flags
+            src, extra = by_name.get(unit, (os.path.join(B.HERE, unit + ".hip"), []))
+            old_src = os.path.join(old_root, os.path.relpath(src, ROOT))
+            if not os.path.exists(old_src):
+                raise SystemExit("%s has no %s" % (rev, os.path.relpath(src, ROOT)))
+            return old_src, old_flags, extra, os.path.join(td, "old_" + unit)
+
+        new_job = lambda unit: (by_name[unit][0], B.FLAGS, by_name[unit][1], os.path.join(td, "new_" + unit))
+        if pooled:
+            jobs = [old_job(u) for u in a.rev_unit] + [new_job(u) for u in a.tree_unit]
+        else:
+            jobs = [j for _, unit, _ in units if unit in names for j in (old_job(unit), new_job(unit))]
         with concurrent.futures.ThreadPoolExecutor(max_workers=min(MAX_COMPILES, os.cpu_count() or 1, len(jobs))) as ex:
             built = list(ex.map(_compile_unit, jobs))
     print("device code of %s against the working tree, cross-compiled for %s (%s)" % (rev, B.ARCH, " ".join(B.FLAGS[:4] + EXTRA)))
     for spec in a.map:
         print("name map (applied to %s's demangled kernel names): %s" % (rev, spec))
     differs = False
-    for i, (src, unit, extra) in enumerate(u for u in units if u[1] in names):
-        old, new = _table(*built[2 * i], maps), _table(*built[2 * i + 1], ())
-        res = compare(old, new)
-        nk = [sum(1 for v in t.values() if v[1] is not None) for t in (old, new)]
-        nlines = sum(len(old[k][0]) for k in res["common"])
-        sha = [hashlib.sha256("\n".join(k + "\n" + "\n".join(t[k][0]) for k in res["common"]).encode()).hexdigest()[:16] for t in (old, new)]
-        print("== %s (%s %s)" % (unit, os.path.basename(src), " ".join(extra)))
-        print("   kernels: %s %d, working tree %d; functions in all: %d, %d; paired: %d" % (rev, nk[0], nk[1], len(old), len(new), len(res["common"])))
-        print("   only in %s: %s" % (rev, res["only_old"]))
-        print("   only in the working tree: %s" % res["only_new"])
-        norem = [k for k in res["common"] if old[k][1] is not None and (old[k][2] is None or new[k][2] is None)]
-        print("   kernels whose resource-usage remark differs: %d%s" % (len(res["remark"]), "; WITHOUT a remark: %s" % norem if norem else ""))
-        print("   kernels whose .amdhsa descriptor differs: %d" % len(res["desc"]))
-        print("   kernels whose instruction text differs (%d instruction lines compared per symbol, labels renumbered): %d" % (nlines, len(res["text"])))
-        print("   sha256 of the paired per-symbol text: %s %s  working tree %s" % (rev, sha[0], sha[1]))
-        for k in res["common"][:1]:
-            print("   e.g. %s | %s" % (k, new[k][2]))
-        for k in res["remark"]:
-            print("   remark  %s\n      %s: %s\n      tree: %s" % (k, rev, old[k][2], new[k][2]))
-        for k in res["desc"]:
-            d0, d1 = old[k][1] or [], new[k][1] or []
-            print("   descriptor  %s\n      %s" % (k, "\n      ".join("%s -> %s" % p for p in zip(d0, d1) if p[0] != p[1])))
-        for k, dc in res["text"]:
-            print("   text  %s\n      opcode counts (tree - %s): %s" % (k, rev, dc or "equal (register naming or order only)"))
-        differs |= bool(res["only_old"] or res["only_new"] or res["remark"] or res["desc"] or res["text"] or norem or nk[0] != nk[1])
+    if pooled:
+        n = len(a.rev_unit)
+        differs = _report("%s: %s | working tree: %s (kernels pooled per side)" % (rev, " ".join(a.rev_unit), " ".join(a.tree_unit)),
+                          _pooled(built[:n], maps), _pooled(built[n:], ()), rev)
+    else:
+        for i, (src, unit, extra) in enumerate(u for u in units if u[1] in names):
+            differs |= _report("%s (%s %s)" % (unit, os.path.basename(src), " ".join(extra)), _table(*built[2 * i], maps), _table(*built[2 * i + 1], ()), rev)
     print("RESULT: device code %s" % ("DIFFERS" if differs else "identical"))
     return 1 if differs else 0
 
 
 if __name__ == "__main__":
     sys.exit(main())
+
