@@ -148,6 +148,7 @@ class SampleDesc(C.Structure):
         ("tok", C.c_void_p), ("pos", C.c_void_p), ("pos_index", C.c_void_p), ("table", C.c_void_p), ("capacity", C.c_int),
         ("out_tokens", C.c_void_p), ("out_len", C.c_int64), ("out_base", C.c_int64),
         ("counter", C.c_void_p),
+        ("given_stride", C.c_int64),
         ("given", C.c_void_p),
     ]
 

@@ -16,7 +16,9 @@
 //          whose inclusive prefix mass exceeds u * Z wins.  Every sum has a fixed order: same (seed, offset) -> same ids.
 //   given  decode mode with a table of given ids (magnify's windows, generation/sampling.py DeviceFiller): where
 //          given[*pos_index + 1] >= 0 that id is fed instead of drawn -- the logits are not read, logp = 0, scores and the
-//          probabilities untouched; the bookkeeping and the counter are those of a draw.
+//          probabilities untouched; the bookkeeping and the counter are those of a draw.  With given_stride > 0 every row
+//          reads its own table, given[row * given_stride + *pos_index + 1] (DeviceBatchFiller: several images on one decode
+//          graph), and rows that are fed and rows that draw share a launch.
 #include "common.cuh"
 #include "cogview_hip.h"
 
@@ -244,13 +246,15 @@ __global__ __launch_bounds__(SB) void sample_kernel(cogv_sample_desc d) {
   const int row = blockIdx.x, t = threadIdx.x;
   const T* src = reinterpret_cast<const T*>(d.logits) + (size_t)row * (size_t)d.row_stride;
   const int64_t off = d.offset ? *d.offset : 0;
-  // a given id for the position this launch fills (decode mode only, checked by the host): the same address for every
-  // thread, so the branch below is uniform across the workgroup and is taken before any barrier.  A given id is published
-  // by thread 0 with logp 0 and no score; one publish site for both paths keeps the register allocation of the draw
+  // a given id for the position this launch fills (decode mode only, checked by the host), from the shared table
+  // (given_stride 0) or from this row's own: the same address for every thread of the workgroup -- a workgroup is one row --
+  // so the branch below is uniform across it and is taken before any barrier, while other rows of the launch may take the
+  // other side.  A given id is published by thread 0 with logp 0 and no score; one publish site for both paths keeps the
+  // register allocation of the draw
   int64_t fed = -1;
   if (d.given) {
     const int64_t p1 = *d.pos_index + 1;
-    if (p1 >= 0 && p1 < d.capacity) fed = d.given[p1];
+    if (p1 >= 0 && p1 < d.capacity) fed = d.given[(int64_t)row * d.given_stride + p1];
   }
   int64_t id = fed;
   float lp = 0.f;
@@ -283,6 +287,7 @@ extern "C" int cogv_sample_logits(const cogv_sample_desc* d, void* stream) {
   if (d->row_stride != 0 && d->row_stride < d->vocab) return COGV_ERR_ARG;
   if (d->pos_index && (!d->counter || (d->table && d->capacity <= 0) || (d->out_tokens && d->out_len <= 0))) return COGV_ERR_ARG;
   if (d->given && (!d->pos_index || d->capacity <= 0)) return COGV_ERR_ARG;
+  if (d->given && (d->given_stride < 0 || (d->given_stride > 0 && d->given_stride < d->capacity))) return COGV_ERR_ARG;
   if (d->rows > 65535) return COGV_ERR_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
   switch (d->dtype) {

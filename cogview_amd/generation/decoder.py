@@ -312,10 +312,13 @@ class SamplingDecoder(GraphDecoder):
         """allow: (lo, hi) range of ids that may be drawn (None: all); out_tokens: int64 [batch, n] that receives the id
         drawn for sequence position out_base + j in column j (None: not recorded); given: int64 [capacity] device buffer,
         by sequence position, of ids to feed instead of drawing (-1: draw), shared by all rows -- device data, so one
-        captured graph serves any table written into it (None: every position is drawn)."""
+        captured graph serves any table written into it (None: every position is drawn).  Or int64 [batch, capacity]: one
+        table per row, by slot (several images on one ragged decoder: row b is fed where given[b, slot] >= 0; chunk steps need
+        the same slots given in every row)."""
         dev = self.tok.device
         assert out_tokens is None or (out_tokens.dtype == torch.int64 and out_tokens.shape[0] == self.batch)
-        assert given is None or (given.dtype == torch.int64 and given.numel() >= self.cap and given.device == dev)
+        assert given is None or (given.dtype == torch.int64 and given.shape[-1] >= self.cap and given.device == dev)
+        assert given is None or given.dim() == 1 or (given.dim() == 2 and given.shape[0] == self.batch and given.stride(1) == 1)
         self.sampling = dict(temperature=float(temperature), top_k=int(top_k), top_p=float(top_p), allow=allow, seed=int(seed))
         self.offset = torch.zeros(1, dtype=torch.int64, device=dev)        # generator offset: one per draw
         self.ids = torch.zeros(self.batch, dtype=torch.int64, device=dev)
@@ -339,8 +342,8 @@ class SamplingDecoder(GraphDecoder):
     def _step_chunk(self):
         """A chunk step inside a sampling run, all on the device: row 0 is the token the previous step published, rows 1 ... C - 1 are
         the given ids of the next C - 1 positions (the plan guarantees they are set; the clamps only keep a warm-up run at the end
-        of the cache inside the tables).  After the layers the decoder state is advanced by C - 1 -- what C - 1 one-token steps that
-        fed a given id would have left: write slot, positions, generator offset (one per position in both modes), the visible
+        of the cache inside the tables); with a table per row, each row's own.  After the layers the decoder state is advanced by
+        C - 1 -- what C - 1 one-token steps that fed a given id would have left: write slot, positions, generator offset (one per position in both modes), the visible
         slots, the output columns -- and the unchanged sampler runs on the last row's logits, exactly as if the one-token step at
         that position had just run."""
         if self.sampling is None:
@@ -349,7 +352,10 @@ class SamplingDecoder(GraphDecoder):
         C, j = self.chunk, self.chunk_j
         at = self.pos_index + j                                                            # sequence positions of the chunk's rows
         self.tok_chunk[:, :1].copy_(self.tok)
-        self.tok_chunk[:, 1:].copy_(self.given.index_select(0, at[1:].clamp(max=self.cap - 1)).clamp(min=0).unsqueeze(0).expand(self.batch, C - 1))
+        if self.given.dim() == 1:
+            self.tok_chunk[:, 1:].copy_(self.given.index_select(0, at[1:].clamp(max=self.cap - 1)).clamp(min=0).unsqueeze(0).expand(self.batch, C - 1))
+        else:                                                                              # every row's own ids
+            self.tok_chunk[:, 1:].copy_(self.given.index_select(1, at[1:].clamp(max=self.cap - 1)).clamp(min=0))
         max_pos = self.gpt.transformer.position_embeddings.weight.shape[0] - 1
         self.pos_chunk.copy_((self.pos + j).clamp(max=max_pos))
         logits = super()._step_chunk()
@@ -359,8 +365,11 @@ class SamplingDecoder(GraphDecoder):
         self.table.copy_(torch.where(new.unsqueeze(0), slots.to(torch.int32).unsqueeze(0), self.table))
         if self.out_tokens is not None:
             cols = torch.arange(self.out_tokens.shape[1], dtype=torch.long, device=p0.device) + self.out_base
-            fed = self.given.index_select(0, cols.clamp(0, self.cap - 1))
-            self.out_tokens.copy_(torch.where(((cols > p0) & (cols < p0 + C)).unsqueeze(0), fed.unsqueeze(0), self.out_tokens))
+            if self.given.dim() == 1:
+                fed = self.given.index_select(0, cols.clamp(0, self.cap - 1)).unsqueeze(0)
+            else:
+                fed = self.given.index_select(1, cols.clamp(0, self.cap - 1))
+            self.out_tokens.copy_(torch.where(((cols > p0) & (cols < p0 + C)).unsqueeze(0), fed, self.out_tokens))
         self.pos_index.add_(C - 1)
         self.pos.add_(C - 1)
         self.offset.add_(C - 1)

@@ -312,13 +312,19 @@ def _plan_context(seq_l, tokenizer):
 
 def _plan_allow(invalid, vocab):
     """The ids `invalid` leaves drawable, as the sampler's one (lo, hi) range."""
-    keep = torch.ones(vocab, dtype=torch.bool)
-    for sl in invalid:
-        keep[sl] = False
-    idx = keep.nonzero().flatten().tolist()
-    if not idx or idx[-1] - idx[0] + 1 != len(idx):
+    kept, at = [], 0                                   # interval arithmetic on the host: a planner allocates no tensor
+    for lo, hi, step in sorted(sl.indices(vocab) for sl in invalid):
+        assert step == 1
+        if lo >= hi:
+            continue
+        if lo > at:
+            kept.append((at, lo))
+        at = max(at, hi)
+    if at < vocab:
+        kept.append((at, vocab))
+    if len(kept) != 1:
         raise NotImplementedError("the drawable ids are not one contiguous range: use filling_sequence")
-    return idx[0], idx[-1] + 1
+    return kept[0]
 
 
 def _plan_capacity(length):
@@ -413,17 +419,55 @@ def plan_chunk_steps(given, context, replays, C):
     return widths
 
 
+def plan_device_batch_fill(seqs_l, tokenizer, vocab):
+    """Host planning of DeviceBatchFiller for G token lists: plan_device_fill per sequence.  The contexts may differ in length
+    (they are right-aligned, as plan_device_batch's), but counted from its own first mark every sequence must have the same
+    `replays`, the same given positions inside the run and the same drawable range: one decode graph takes the same step --
+    feed or draw, one token or a chunk -- for every row.  The nine magnify windows of different images are so by construction.
+    Otherwise NotImplementedError naming DeviceFiller, which takes the sequences one after another.  The given IDS differ from
+    row to row (cogv_sample_desc.given_stride); the [ROI2] offset may differ too.
+    Returns dict(contexts, pads, P, replays, run = replays + 1, nb = 1, rows = G, allow, offsets, trailing, capacity, given,
+    pattern): P / pads as plan_device_batch's; capacity for P + replays + 1 slots; given[g] the table of row g BY SLOT, capacity
+    long -- given[g][pads[g] + i] = the entry of sequence position i in plan_device_fill's table, -1 elsewhere; pattern: the
+    shared table by slot (0 where every row is given an id, -1 elsewhere) -- plan_chunk_steps(pattern, P, replays, C) are the
+    widths of the run; trailing[g]: the given ids of sequence g after its last mark."""
+    if not seqs_l:
+        raise ValueError("no sequences")
+    plans = [plan_device_fill(list(seq_l), tokenizer, vocab) for seq_l in seqs_l]
+    inside = [[i - p["context"] for i, t in enumerate(p["given"]) if t >= 0] for p in plans]
+    for what, values in (("`replays`", [p["replays"] for p in plans]), ("the given positions inside the run", inside),
+                         ("`allow`", [p["allow"] for p in plans])):
+        if any(v != values[0] for v in values):
+            raise NotImplementedError(f"the sequences differ in {what}: one decode graph feeds or draws at the same step, from the same "
+                                      f"range, for every row -- use DeviceFiller per sequence")
+    contexts = [p["context"] for p in plans]
+    P, replays = max(contexts), plans[0]["replays"]
+    pads = [P - n for n in contexts]
+    capacity = _plan_capacity(P + replays + 1)
+    given = [[-1] * capacity for _ in plans]
+    for row, p, pad in zip(given, plans, pads):
+        n = p["context"]
+        row[pad + n:pad + n + replays + 1] = p["given"][n:n + replays + 1]
+    pattern = [-1] * capacity
+    for k in inside[0]:
+        pattern[P + k] = 0
+    return dict(contexts=contexts, pads=pads, P=P, replays=replays, run=replays + 1, nb=1, rows=len(plans), allow=plans[0]["allow"],
+                offsets=[p["offset"] for p in plans], trailing=[p["trailing"] for p in plans], capacity=capacity, given=given,
+                pattern=pattern)
+
+
 class _DeviceRun:
     """What the device entry points share: the refusals, ONE lazily built SamplingDecoder with its format keywords, the sampler
     armed for (temperature, top_k, top_p, allow) -- baked into a capture, so other values re-arm it and drop the graph, while the
     generator offset keeps counting -- and the run itself: start, capture once, generate.  generate_on_device and
-    generate_batch_on_device use one for one call; DeviceGenerator and DeviceFiller keep theirs call after call.
-    .out [batch, width] receives the id drawn for sequence position out_base + j in column j; .given (DeviceFiller) is the sampler's
-    given table."""
+    generate_batch_on_device use one for one call; DeviceGenerator, DeviceFiller and DeviceBatchFiller keep theirs call after call.
+    .out [batch, width] receives the id drawn for sequence position out_base + j in column j; .given (DeviceFiller: [capacity],
+    DeviceBatchFiller: [rows, capacity]) is the sampler's given table.  batch: the decoder's rows where the caller knows them
+    before the first call (the refusal rule then also judges chunk= and weights= at that row count)."""
     given = None
 
-    def __init__(self, model, args, seed=0, capture=True, weights=None, kv=None, ragged=False, chunk=0):
-        decoder.refuse_unsupported(weights, kv, ragged, args=args, model=model, use="filling_sequence", chunk=chunk)
+    def __init__(self, model, args, seed=0, capture=True, weights=None, kv=None, ragged=False, chunk=0, batch=None):
+        decoder.refuse_unsupported(weights, kv, ragged, args=args, model=model, use="filling_sequence", chunk=chunk, batch=batch)
         self.model, self.seed, self.capture, self.ragged, self.chunk = model, int(seed), capture, ragged, int(chunk)
         self.formats = {"weights": weights}           # only the keywords that are set: a default build issues the call it always did
         if kv is not None:
@@ -649,3 +693,103 @@ class DeviceFiller(_DeviceRun):
         out = seq.clone()
         out[n:n + replays + 1] = self.out[0, n:n + replays + 1].to(seq.device)
         return out.unsqueeze(0)
+
+
+class DeviceBatchFiller(_DeviceRun):
+    """DeviceFiller for several sequences at once on ONE ragged SamplingDecoder and ONE captured decode graph that are reused
+    call after call: the same window of several images (magnify_batch: `fill=DeviceBatchFiller(model, args, rows=G)`), as
+    DeviceGenerator is generate_on_device for several prompts.  A decode step is a weight stream, so `rows` images cost little
+    more per step than one.  `filler(seqs)` takes 1 <= G <= rows sequences that plan_device_batch_fill accepts (contexts of any
+    lengths, right-aligned in the caches; the same marks and given positions counted from each first mark, with every row's OWN
+    given ids); spare rows repeat the last sequence and are dropped from the result.  Per call: every row's given table goes to
+    the device by slot ([rows, capacity]; the sampler reads row r's at r * given_stride), one ragged prefill draws every row's
+    first mark, then one replay per later slot up to the last mark -- each row is fed or draws on its own.  The output buffer is
+    [rows, capacity] with column = slot.  Returns the list of G completed rows [1, len(seq_g)] on each sequence's device; given
+    ids after the last mark are kept from the input.  After a call .scores is [G] fp32 and .model_calls the decode steps, as
+    DeviceFiller's.  Temperature, top-k / top-p and the drawable range are baked into the capture (a call with other values
+    re-arms and captures again); the generator offset keeps counting across calls.
+    capture / weights / kv as DeviceFiller's.  chunk=C: runs of given ids are fed as chunk steps on a second graph (rows * C <= 8
+    rows per step, 16-bit cache only).  Above 8 rows the decoder takes the wide step (9 ... 24 rows) or the tile kernels by
+    itself; weights="e4m3" covers up to 8 rows, so it is refused above them.  Dense attention, one model-parallel partition,
+    fp16 / bf16, P + replays + 1 <= capacity slots."""
+
+    def __init__(self, model, args, rows, capacity=1408, seed=0, capture=True, weights=None, kv=None, chunk=0):
+        super().__init__(model, args, seed, capture, weights, kv, ragged=True, chunk=chunk, batch=rows)
+        if rows < 1:
+            raise ValueError(f"rows = {rows} must be positive")
+        self.size(rows, capacity)
+        self.rows, self.args = self.batch, args
+        self.scores = None
+        self.model_calls = 0
+
+    def _buffers(self, dev):
+        self.out = torch.zeros((self.rows, self.capacity), dtype=torch.long, device=dev)
+        self.given = torch.full((self.rows, self.capacity), -1, dtype=torch.long, device=dev)
+
+    def __call__(self, seqs, args=None, tokenizer=None):
+        """seqs: list of 1-D tensors (filling_sequence's marks, nb = 1); args: the sampling arguments of this call (default: the
+        constructor's).  Returns the list of completed rows [1, len(seq_g)]."""
+        args = args if args is not None else self.args
+        decoder.refuse_unsupported(args=args, use="filling_sequence")
+        tokenizer = tokenizer if tokenizer is not None else IdSpace()
+        seqs = list(seqs)
+        if not 1 <= len(seqs) <= self.rows:
+            raise ValueError(f"{len(seqs)} sequences: this filler was built for 1 ... {self.rows}")
+        assert all(seq.dim() == 1 for seq in seqs)
+        G = len(seqs)
+        filled = seqs + [seqs[-1]] * (self.rows - G)                      # spare rows repeat the last sequence
+        plan = plan_device_batch_fill([seq.tolist() for seq in filled], tokenizer, self.vocab())
+        P, replays = plan["P"], plan["replays"]
+        if P + replays + 1 > self.capacity:
+            raise NotImplementedError(f"{P + replays + 1} slots exceed this filler's {self.capacity} decode slots: use DeviceFiller "
+                                      f"per sequence or a larger capacity")
+        dec = self.arm(args, plan["allow"])
+        tokens, position_ids = _batch_inputs(filled, plan, dec.tok.device)
+        width = min(plan["capacity"], self.capacity)                      # (entries past P + replays are -1)
+        table = torch.full((self.rows, self.capacity), -1, dtype=torch.long)
+        table[:, :width] = torch.tensor(plan["given"], dtype=torch.long)[:, :width]
+        self.given.copy_(table)                       # before start_ragged(): its draw reads the entries of slot P (-1)
+        if self.chunk:
+            widths = plan_chunk_steps(plan["pattern"], P, replays, self.chunk)
+            self.model_calls = len(widths)
+            scores = self.run(replays, tokens, position_ids, plan["pads"], widths=widths)
+        else:
+            self.model_calls = replays
+            scores = self.run(replays, tokens, position_ids, plan["pads"])
+        self.scores = scores[:G].to(seqs[0].device)
+        res = []
+        for g, (seq, n) in enumerate(zip(seqs, plan["contexts"])):
+            out = seq.clone()
+            out[n:n + replays + 1] = self.out[g, P:P + replays + 1].to(seq.device)
+            res.append(out.unsqueeze(0))
+        return res
+
+
+def magnify_batch(model, tokenizer, codes, texts, args, fill=None):
+    """magnify for G images at once (the reference's super-resolution task walks a file of images one after another,
+    generate_samples.py generate_images_continually; post-selection keeps several candidates per prompt).  codes: [G, 1024] or a
+    list of G 1-D tensors of 1024 codes; texts: list of G 1-D tensors of any lengths.  The nine windows run in magnify's order;
+    window w of ALL images is one call `fill(seqs, args, tokenizer=tokenizer)` with the G window sequences, which returns the
+    list of G completed rows [1, len(seq_g)] -- DeviceBatchFiller(model, args, rows=G) does it on one decode graph (the windows
+    of different images differ in their ids, not in where the marks are).  Default `fill`: filling_sequence per sequence.
+    Returns [G, 4096] codes."""
+    if fill is None:
+        def fill(seqs, args_, tokenizer=None):
+            return [filling_sequence(model, seq, args_, tokenizer=tokenizer) for seq in seqs]
+    codes = list(codes)
+    G = len(codes)
+    if len(texts) != G:
+        raise ValueError(f"{G} code maps but {len(texts)} texts")
+    maps = [code.view(32, 32) for code in codes]
+    dev = maps[0].device
+    midfix = torch.tensor([tokenizer[m] for m in ('[EOI1]', '[ROI2]', '[POS0]', '[BASE]', '[BOI2]')], device=dev)
+    big = torch.full((G, 64, 64), -1, dtype=torch.long, device=dev)
+    for bi, bj, lines in _MAGNIFY_WINDOWS:
+        contexts = [torch.cat([text.to(dev), m[8 * bi: 8 * (bi + 2), 8 * bj: 8 * (bj + 2)].reshape(-1), midfix], dim=0)
+                    for text, m in zip(texts, maps)]
+        seqs = [torch.cat([context, big[g, 16 * bi: 16 * bi + lines, 16 * bj: 16 * (bj + 2)].reshape(-1)], dim=0)
+                for g, context in enumerate(contexts)]
+        done = fill(seqs, args, tokenizer=tokenizer)
+        for g, (context, row) in enumerate(zip(contexts, done)):
+            big[g, 16 * bi: 16 * bi + lines, 16 * bj: 16 * (bj + 2)] = row[0, len(context):].view(lines, 32)
+    return big.view(G, 4096)

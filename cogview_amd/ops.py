@@ -1139,7 +1139,9 @@ def sample_logits(logits, *, temperature=1.0, top_k=0, top_p=0.0, allow=None, se
     filtered distribution [rows, vocab] fp32.
     decode: dict of the decode graph's buffers (generation/decoder.py SamplingDecoder): tok, pos, pos_index, table, counter,
     out_tokens (optional), out_base, given (optional: int64 [>= capacity] by sequence position, shared by all rows; where
-    given[*pos_index + 1] >= 0 that id is fed instead of drawn, with logp 0 and no score).
+    given[*pos_index + 1] >= 0 that id is fed instead of drawn, with logp 0 and no score.  Or int64 [rows, >= capacity] with
+    a contiguous last dimension: one table per row, the row stride taken from the tensor -- row r is fed where
+    given[r, *pos_index + 1] >= 0 and draws elsewhere, whatever the other rows do).
     Returns (ids, logp, probs or None).  Allocates nothing when every output is given (what a captured graph needs)."""
     v = logits.shape[-1]
     src = logits.reshape(-1, v) if logits.dim() != 2 else logits
@@ -1190,7 +1192,14 @@ def sample_logits(logits, *, temperature=1.0, top_k=0, top_p=0.0, allow=None, se
             assert out.dtype == torch.int64 and out.is_contiguous() and out.shape[0] == n
             d.out_tokens, d.out_len, d.out_base = out.data_ptr(), out.shape[1], int(decode["out_base"])
         given = decode.get("given")
-        if given is not None:
+        if given is not None and given.dim() == 2:
+            stride = given.stride(0) if n > 1 else given.shape[1]         # (one row: its stride is never applied)
+            if (given.dtype != torch.int64 or given.stride(1) != 1 or given.shape[0] != n or given.shape[1] < d.capacity
+                    or stride < given.shape[1] or given.device != dev):
+                raise ValueError(f"given: want an int64 tensor [{n}, >= {d.capacity}] with a contiguous last dimension on {dev}, "
+                                 f"got {tuple(given.shape)}")
+            d.given, d.given_stride = given.data_ptr(), stride
+        elif given is not None:
             if given.dtype != torch.int64 or not given.is_contiguous() or given.numel() < d.capacity or given.device != dev:
                 raise ValueError(f"given: want a contiguous int64 tensor of >= {d.capacity} elements on {dev}")
             d.given = given.data_ptr()

@@ -524,10 +524,13 @@ int cogv_cast_flat_back(int dtype, const float* src_f32, void* dst_half, size_t 
  *   tok[row] = id; pos[row] += 1; table[row][p + 1] = p + 1 (if < capacity); out_tokens[row][p + 1 - out_base] = id (if in
  *   [0, out_len)); then the last workgroup to finish sets *pos_index = p + 1 and *offset += 1 and re-zeroes *counter, a
  *   zero-initialised device word owned by this call site.  With these a replayed decode graph generates one token per replay.
- * Given ids (decode mode only; NULL: none): given int64 [capacity], indexed by sequence position, shared by all rows.  Where
- *   given[p + 1] >= 0 that id is fed instead of drawn (a position filling_sequence copies from its input): the logits are
- *   not read, ids[row] = tok[row] = out_tokens[row][p + 1 - out_base] = given[p + 1], logp[row] = 0, scores and probs are
- *   left as they are; pos / table / *pos_index / *offset advance exactly as for a draw. */
+ * Given ids (decode mode only; NULL: none): given int64 [capacity], indexed by sequence position, shared by all rows
+ *   (given_stride = 0), or one table per row, given int64 [rows][given_stride] with given_stride >= capacity (several images
+ *   on one decode graph, generation/sampling.py DeviceBatchFiller: every row carries its own given ids, indexed by slot).
+ *   With g = given[row * given_stride + p + 1]: where g >= 0 that id is fed to this row instead of drawn (a position
+ *   filling_sequence copies from its input): the logits are not read, ids[row] = tok[row] = out_tokens[row][p + 1 - out_base]
+ *   = g, logp[row] = 0, scores and probs are left as they are; pos / table / *pos_index / *offset advance exactly as for a
+ *   draw.  Every row decides for itself: in one launch some rows may be fed while the others draw. */
 typedef struct cogv_sample_desc {
   int dtype; int rows; int vocab; int64_t row_stride;
   const void* logits;
@@ -537,6 +540,7 @@ typedef struct cogv_sample_desc {
   int64_t* tok; int64_t* pos; int64_t* pos_index; int32_t* table; int capacity;
   int64_t* out_tokens; int64_t out_len; int64_t out_base;
   uint32_t* counter;
+  int64_t given_stride;                  /* elements between the rows' given tables; 0: one table shared by all rows */
   const int64_t* given;
 } cogv_sample_desc;
 int cogv_sample_logits(const cogv_sample_desc* d, void* stream);

@@ -13,6 +13,9 @@ of the weights (generate_on_device / DeviceFiller `weights=`), timed next to the
 8-bit key/value cache (`kv=`), alone or together with `--weights`.  `--chunk C` (`--super-resolution` leg): the same image again in
 the same process with DeviceFiller(chunk=C) -- runs of given ids fed as chunk steps of C tokens -- next to the chunk=0 leg above:
 seconds per image, model calls, and ms per replay of the one-token and of the chunk graph.
+`--super-resolution --images 1,4,8,16` (alone: no other leg runs): G images of different text lengths on ONE decode graph
+(magnify_batch with DeviceBatchFiller(rows=G)), also rows=2 chunk=4 and rows=4 chunk=2, against images one after another
+(magnify with DeviceFiller, chunk=0 and chunk=8, timed at the start and at the end of the process); seconds per image for each.
 `--prompts G [--nb N]` (comma lists run several settings in one process: `--prompts 8,2 --nb 1,4`): G prompts of different text
 lengths x N candidates each (default 1) for one 1024-code image per row, on ONE decode graph (generate_batch_on_device) against
 the same prompts through generate_on_device one after another, in the same process; ms per generated token per prompt for each.
@@ -38,7 +41,7 @@ import torch.distributed as dist
 dist.init_process_group("nccl", init_method="env://", world_size=1, rank=0)
 from cogview_amd import mpu
 from cogview_amd.fp16 import FP16_Module
-from cogview_amd.generation import (DeviceFiller, IdSpace, add_interlacing_beam_marks, filling_sequence, generate_batch_on_device,
+from cogview_amd.generation import (DeviceBatchFiller, DeviceFiller, IdSpace, magnify_batch, add_interlacing_beam_marks, filling_sequence, generate_batch_on_device,
                                     generate_on_device,
                                     inverse_prompt_score, inverse_prompt_score_on_device, magnify, plan_device_fill,
                                     post_selection_rows, rerank_generated)
@@ -61,6 +64,79 @@ if SR:
     args = types.SimpleNamespace(temperature=1.02, top_k=200, top_p=0.0, is_sparse=0)
     code = torch.randint(0, 8192, (1024,), device="cuda")
     text_t = torch.tensor(text, device="cuda")
+    if "--images" in sys.argv:
+        # several images per decode graph (magnify_batch + DeviceBatchFiller) against one image after another (magnify +
+        # DeviceFiller), all in this process.  Every filler is warmed on the first window of its first image (prefill, capture of
+        # its graphs, first-use allocations) and then timed over whole images; the one-image fillers are timed over one image each
+        # at the start AND at the end of the process (their per-image time does not depend on how many images follow; the two
+        # readings show the drift inside the process).
+        Gs = [int(x) for x in sys.argv[sys.argv.index("--images") + 1].split(",")]
+        gen = torch.Generator().manual_seed(7)
+        midfix = torch.tensor([ids[m] for m in ("[EOI1]", "[ROI2]", "[POS0]", "[BASE]", "[BOI2]")], device="cuda")
+
+        def images(G):                                                         # text lengths 20, 18, 23, 21, 26, ...
+            codes = torch.randint(0, 8192, (G, 1024), generator=gen).cuda()
+            return codes, [torch.randint(8192, 58192, (20 + 3 * (g // 2) - 2 * (g % 2),), generator=gen).cuda() for g in range(G)]
+
+        def first_window(code, txt):
+            return torch.cat([txt, code.view(32, 32)[:16, :16].reshape(-1), midfix, torch.full((18 * 32,), -1, dtype=torch.long, device="cuda")])
+
+        def timed(fn):
+            torch.cuda.synchronize(); t0 = time.time()
+            out = fn()
+            torch.cuda.synchronize()
+            return out, time.time() - t0
+
+        def one_after_another(chunk, n_images, tag):
+            f = DeviceFiller(model, args, seed=1, chunk=chunk)
+            codes, texts = images(n_images)
+            f(model, first_window(codes[0], texts[0]), args, tokenizer=ids)                   # warm-up
+            calls = []
+
+            def fill(model_, seq, args_, invalid_slices=None, tokenizer=None):
+                out = f(model_, seq, args_, invalid_slices, tokenizer)
+                calls.append(f.model_calls)
+                return out
+
+            big, t = timed(lambda: [magnify(model, ids, c_, t_, args, fill=fill) for c_, t_ in zip(codes, texts)])
+            assert all(b.shape == (1, 4096) and int(b.min()) >= 0 and int(b.max()) < 8192 for b in big)
+            print(f"images one after another ({tag}): DeviceFiller chunk={chunk}, {n_images} image(s): {t / n_images:.2f} s per image, "
+                  f"{sum(calls) // n_images} decode calls per image, {t / (sum(calls) + 9 * n_images) * 1e3:.2f} ms per model call", flush=True)
+            del f
+            torch.cuda.empty_cache()
+            return t / n_images
+
+        def batched(G, chunk=0):
+            f = DeviceBatchFiller(model, args, rows=G, seed=1, chunk=chunk)
+            codes, texts = images(G)
+            f([first_window(c_, t_) for c_, t_ in zip(codes, texts)], tokenizer=ids)         # warm-up
+            calls = []
+
+            def fill(seqs_, args_, tokenizer=None):
+                out = f(seqs_, args_, tokenizer=tokenizer)
+                calls.append(f.model_calls)
+                return out
+
+            big, t = timed(lambda: magnify_batch(model, ids, codes, texts, args, fill=fill))
+            assert big.shape == (G, 4096) and int(big.min()) >= 0 and int(big.max()) < 8192 and torch.isfinite(f.scores).all()
+            assert G == 1 or len({tuple(b.tolist()) for b in big}) == G
+            print(f"images on one decode graph: DeviceBatchFiller rows={G} chunk={chunk}: {t:.2f} s for {G} image(s) = {t / G:.2f} s per image, "
+                  f"{sum(calls)} decode calls, {t / (sum(calls) + 9) * 1e3:.2f} ms per model call", flush=True)
+            del f
+            torch.cuda.empty_cache()
+            return t / G
+
+        base = {c_: [one_after_another(c_, 1, "start")] for c_ in (0, 8)}
+        per_image = {(G, 0): batched(G) for G in Gs}
+        for G, c_ in ((2, 4), (4, 2)):
+            per_image[(G, c_)] = batched(G, c_)
+        for c_ in (0, 8):
+            base[c_].append(one_after_another(c_, 1, "end"))
+        best = min(per_image, key=per_image.get)
+        print("seconds per image: " + ", ".join(f"rows={G}{f' chunk={c_}' if c_ else ''} {t:.2f}" for (G, c_), t in per_image.items())
+              + f"; one after another chunk=0 {base[0][0]:.2f} / {base[0][1]:.2f}, chunk=8 {base[8][0]:.2f} / {base[8][1]:.2f} (start / end); "
+              f"best rows={best[0]} chunk={best[1]}: {min(base[8]) / per_image[best]:.2f}x the chunk=8 filler", flush=True)
+        sys.exit(0)
     seqs = []
     filler = DeviceFiller(model, args, seed=1)
 
