@@ -238,6 +238,10 @@ SIGNATURES = {
     "cogv_sample_logits": (_i, [C.POINTER(SampleDesc), _vp]),
     "cogv_score_targets": (_i, [C.POINTER(ScoreDesc), _vp]),
     "cogv_conv1x1_to_rgb_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), _vp]),
+    "cogv_resample_coeffs": (_i, [_i, _i, _vp, _vp, _vp, _i]),
+    "cogv_image_prep_plan": (_i, [_i, _i, _i, C.POINTER(C.c_int)]),
+    "cogv_image_prep_u8": (_i, [_vp, _sz, _vp, _vp, _vp, _sz, _i, _i, _vp, _vp, _vp]),
+    "cogv_sr_patches_nhwc4_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
 }
 
 _lib = None
@@ -313,3 +317,28 @@ def gemm_rows_plan(dtype, M, N, K, desc=None):
     out = (C.c_int * GEMM_ROWS_PLAN_INTS)(*([-1] * GEMM_ROWS_PLAN_INTS))
     rc = lib().cogv_gemm_rows_plan(C.byref(d), out)
     return rc, list(out)
+
+
+IMAGE_PREP_PLAN_INTS = 10
+IMAGE_PREP_PLAN_FIELDS = ("nh", "nw", "top", "left", "taps_h", "taps_v", "band_rows", "seg_cols", "lds_rows", "lds_bytes")
+IMAGE_PREP_MAX_TAPS = 65
+
+
+def image_prep_plan(H, W, S):
+    """cogv_image_prep_plan: (error code, dict of IMAGE_PREP_PLAN_FIELDS; empty where the image is refused) of what
+    cogv_image_prep_u8 does with one H x W image at size S.  Host only."""
+    out = (C.c_int * IMAGE_PREP_PLAN_INTS)(*([-1] * IMAGE_PREP_PLAN_INTS))
+    rc = lib().cogv_image_prep_plan(H, W, S, out)
+    return rc, dict(zip(IMAGE_PREP_PLAN_FIELDS, out)) if rc == OK else {}
+
+
+def resample_coeffs(n_in, n_out, max_taps=IMAGE_PREP_MAX_TAPS):
+    """cogv_resample_coeffs: (error code, xmin [n_out], count [n_out], k [n_out, max_taps]) as int32 numpy arrays (None where
+    refused): Pillow's bilinear tables of one axis n_in -> n_out.  Host only."""
+    import numpy as np
+    if n_out <= 0 or max_taps <= 0:
+        return ERR_ARG, None, None, None
+    xmin, count = np.zeros(n_out, np.int32), np.zeros(n_out, np.int32)
+    k = np.zeros((n_out, max_taps), np.int32)
+    rc = lib().cogv_resample_coeffs(n_in, n_out, xmin.ctypes.data, count.ctypes.data, k.ctypes.data, max_taps)
+    return (rc, xmin, count, k) if rc == OK else (rc, None, None, None)

@@ -91,12 +91,12 @@ def get_dataset_by_type(dataset_type, path, args, tokenizer=None, **kwargs):
     raise NotImplementedError(f"{dataset_type}: the LMDB-backed datasets need the lmdb module (not in this image)")
 
 
-def write_compact_binary(path, text_ids, codes, append=False):
+def write_compact_binary(path, text_ids, codes, append=False, code_len=1024):
     """Write rows in the CompactBinaryDataset layout: text_ids = sequence of id lists (<= 64 ids each, padded with -1),
-    codes [n, 1024] image codes."""
+    codes [n, 1024] image codes (code_len: another row width, for the super-resolution rows of preprocess.py)."""
     codes = np.asarray(codes)
-    assert codes.ndim == 2 and codes.shape[1] == 1024 and len(text_ids) == codes.shape[0]
-    rows = np.full((codes.shape[0], 64 + 1024), -1, dtype=np.int32)
+    assert codes.ndim == 2 and codes.shape[1] == code_len and len(text_ids) == codes.shape[0]
+    rows = np.full((codes.shape[0], 64 + code_len), -1, dtype=np.int32)
     for i, t in enumerate(text_ids):
         t = np.asarray(t, dtype=np.int32)[:64]
         rows[i, :len(t)] = t

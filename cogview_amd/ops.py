@@ -1277,3 +1277,142 @@ def _counter(dev):
     if key not in _COUNTERS:
         _COUNTERS[key] = torch.zeros(1, dtype=torch.int32, device=dev)
     return _COUNTERS[key]
+
+
+# ------------------------------------------------------------------------------------------ tokenizer ingest
+_PREP_TABLES = {}     # (n_in, n_out, S) -> int32 block xmin[S], count[S], k[taps][S] of the crop's outputs of one axis
+_PREP_LUT = {}
+
+
+def _prep_table(n_in, n_out, first, S, taps):
+    """The device layout of one axis' coefficient table (cogv_image_prep_u8), cut to the S outputs from `first` on; the
+    tables come from cogv_resample_coeffs and are cached per (n_in, n_out): a data set has few distinct sizes."""
+    import numpy as np
+    key = (n_in, n_out, S)
+    blk = _PREP_TABLES.get(key)
+    if blk is None:
+        rc, xmin, count, k = L.resample_coeffs(n_in, n_out, taps)
+        L.check(rc, "cogv_resample_coeffs")
+        blk = np.concatenate((xmin[first:first + S], count[first:first + S], k[first:first + S].T.reshape(-1))).astype(np.int32)
+        if len(_PREP_TABLES) >= 4096:
+            _PREP_TABLES.clear()
+        _PREP_TABLES[key] = blk
+    return blk
+
+
+def image_prep_lut(mean, std, device=None):
+    """[3, 256] fp32: what ToTensor and Normalize(mean, std) make of each byte value, computed by torch in fp32 with their
+    own operations ((u / 255) - mean) / std, so that indexing it equals running them."""
+    key = (tuple(float(m) for m in mean), tuple(float(v) for v in std), str(device))
+    lut = _PREP_LUT.get(key)
+    if lut is None:
+        u = torch.arange(256, dtype=torch.float32).div(255)
+        m, sd = torch.tensor(key[0], dtype=torch.float32), torch.tensor(key[1], dtype=torch.float32)
+        lut = u.unsqueeze(0).sub(m.unsqueeze(1)).div(sd.unsqueeze(1)).contiguous()
+        if device is not None:
+            lut = lut.to(device)
+        _PREP_LUT[key] = lut
+    return lut
+
+
+def image_prep_pack(images, size):
+    """The host half of image_prep: (table [B, 8] int32, coeffs int32, byte offsets, total image bytes) for a list of uint8
+    HWC images -- the per-image records and the coefficient tables cogv_image_prep_u8 reads.  Needs no device; an image
+    the kernel does not take raises here with cogv_image_prep_plan's code."""
+    import numpy as np
+    S = int(size)
+    table = np.zeros((len(images), 8), dtype=np.uint32)
+    blocks, at, n_ints, off = [], {}, 0, 0
+    for i, im in enumerate(images):
+        if im.dim() != 3 or im.shape[2] != 3 or im.dtype != torch.uint8:
+            raise ValueError(f"image {i}: want a uint8 tensor [H, W, 3], got {tuple(im.shape)} {im.dtype}")
+        H, W = int(im.shape[0]), int(im.shape[1])
+        rc, plan = L.image_prep_plan(H, W, S)
+        L.check(rc, f"cogv_image_prep_plan({H}, {W}, {S})")
+        tabs = []
+        for n_in, n_out, first, taps in ((W, plan["nw"], plan["left"], plan["taps_h"]), (H, plan["nh"], plan["top"], plan["taps_v"])):
+            key = (n_in, n_out)
+            if key not in at:
+                blk = _prep_table(n_in, n_out, first, S, taps)
+                at[key] = n_ints
+                blocks.append(blk)
+                n_ints += blk.size
+            tabs.append(at[key])
+        table[i] = (off & 0xffffffff, off >> 32, H, W, tabs[0], tabs[1], plan["taps_h"], plan["taps_v"])
+        off += H * W * 3
+    coeffs = np.concatenate(blocks) if blocks else np.zeros(0, np.int32)
+    return table.view(np.int32), coeffs, off
+
+
+def image_prep(images, size, mean, std, out=None, device=None):
+    """transforms.Resize(size) + CenterCrop(size) + ToTensor() + Normalize(mean, std) of a list of uint8 HWC RGB images of
+    any sizes (CPU or device tensors) -> [B, size, size, 4] fp32 NHWC with channel 3 zero, the encoder's input
+    (data_utils/vqvae_tokenizer.py:72-82).  Host images travel in one host-to-device copy together with their table; one
+    launch does the rest.  out: optional destination; device: where host images go (default: the current device)."""
+    import numpy as np
+    S, B = int(size), len(images)
+    if B == 0:
+        raise ValueError("image_prep: no images")
+    on_dev = [im.device for im in images if im.is_cuda]
+    dev = on_dev[0] if on_dev else torch.device(device if device is not None else "cuda")
+    if dev.type != "cuda":
+        raise L.CogviewHipError("cogview_amd ops run only on an MI355X (HIP) device: there is no CPU fallback")
+    table, coeffs, nbytes = image_prep_pack(images, S)
+    head = (table.nbytes + coeffs.nbytes + 15) // 16 * 16
+    body = (nbytes + 15) // 16 * 16
+    buf = np.zeros(head + (0 if on_dev else body), dtype=np.uint8)
+    buf[:table.nbytes] = table.reshape(-1).view(np.uint8)
+    buf[table.nbytes:table.nbytes + coeffs.nbytes] = coeffs.view(np.uint8)
+    if on_dev:
+        pad = torch.zeros(body - nbytes, dtype=torch.uint8, device=dev)
+        pack = torch.cat([im.to(dev).contiguous().view(-1) for im in images] + [pad])
+        dbuf = torch.from_numpy(buf).to(dev)
+    else:
+        at = head
+        for im in images:
+            flat = im.contiguous().view(-1).numpy()
+            buf[at:at + flat.size] = flat
+            at += flat.size
+        dbuf = torch.from_numpy(buf).to(dev)
+        pack = dbuf[head:]
+    lut = image_prep_lut(mean, std, dev)
+    if out is None:
+        out = torch.empty((B, S, S, 4), dtype=torch.float32, device=dev)
+    elif out.shape != (B, S, S, 4) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dbuf.device:
+        raise ValueError(f"out: want a contiguous fp32 tensor [{B}, {S}, {S}, 4] on {dbuf.device}")
+    rc = L.lib().cogv_image_prep_u8(_p(pack), body, C.c_void_p(dbuf.data_ptr()), C.c_void_p(table.ctypes.data),
+                                    C.c_void_p(dbuf.data_ptr() + table.nbytes), coeffs.size, B, S, _p(lut), _p(out), _stream())
+    L.check(rc, "cogv_image_prep_u8")
+    return out
+
+
+def nchw3_to_nhwc4(x):
+    """[b, 3, h, w] -> [b, h, w, 4] fp32, channel 3 zero: the layout the encoder's first convolution reads."""
+    _need_gpu(x)
+    x = x.contiguous().float()
+    b, c, h, w = x.shape
+    assert c == 3, "expects RGB input"
+    x4 = torch.empty((b, h, w, 4), dtype=torch.float32, device=x.device)
+    L.check(L.lib().cogv_nchw3_to_nhwc4_f32(_p(x), _p(x4), b, h, w, _stream()), "cogv_nchw3_to_nhwc4_f32")
+    return x4
+
+
+def sr_patches(x4, positions):
+    """The device half of make_super_resolution_batch (preprocess/pretokenized_data.py:100-124) on x4 [b, S, S, 4] fp32:
+    (patches [b * k, S/2, S/2, 4], image-major, patch i * k + j = image i at crop positions[j] in 0..8 of the 3 x 3 grid
+    with step S/4; overview [b, S/2, S/2, 4] = F.interpolate(size=(S/2, S/2), mode='bilinear')).  positions: a list or an
+    int tensor on either side, shared by all images."""
+    _need_gpu(x4)
+    if x4.dim() != 4 or x4.shape[3] != 4 or x4.shape[1] != x4.shape[2] or x4.dtype != torch.float32:
+        raise ValueError(f"x4: want an fp32 tensor [b, S, S, 4], got {tuple(x4.shape)} {x4.dtype}")
+    pos = [int(v) for v in (positions.reshape(-1).tolist() if isinstance(positions, torch.Tensor) else positions)]
+    if not pos or any(v < 0 or v > 8 for v in pos):
+        raise ValueError(f"positions: want one or more of 0..8, got {pos}")
+    x4 = x4.contiguous()
+    b, S, k = x4.shape[0], x4.shape[1], len(pos)
+    pos_t = torch.tensor(pos, dtype=torch.int32, device=x4.device)
+    patches = torch.empty((b * k, S // 2, S // 2, 4), dtype=torch.float32, device=x4.device)
+    overview = torch.empty((b, S // 2, S // 2, 4), dtype=torch.float32, device=x4.device)
+    L.check(L.lib().cogv_sr_patches_nhwc4_f32(_p(x4), _p(pos_t), _p(patches), _p(overview), b, S, k, _stream()),
+            "cogv_sr_patches_nhwc4_f32")
+    return patches, overview

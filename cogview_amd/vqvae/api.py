@@ -1,4 +1,5 @@
-"""Production tokenizer API (vqvae/api.py:12-44): new_model / img2code / code2img."""
+"""Production tokenizer API (vqvae/api.py:12-44): new_model / img2code / code2img, and the ingest of raw images
+(data_utils/vqvae_tokenizer.py:72-82) in front of it: read_images / img2code_raw."""
 import math
 
 import torch
@@ -19,6 +20,23 @@ def img2code(model, img):
     with torch.no_grad():
         ids = model.encode_ids(img)
     return ids.view(img.shape[0], -1)
+
+
+def read_images(images, img_size=256, device=None):
+    """read_img (data_utils/vqvae_tokenizer.py:72-82) for a list of decoded uint8 HWC RGB images of any sizes: Resize,
+    CenterCrop, ToTensor and Normalize in one launch -> [b, img_size, img_size, 4] fp32 NHWC, channel 3 zero."""
+    from .. import ops
+    images = [torch.as_tensor(im) for im in images]
+    return ops.image_prep(images, img_size, _MEAN, _STD, device=device)
+
+
+def img2code_raw(model, images, img_size=256):
+    """raw uint8 HWC images -> LongTensor [b, (img_size/8)**2]: read_images, then the encoder on its NHWC4 output."""
+    dev = next(model.parameters()).device
+    with torch.no_grad():
+        x4 = read_images(images, img_size, device=dev)
+        ids = model.encode_ids_nhwc4(x4)
+    return ids.view(x4.shape[0], -1)
 
 
 def code2img(model, code):

@@ -281,11 +281,13 @@ class Encoder(_ConvStack):
 
     def forward(self, input):
         """NCHW image -> [b, h/8, w/8, embed_dim] (the reference returns the NHWC permutation too, :164)."""
-        x = input.contiguous().float()
-        b, c, h, w = x.shape
-        assert c == 3, "encoder expects RGB input"
-        x4 = torch.empty((b, h, w, 4), dtype=torch.float32, device=x.device)
-        L.check(L.lib().cogv_nchw3_to_nhwc4_f32(_p(x), _p(x4), b, h, w, _stream()), "cogv_nchw3_to_nhwc4_f32")
+        return self.forward_nhwc4(ops.nchw3_to_nhwc4(input))
+
+    def forward_nhwc4(self, x4):
+        """[b, h, w, 4] fp32 image, channel 3 zero (what the layout launch of forward or ops.image_prep writes) ->
+        [b, h/8, w/8, embed_dim]."""
+        assert x4.dim() == 4 and x4.shape[3] == 4 and x4.dtype == torch.float32, "encoder expects NHWC4 fp32 input"
+        x4 = x4.contiguous()
         if not self._fast:
             y = run_block_list(self.blocks, x4, self._generic_cache)
             return y[..., :self.embed_dim].contiguous() if y.shape[-1] != self.embed_dim else y
@@ -371,6 +373,10 @@ class VQVAE(nn.Module):
     def encode_ids(self, input):
         """ids only: skips the embedding lookup / diff that img2code discards."""
         return self.quantize_t.nearest_code(self.enc_b(input))
+
+    def encode_ids_nhwc4(self, x4):
+        """encode_ids of an image that is NHWC4 already (ops.image_prep): no layout launch."""
+        return self.quantize_t.nearest_code(self.enc_b.forward_nhwc4(x4))
 
     def decode(self, code):
         return self.dec(code)

@@ -608,6 +608,44 @@ int cogv_embed_code_f32(const int64_t* ids, const float* embed_t, float* out, in
 int cogv_conv1x1_to_rgb_f32(const float* in, const float* w, const float* bias, float* out, int B, int H, int W,
                             int Cin, const float* scale3_host, const float* shift3_host, void* stream);
 
+/* ------------------------------------------------------------------ tokenizer ingest: raw uint8 images -> encoder input
+ * replaces transforms.Resize(S) / CenterCrop(S) / ToTensor() / Normalize(mean, std) on PIL images at
+ * data_utils/vqvae_tokenizer.py:72-82 (read_img) and preprocess_entry.py:87-106, and the layout launch
+ * cogv_nchw3_to_nhwc4_f32 behind them.  The uint8 stage is Pillow's Image.resize(BILINEAR) followed by the crop, bit for
+ * bit: per axis in -> out, scale = in / out, support = max(scale, 1); output xx reads the source pixels
+ * [xmin, xmin + count) = [max(int(c - support + .5), 0), min(int(c + support + .5), in)) around c = (xx + .5) * scale with the
+ * triangle weights, normalised by their left-to-right sum, as integers k = (int)(w * 2^22 + .5); a pixel is
+ * clip8((2^21 + sum p * k) >> 22); the horizontal pass is rounded to uint8 before the vertical pass; an axis that keeps its
+ * size is copied.  Resized size: short side S, long side int(S * long / short); crop offsets round((n - S) / 2), half to even.
+ *
+ * cogv_resample_coeffs: HOST ONLY (all pointers are host memory, no device is touched): the tables of one axis,
+ *   xmin[out], count[out], k[out][max_taps] (zero beyond count).  3 when some output needs more than max_taps pixels. */
+int cogv_resample_coeffs(int in, int out, int* xmin, int* count, int* k, int max_taps);
+/* HOST ONLY: what cogv_image_prep_u8 does with one H x W image at size S, and whether it takes it:
+ *   plan = {resized H, resized W, crop top, crop left, taps horizontal, taps vertical (largest count of the axis),
+ *           output rows per workgroup, output columns per workgroup, LDS rows of the horizontal pass, LDS bytes}.
+ *   1: S <= 0, S % 8 != 0 or an empty image; 3: an axis needs more than 65 taps (count <= 2 * scale + 1, so no scale up to 32
+ *   does) or a side beyond 2^24. */
+#define COGV_IMAGE_PREP_PLAN_INTS 10
+int cogv_image_prep_plan(int H, int W, int S, int* plan);
+/* out [B][S][S][4] fp32 (channel 3 zero) = lut[c][resize + crop of image b][c].  One launch for images of different sizes:
+ *   pack        the images' bytes, each HWC, 3 channels, contiguous, at any byte offset; 16-byte aligned, pack_bytes % 4 == 0
+ *   table       [B][8] int32: {offset low, offset high, H, W, htab, vtab, taps horizontal, taps vertical}; table_host is the
+ *               same table in HOST memory (the arguments are checked on it before anything is launched)
+ *   coeffs      int32 tables; htab / vtab index the image's column / row table: xmin[S], count[S], k[taps][S] of the S outputs
+ *               inside the crop (rows of cogv_resample_coeffs from the crop offset on, k transposed)
+ *   lut         [3][256] fp32: ((u / 255) - mean[c]) / std[c], computed by the caller in fp32 (ToTensor, Normalize)
+ * B <= 65535.  Returns as cogv_image_prep_plan for the first image it refuses, 1 for a table entry outside pack / coeffs. */
+int cogv_image_prep_u8(const uint8_t* pack, size_t pack_bytes, const int* table, const int* table_host, const int* coeffs,
+                       size_t coeffs_ints, int B, int S, const float* lut, float* out, void* stream);
+/* the device half of make_super_resolution_batch (preprocess/pretokenized_data.py:100-124) on x [b][S][S][4], S % 16 == 0:
+ *   patches [b * k][S/2][S/2][4], image-major: patch i * k + j = image i at rows ph[p] .. + S/2, columns pw[p] .. + S/2,
+ *           p = positions[j] in 0..8 (device int32 [k]), pw = {0, S/4, S/2} x 3, ph = {0,0,0, S/4,S/4,S/4, S/2,S/2,S/2};
+ *   overview [b][S/2][S/2][4] = F.interpolate(x, size=(S/2, S/2), mode='bilinear'): every weight is 0.5 at this factor,
+ *           computed as 0.5 * (0.5 a + 0.5 b) + 0.5 * (0.5 c + 0.5 d), horizontal pairs first. */
+int cogv_sr_patches_nhwc4_f32(const float* x, const int* positions, float* patches, float* overview, int b, int S, int k,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif
