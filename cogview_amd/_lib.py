@@ -242,6 +242,9 @@ SIGNATURES = {
     "cogv_image_prep_plan": (_i, [_i, _i, _i, C.POINTER(C.c_int)]),
     "cogv_image_prep_u8": (_i, [_vp, _sz, _vp, _vp, _vp, _sz, _i, _i, _vp, _vp, _vp]),
     "cogv_sr_patches_nhwc4_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "cogv_image_grid_plan": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int64)]),
+    "cogv_image_range_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "cogv_image_grid_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, C.c_double, _i, _vp, C.c_double, C.c_double, _vp, _sz, _vp]),
 }
 
 _lib = None
@@ -342,3 +345,18 @@ def resample_coeffs(n_in, n_out, max_taps=IMAGE_PREP_MAX_TAPS):
     k = np.zeros((n_out, max_taps), np.int32)
     rc = lib().cogv_resample_coeffs(n_in, n_out, xmin.ctypes.data, count.ctypes.data, k.ctypes.data, max_taps)
     return (rc, xmin, count, k) if rc == OK else (rc, None, None, None)
+
+
+IMAGE_GRID_PLAN_INTS = 6
+IMAGE_GRID_PLAN_FIELDS = ("xmaps", "ymaps", "grid_h", "grid_w", "out_bytes", "range_bytes")
+GRID_NORM_NONE, GRID_NORM_FIXED, GRID_NORM_RANGE, GRID_NORM_RANGE_EACH = 0, 1, 2, 3
+
+
+def image_grid_plan(B, H, W, nrow=8, padding=2, scale_each=False, table=None):
+    """cogv_image_grid_plan: (error code, dict of IMAGE_GRID_PLAN_FIELDS; empty where the call is refused) of the grid
+    cogv_image_grid_u8 writes for B images of H x W.  table: the int32 [K, 8] source table as a numpy array, checked as the
+    launches check it (None: geometry only).  Host only."""
+    out = (C.c_int64 * IMAGE_GRID_PLAN_INTS)(*([-1] * IMAGE_GRID_PLAN_INTS))
+    K = 0 if table is None else int(table.shape[0])
+    rc = lib().cogv_image_grid_plan(None if table is None else table.ctypes.data, K, B, H, W, nrow, padding, int(bool(scale_each)), out)
+    return rc, dict(zip(IMAGE_GRID_PLAN_FIELDS, out)) if rc == OK else {}

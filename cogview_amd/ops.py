@@ -1416,3 +1416,86 @@ def sr_patches(x4, positions):
     L.check(L.lib().cogv_sr_patches_nhwc4_f32(_p(x4), _p(pos_t), _p(patches), _p(overview), b, S, k, _stream()),
             "cogv_sr_patches_nhwc4_f32")
     return patches, overview
+
+
+# ------------------------------------------------------------------------------------------ image egress
+_GRID_TABLES = {}     # (device, table bytes) -> the source table on the device; the key IS the content
+_GRID_TABLES_CAPTURED = {}     # the tables among them that a stream capture has recorded
+
+
+def image_grid_sources(images, size=None):
+    """The host half of image_grid: (sources, table [K, 8] int32, B, H, W) for a tensor [B, 3, h, w] / [3, h, w] or a list
+    of such tensors of different sizes.  size=(H, W): the size every image is replicated to by an integer factor (default:
+    the largest source).  The table holds the sources' device pointers, so the returned sources must outlive its use."""
+    import numpy as np
+    srcs = [images] if isinstance(images, torch.Tensor) else list(images)
+    if not srcs:
+        raise ValueError("image_grid: no images")
+    _need_gpu(*srcs)
+    srcs = [s.unsqueeze(0) if s.dim() == 3 else s for s in srcs]
+    for s in srcs:
+        if s.dim() != 4 or s.shape[1] != 3 or s.dtype != torch.float32:
+            raise ValueError(f"image_grid: want fp32 tensors [B, 3, H, W] or [3, H, W], got {tuple(s.shape)} {s.dtype}")
+    srcs = [s.contiguous() for s in srcs if s.shape[0] > 0]
+    if not srcs:
+        raise ValueError("image_grid: no images")
+    if size is None:
+        H, W = max(int(s.shape[2]) for s in srcs), max(int(s.shape[3]) for s in srcs)
+    else:
+        H, W = int(size[0]), int(size[1])
+    table = np.zeros((len(srcs), 8), dtype=np.uint32)
+    first = 0
+    for k, s in enumerate(srcs):
+        n, h, w = int(s.shape[0]), int(s.shape[2]), int(s.shape[3])
+        ptr = s.data_ptr()
+        table[k] = (ptr & 0xffffffff, ptr >> 32, n, h, w, H // h if h <= H else 0, first, 0)
+        first += n
+    return srcs, table.view(np.int32), first, H, W
+
+
+def image_grid(images, nrow=8, padding=2, normalize=False, value_range=None, scale_each=False, pad_value=0.0, size=None,
+               out=None):
+    """torchvision.utils.make_grid followed by save_image's conversion (mul(255).add_(0.5).clamp_(0, 255).permute(1, 2, 0)
+    .to(uint8)) on the device, byte for byte as torch computes them on CPU tensors (generate_samples.py:175-199, :236-244,
+    preprocess/utils.py:25-31) -> uint8 [GH, GW, 3].  images: a CUDA fp32 tensor [B, 3, H, W] or [3, H, W], or a list of such
+    tensors of different sizes; size=(H, W) (default: the largest) is what each is brought to by nearest replication with an
+    integer factor 1, 2, 4 or 8 (F.interpolate(size=...) at these factors).  Nothing is read back: with normalize and no
+    value_range the extremes stay in device memory between the two launches.  out: optional uint8 destination of exactly
+    GH * GW * 3 elements, 16-byte aligned."""
+    srcs, table, B, H, W = image_grid_sources(images, size)
+    dev = srcs[0].device
+    nrow, padding = int(nrow), int(padding)
+    if value_range is not None and not isinstance(value_range, tuple):
+        raise TypeError("value_range has to be a tuple (min, max) if specified. min and max are numbers")
+    each = bool(normalize and scale_each and value_range is None)
+    rc, plan = L.image_grid_plan(B, H, W, nrow, padding, each, table)
+    L.check(rc, f"cogv_image_grid_plan({B}, {H}, {W}, nrow={nrow}, padding={padding})")
+    key = (dev.index if dev.index is not None else torch.cuda.current_device(), table.tobytes())
+    dtab = _GRID_TABLES_CAPTURED.get(key, _GRID_TABLES.get(key))
+    if dtab is None:
+        if len(_GRID_TABLES) >= 256:
+            _GRID_TABLES.clear()
+        dtab = _GRID_TABLES[key] = torch.from_numpy(table.copy()).to(dev)
+    if torch.cuda.is_current_stream_capturing():
+        _GRID_TABLES_CAPTURED[key] = dtab      # a captured graph reads this table at every replay: never dropped
+    K, src_bytes = table.shape[0], 4 * sum(s.numel() for s in srcs)
+    shape = (plan["grid_h"], plan["grid_w"], 3)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=dev)
+    elif out.numel() != plan["out_bytes"] or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"out: want a contiguous uint8 tensor of {list(shape)} on {dev}")
+    mode, rng, low, high = L.GRID_NORM_NONE, None, 0.0, 0.0
+    if normalize and value_range is not None:
+        mode, low, high = L.GRID_NORM_FIXED, float(value_range[0]), float(value_range[1])
+    elif normalize:
+        mode = L.GRID_NORM_RANGE_EACH if each else L.GRID_NORM_RANGE
+        rng = torch.empty(plan["range_bytes"] // 4, dtype=torch.int32, device=dev)
+        with timed_launch("image_range", 0.0, src_bytes, lambda: f"{B}x3x{H}x{W}" + (" per image" if each else "")):
+            rc = L.lib().cogv_image_range_f32(_p(dtab), C.c_void_p(table.ctypes.data), K, B, H, W, int(each), _p(rng),
+                                              plan["range_bytes"], _stream())
+        L.check(rc, "cogv_image_range_f32")
+    with timed_launch("image_grid", 0.0, src_bytes + plan["out_bytes"], lambda: f"{B}x3x{H}x{W} -> {shape[0]}x{shape[1]}x3"):
+        rc = L.lib().cogv_image_grid_u8(_p(dtab), C.c_void_p(table.ctypes.data), K, B, H, W, nrow, padding, float(pad_value), mode,
+                                        _p(rng), low, high, _p(out), plan["out_bytes"], _stream())
+    L.check(rc, "cogv_image_grid_u8")
+    return out.view(shape)

@@ -1,5 +1,6 @@
 """Production tokenizer API (vqvae/api.py:12-44): new_model / img2code / code2img, and the ingest of raw images
-(data_utils/vqvae_tokenizer.py:72-82) in front of it: read_images / img2code_raw."""
+(data_utils/vqvae_tokenizer.py:72-82) in front of it: read_images / img2code_raw; behind it the image grid bytes of
+torchvision.utils.save_image (generate_samples.py:175-199, :236-244): code2img_u8 / save_image."""
 import math
 
 import torch
@@ -48,3 +49,22 @@ def code2img(model, code):
         code = code.view(code.shape[0], s, s)
     with torch.no_grad():
         return model.decode_code(code, scale=_STD, shift=_MEAN)
+
+
+def code2img_u8(model, code, **grid_kwargs):
+    """code2img, then ops.image_grid on its output: codes -> the uint8 [GH, GW, 3] image grid torchvision.utils.save_image
+    would write (generate_samples.py:175-199, :236-244), on the device.  code: as for code2img, or a list of code maps of
+    different sizes (32 x 32 and 64 x 64: the smaller images are replicated to the larger, as F.interpolate does there);
+    grid_kwargs: nrow, padding, normalize, value_range, scale_each, pad_value, size, out."""
+    from .. import ops
+    codes = code if isinstance(code, (list, tuple)) else [code]
+    return ops.image_grid([code2img(model, c) for c in codes], **grid_kwargs)
+
+
+def save_image(tensor, fp, format=None, **grid_kwargs):
+    """torchvision.utils.save_image for CUDA fp32 images [B, 3, H, W] (or a list, as ops.image_grid takes it): the grid and
+    the bytes are made on the device, one device-to-host copy of 3 bytes per pixel, then Pillow writes the file."""
+    from PIL import Image
+    from .. import ops
+    grid = ops.image_grid(tensor, **grid_kwargs)
+    Image.fromarray(grid.cpu().numpy()).save(fp, format=format)

@@ -646,6 +646,48 @@ int cogv_image_prep_u8(const uint8_t* pack, size_t pack_bytes, const int* table,
 int cogv_sr_patches_nhwc4_f32(const float* x, const int* positions, float* patches, float* overview, int b, int S, int k,
                               void* stream);
 
+/* ------------------------------------------------------------------ image egress: decoded fp32 images -> uint8 image grid
+ * replaces F.interpolate + torchvision.utils.save_image(..., normalize=True) at generate_samples.py:175-199
+ * (generate_images_once) and :236-244 (super_resolution), and save_image(..., normalize=False, nrow=len(imgs)) at
+ * preprocess/utils.py:25-31: make_grid, then save_image's mul(255).add_(0.5).clamp_(0, 255).permute(1, 2, 0).to(uint8),
+ * byte for byte as torch computes them on CPU tensors.
+ *   images   B images of 3 x H x W in K source batches: contiguous fp32 NCHW [n][3][h][w] with an integer factor f in
+ *            {1, 2, 4, 8}, h * f == H, w * f == W; image pixel (i, j) reads source pixel (i / f, j / f) -- F.interpolate's
+ *            default nearest mode at these factors.
+ *   table    [K][8] int32: {pointer low, pointer high, n, h, w, f, first image (the n of the batches in front), 0}, sum n == B,
+ *            every pointer 16-byte aligned; table_host is the same table in HOST memory (the arguments are checked on it
+ *            before anything is launched).
+ *   grid     B == 1: the image itself, [H][W][3].  Otherwise xmaps = min(nrow, B), ymaps = ceil(B / xmaps), the grid is
+ *            [(H + padding) * ymaps + padding][(W + padding) * xmaps + padding][3], image k has its top-left at row
+ *            (k / xmaps) * (H + padding) + padding, column (k % xmaps) * (W + padding) + padding; everything else is padding.
+ *   bytes    t = y * 255 (rounded), t + 0.5 (rounded; never one fused multiply-add), clamped to [0, 255], truncated; the
+ *            padding byte is the same of pad_value.  y = x, or with a normalisation
+ *            y = (min(max(x, low), high) - low) / d, d = (float)max((double)high - (double)low, 1e-5), a true fp32 division.
+ * Returns 1: B == 0 or B > 65535, nrow <= 0, padding < 0, a null or misaligned pointer, a table whose n do not add up to B,
+ *   high < low, an out or range smaller than the plan's; 3: another factor, h * f != H, w * f != W, H, W or padding beyond
+ *   32768, a grid side beyond 2^28.
+ *
+ * cogv_image_grid_plan: HOST ONLY.  plan = {xmaps, ymaps, grid H, grid W, out bytes, range workspace bytes}; table_host may be
+ *   NULL (geometry only), otherwise the sources are checked as the launches check them. */
+#define COGV_IMAGE_GRID_PLAN_INTS 6
+int cogv_image_grid_plan(const int* table_host, int K, int B, int H, int W, int nrow, int padding, int scale_each, int64_t* plan);
+/* range (device, the plan's range workspace bytes, 4-byte aligned): one slot for all images, or one per image with
+ * scale_each; a slot is two uint32 {~key(minimum), key(maximum)}, key(v) = bits(v) ^ (v < 0 ? 0xffffffff : 0x80000000), which
+ * orders as the floats do, so that integer atomics give the exact extremes in any order.  Zeroes the slots (a memset node
+ * under capture), then one launch; nothing is read back. */
+int cogv_image_range_f32(const int* table, const int* table_host, int K, int B, int H, int W, int scale_each, void* range,
+                         size_t range_bytes, void* stream);
+/* out (device, 16-byte aligned, at least the plan's out bytes): every byte of the grid written exactly once by one launch.
+ * norm: NONE; FIXED: low, high as given (value_range; d from the doubles, the clamp and the subtraction on their fp32
+ * roundings, as torch reads Python scalars); RANGE / RANGE_EACH: slot 0 / slot k of cogv_image_range_f32's range. */
+#define COGV_GRID_NORM_NONE 0
+#define COGV_GRID_NORM_FIXED 1
+#define COGV_GRID_NORM_RANGE 2
+#define COGV_GRID_NORM_RANGE_EACH 3
+int cogv_image_grid_u8(const int* table, const int* table_host, int K, int B, int H, int W, int nrow, int padding,
+                       double pad_value, int norm, const void* range, double low, double high, uint8_t* out, size_t out_bytes,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif
