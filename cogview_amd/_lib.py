@@ -138,6 +138,15 @@ class ConvDesc(C.Structure):
     ]
 
 
+class ConvWgradDesc(C.Structure):
+    _fields_ = [
+        ("kind", C.c_int), ("B", C.c_int), ("IH", C.c_int), ("IW", C.c_int), ("Cin", C.c_int), ("Cout", C.c_int),
+        ("splits", C.c_int),
+        ("x", C.c_void_p), ("dy", C.c_void_p), ("dw", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+    ]
+
+
 class SampleDesc(C.Structure):
     _fields_ = [
         ("dtype", C.c_int), ("rows", C.c_int), ("vocab", C.c_int), ("row_stride", C.c_int64),
@@ -238,6 +247,15 @@ SIGNATURES = {
     "cogv_sample_logits": (_i, [C.POINTER(SampleDesc), _vp]),
     "cogv_score_targets": (_i, [C.POINTER(ScoreDesc), _vp]),
     "cogv_conv1x1_to_rgb_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), _vp]),
+    "cogv_conv_wgrad_plan": (_i, [C.POINTER(ConvWgradDesc), C.POINTER(C.c_int)]),
+    "cogv_conv_wgrad_workspace_bytes": (_sz, [C.POINTER(ConvWgradDesc)]),
+    "cogv_conv_wgrad_nhwc_f32": (_i, [C.POINTER(ConvWgradDesc), _vp]),
+    "cogv_relu_bias_bwd_workspace_bytes": (_sz, [_i64, _i]),
+    "cogv_relu_bias_bwd_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _i64, _i, _vp]),
+    "cogv_vq_code_stats_workspace_bytes": (_sz, [_i, _i, _i]),
+    "cogv_vq_code_stats_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
+    "cogv_vq_ema_update_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _i, _i, _vp]),
+    "cogv_vq_ste_bwd_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "cogv_resample_coeffs": (_i, [_i, _i, _vp, _vp, _vp, _i]),
     "cogv_image_prep_plan": (_i, [_i, _i, _i, C.POINTER(C.c_int)]),
     "cogv_image_prep_u8": (_i, [_vp, _sz, _vp, _vp, _vp, _sz, _i, _i, _vp, _vp, _vp]),
@@ -320,6 +338,20 @@ def gemm_rows_plan(dtype, M, N, K, desc=None):
     out = (C.c_int * GEMM_ROWS_PLAN_INTS)(*([-1] * GEMM_ROWS_PLAN_INTS))
     rc = lib().cogv_gemm_rows_plan(C.byref(d), out)
     return rc, list(out)
+
+
+CONV_WGRAD_PLAN_INTS = 6
+CONV_WGRAD_PLAN_FIELDS = ("splits", "span", "workgroups", "cout_tiles", "k_tiles", "parities")
+
+
+def conv_wgrad_plan(kind, B, IH, IW, Cin, Cout, splits=0):
+    """cogv_conv_wgrad_plan: (error code, dict of CONV_WGRAD_PLAN_FIELDS; empty where the layer is refused) of what
+    cogv_conv_wgrad_nhwc_f32 launches for that forward layer.  Host only."""
+    d = ConvWgradDesc()
+    d.kind, d.B, d.IH, d.IW, d.Cin, d.Cout, d.splits = kind, B, IH, IW, Cin, Cout, splits
+    out = (C.c_int * CONV_WGRAD_PLAN_INTS)(*([-1] * CONV_WGRAD_PLAN_INTS))
+    rc = lib().cogv_conv_wgrad_plan(C.byref(d), out)
+    return rc, dict(zip(CONV_WGRAD_PLAN_FIELDS, out)) if rc == OK else {}
 
 
 IMAGE_PREP_PLAN_INTS = 10

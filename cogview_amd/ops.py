@@ -1397,6 +1397,100 @@ def nchw3_to_nhwc4(x):
     return x4
 
 
+# ------------------------------------------------------------------------------------------ VQ-VAE tokenizer training
+def conv_wgrad(kind, x, dy, splits=0):
+    """Weight gradient of the convolution layer `kind` (L.CONV_4X4_S2 / CONV_1X1 / CONVT_4X4_S2) with input x
+    [b, ih, iw, cin] and pre-activation output gradient dy [b, oh, ow, cout], both NHWC fp32, in the PACKED layout the
+    forward kernel reads: [cout, taps, cin], or [4, cout, 4, cin] for the transposed convolution
+    (vqvae_zc.unpack_*_weight_grad turn it into the parameter's layout).  splits: pixel-range splits, 0 = the plan's."""
+    _need_gpu(x, dy)
+    assert x.dtype == torch.float32 and dy.dtype == torch.float32 and x.dim() == 4 and dy.dim() == 4
+    x, dy = x.contiguous(), dy.contiguous()
+    b, ih, iw, cin = x.shape
+    cout = dy.shape[3]
+    d = L.ConvWgradDesc()
+    d.kind, d.B, d.IH, d.IW, d.Cin, d.Cout, d.splits = kind, b, ih, iw, cin, cout, int(splits)
+    plan = (C.c_int * L.CONV_WGRAD_PLAN_INTS)()
+    L.check(L.lib().cogv_conv_wgrad_plan(C.byref(d), plan), f"cogv_conv_wgrad_plan(kind {kind}, {b}x{ih}x{iw}x{cin}->{cout})")
+    par, taps = (4, 4) if kind == L.CONVT_4X4_S2 else (1, 16 if kind == L.CONV_4X4_S2 else 1)
+    om = {L.CONV_4X4_S2: (ih // 2, iw // 2), L.CONVT_4X4_S2: (ih * 2, iw * 2)}.get(kind, (ih, iw))
+    assert tuple(dy.shape) == (b, om[0], om[1], cout), "dy does not have the layer's output shape"
+    dw = torch.empty((4, cout, taps, cin) if par == 4 else (cout, taps, cin), dtype=torch.float32, device=x.device)
+    nws = L.lib().cogv_conv_wgrad_workspace_bytes(C.byref(d))
+    ws = workspace("conv_wgrad", nws, x.device) if nws else None
+    d.x, d.dy, d.dw = x.data_ptr(), dy.data_ptr(), dw.data_ptr()
+    d.workspace, d.workspace_bytes = (ws.data_ptr(), ws.numel()) if nws else (None, 0)
+    npix = b * (ih // 2) * (iw // 2) if kind == L.CONV_4X4_S2 else b * ih * iw
+    with timed_launch("conv_wgrad", 2.0 * npix * par * cout * taps * cin, 4.0 * (x.numel() + dy.numel() + dw.numel() * (1 + 2 * (plan[0] > 1) * plan[0])),
+                      f"kind{kind} {b}x{ih}x{iw}x{cin}->{cout} splits {plan[0]}"):
+        L.check(L.lib().cogv_conv_wgrad_nhwc_f32(C.byref(d), _stream()), "cogv_conv_wgrad_nhwc_f32")
+    return dw
+
+
+def relu_bias_bwd(dy, act=None):
+    """(dx, db) of a layer's epilogue: dx = dy * (act > 0) for the saved post-ReLU activation `act` (None: dx is dy), db[c] =
+    the sum of dx over every leading dimension, fp32, fixed order."""
+    _need_gpu(dy, act)
+    assert dy.dtype == torch.float32 and (act is None or (act.dtype == torch.float32 and act.shape == dy.shape))
+    dy = dy.contiguous()
+    act = None if act is None else act.contiguous()
+    c = dy.shape[-1]
+    m = dy.numel() // c
+    dx = None if act is None else torch.empty_like(dy)
+    db = torch.empty(c, dtype=torch.float32, device=dy.device)
+    nws = L.lib().cogv_relu_bias_bwd_workspace_bytes(m, c)
+    ws = workspace("relu_bias_bwd", nws, dy.device)
+    with timed_launch("relu_bias_bwd", 0.0, 4.0 * dy.numel() * (1 + (act is not None) + (dx is not None)), f"{m}x{c}"):
+        L.check(L.lib().cogv_relu_bias_bwd_f32(_p(dy), _p(act), _p(dx), _p(db), _p(ws), ws.numel(), m, c, _stream()),
+                "cogv_relu_bias_bwd_f32")
+    return (dx if act is not None else dy), db
+
+
+def vq_code_stats(ids, x, n_embed):
+    """(count int32 [n_embed], sum fp32 [n_embed, d]) of the pixels x [m, d] under their code ids [m] (int64): how many pixels
+    chose each code and the sum of their vectors, in ascending pixel order (bitwise reproducible)."""
+    _need_gpu(ids, x)
+    assert ids.dtype == torch.int64 and x.dtype == torch.float32 and x.dim() == 2 and ids.numel() == x.shape[0]
+    ids, x = ids.contiguous().view(-1), x.contiguous()
+    m, dim = x.shape
+    count = torch.empty(n_embed, dtype=torch.int32, device=x.device)
+    total = torch.empty((n_embed, dim), dtype=torch.float32, device=x.device)
+    nws = L.lib().cogv_vq_code_stats_workspace_bytes(m, dim, n_embed)
+    ws = workspace("vq_code_stats", nws, x.device)
+    with timed_launch("vq_code_stats", 1.0 * m * dim, 4.0 * (2 * x.numel() + 2 * total.numel()) + 16.0 * m, f"{m}x{dim}x{n_embed}"):
+        L.check(L.lib().cogv_vq_code_stats_f32(_p(ids), _p(x), _p(count), _p(total), _p(ws), ws.numel(), m, dim, n_embed, _stream()),
+                "cogv_vq_code_stats_f32")
+    return count, total
+
+
+def vq_ema_update(count, total, cluster_size, embed_avg, embed, decay, eps):
+    """The EMA codebook update of Quantize.forward_ (vqvae/vqvae_zc.py:74-83) IN PLACE on cluster_size [n_embed], embed_avg and
+    embed [d, n_embed], from vq_code_stats' (count, total).  Writes through the raw pointers: the tensors' version counters do
+    not move (the caller invalidates what it derived from them).  Returns n = cluster_size.sum() as a device scalar."""
+    _need_gpu(count, total, cluster_size, embed_avg, embed)
+    dim, n_embed = embed.shape
+    for t in (cluster_size, embed_avg, embed, total):
+        assert t.dtype == torch.float32 and t.is_contiguous()
+    assert count.dtype == torch.int32 and tuple(total.shape) == (n_embed, dim) and embed_avg.shape == embed.shape
+    n = torch.empty(1, dtype=torch.float32, device=embed.device)
+    with timed_launch("vq_ema_update", 4.0 * embed.numel(), 4.0 * 4 * embed.numel(), f"{dim}x{n_embed}"):
+        L.check(L.lib().cogv_vq_ema_update_f32(_p(count), _p(total), _p(cluster_size), _p(embed_avg), _p(embed), _p(n), float(decay),
+                                               float(eps), dim, n_embed, _stream()), "cogv_vq_ema_update_f32")
+    return n
+
+
+def vq_ste_bwd(g_q, g_diff, x, q):
+    """Gradient of the quantiser's input: g_q + g_diff * 2 (x - q) / numel (straight-through estimator + commitment term,
+    vqvae/vqvae_zc.py:85-86).  g_q / g_diff (a device scalar) may be None."""
+    _need_gpu(x, q, g_q, g_diff)
+    x, q = x.contiguous(), q.contiguous()
+    g_q = None if g_q is None else g_q.contiguous()
+    g_x = torch.empty_like(x)
+    with timed_launch("vq_ste_bwd", 3.0 * x.numel(), 4.0 * 4 * x.numel(), f"{x.numel()}"):
+        L.check(L.lib().cogv_vq_ste_bwd_f32(_p(g_q), _p(g_diff), _p(x), _p(q), _p(g_x), x.numel(), _stream()), "cogv_vq_ste_bwd_f32")
+    return g_x
+
+
 def sr_patches(x4, positions):
     """The device half of make_super_resolution_batch (preprocess/pretokenized_data.py:100-124) on x4 [b, S, S, 4] fp32:
     (patches [b * k, S/2, S/2, 4], image-major, patch i * k + j = image i at crop positions[j] in 0..8 of the 3 x 3 grid

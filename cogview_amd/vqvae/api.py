@@ -51,6 +51,22 @@ def code2img(model, code):
         return model.decode_code(code, scale=_STD, shift=_MEAN)
 
 
+def train_step(model, optimizer, img, latent_loss_weight=0.25):
+    """One training step of the tokenizer (model.train(); the default, non-relaxed path of vqvae/vqvae_zc.py:67-86 and
+    :261-268): forward, loss = mse(dec, img) + latent_loss_weight * diff, backward, optimizer.step() -- any torch.optim
+    optimizer over the fp32 parameters.  The EMA codebook update happens inside the forward, as in the reference.
+    Returns dict(loss, recon_loss, latent_loss) as device scalars (no host read)."""
+    optimizer.zero_grad(set_to_none=True)
+    dec, diff = model(img)
+    recon_loss = torch.nn.functional.mse_loss(dec, img)
+    latent_loss = diff.mean()
+    loss = recon_loss + latent_loss_weight * latent_loss
+    loss.backward()
+    optimizer.step()
+    model.invalidate_caches()
+    return dict(loss=loss.detach(), recon_loss=recon_loss.detach(), latent_loss=latent_loss.detach())
+
+
 def code2img_u8(model, code, **grid_kwargs):
     """code2img, then ops.image_grid on its output: codes -> the uint8 [GH, GW, 3] image grid torchvision.utils.save_image
     would write (generate_samples.py:175-199, :236-244), on the device.  code: as for code2img, or a list of code maps of

@@ -7,8 +7,14 @@ Scope: the frozen tokenizer as CogView uses it (vqvae/api.py: img2code / code2im
 transposed convolutions + 1x1 -- runs the fused fast path (final 1x1 -> RGB in the last transposed convolution's epilogue).
 Every OTHER topology the reference's constructors can build (vqvae/vqvae_zc.py:116-214: stride 6 / 4 / 2, simple or not,
 any number of ResBlocks) runs through a generic interpreter of the same block list on the same kernels (round 4: 3x3
-convolution, input ReLU and residual add in the convolution kernel) -- channel counts a multiple of 8.  Training of the VQ-VAE (EMA codebook update, Gumbel-softmax relaxation) is not
-part of CogView's pipeline (no training script in the reference) and raises.
+convolution, input ReLU and residual add in the convolution kernel) -- channel counts a multiple of 8.
+
+Training (module.train(), vqvae/vqvae_zc.py:67-86): the default, non-relaxed path of every topology made of 4x4 stride-2
+convolutions, 4x4 stride-2 transposed convolutions, 1x1 convolutions and ReLU (new_model() and every n_res_block=0 stride-6
+configuration).  The stacks run layer by layer, each layer a torch.autograd.Function on the kernels of
+cogview_amd/csrc/conv.hip (forward, data gradient) and conv_bwd.hip (weight gradient, ReLU mask + bias gradient, codebook
+statistics, EMA update, straight-through gradient).  What still raises NotImplementedError in training mode: ResBlock
+topologies and 3x3 convolutions (no weight gradient kernel), and continuous_relax=True (the Gumbel-softmax branch) in any mode.
 """
 import ctypes as C
 
@@ -47,7 +53,7 @@ def _conv(kind, x, w, bias, cout, relu, rgb=None, relu_in=False, residual=None, 
         assert residual.shape == (b, oh, ow, cout) and residual.is_contiguous() and rgb is None
         d.residual = residual.data_ptr()
     setattr(d, "in", x.data_ptr())
-    d.w, d.bias = w.data_ptr(), bias.data_ptr()
+    d.w, d.bias = w.data_ptr(), (None if bias is None else bias.data_ptr())      # no bias: the data gradient of a layer
     if rgb is None:
         out = torch.empty((b, oh, ow, cout), dtype=torch.float32, device=x.device)
         d.out = out.data_ptr()
@@ -98,6 +104,49 @@ def pack_convt_weight(w):
     return out.contiguous()
 
 
+def _convt_taps():
+    """(parity, tap, ky, kx) of pack_convt_weight's layout: every (ky, kx) of the 4x4 kernel occurs exactly once."""
+    for py in range(2):
+        for px in range(2):
+            for ty in range(2):
+                for tx in range(2):
+                    yield py * 2 + px, ty * 2 + tx, (2 * ty if py else 1 + 2 * ty), (2 * tx if px else 1 + 2 * tx)
+
+
+def unpack_conv_weight_grad(dwp, shape):
+    """Inverse of pack_conv_weight for a weight gradient: packed [Cout', kh*kw, Cin'] (channels possibly padded) -> the
+    Conv2d parameter's layout `shape` = [Cout, Cin, kh, kw]; the padding is dropped."""
+    co, ci, kh, kw = shape
+    return dwp[:co, :, :ci].reshape(co, kh, kw, ci).permute(0, 3, 1, 2).contiguous()
+
+
+def unpack_convt_weight_grad(dwp, shape):
+    """Inverse of pack_convt_weight for a weight gradient: packed [4, Cout', 4, Cin'] -> the ConvTranspose2d parameter's
+    layout `shape` = [Cin, Cout, 4, 4]; the padding is dropped."""
+    ci, co, kh, kw = shape
+    assert kh == 4 and kw == 4
+    out = torch.empty(tuple(shape), dtype=dwp.dtype, device=dwp.device)
+    for z, t, ky, kx in _convt_taps():
+        out[:, :, ky, kx] = dwp[z, :co, t, :ci].t()
+    return out
+
+
+class _StraightThrough(torch.autograd.Function):
+    """(quantize, diff) of vqvae/vqvae_zc.py:85-86 with their graph: diff = (q - x)^2 .mean(), and the straight-through
+    output, whose VALUE is the lookup q itself (the reference's x + (q - x) is q up to one rounding; returning q keeps the
+    decoder's input bit-identical to the frozen-codebook path).  Backward: one launch, g_q + g_diff * 2 (x - q) / numel."""
+
+    @staticmethod
+    def forward(ctx, x, q):
+        ctx.save_for_backward(x, q)
+        return q.view_as(q), (q - x).pow(2).mean()
+
+    @staticmethod
+    def backward(ctx, g_q, g_diff):
+        x, q = ctx.saved_tensors
+        return ops.vq_ste_bwd(g_q, None if g_diff is None else g_diff.reshape(1).contiguous(), x, q), None
+
+
 class Quantize(nn.Module):
     """Codebook holder (vqvae/vqvae_zc.py:26-96).  `embed` is [dim, n_embed] as in the reference."""
 
@@ -141,12 +190,33 @@ class Quantize(nn.Module):
         return out
 
     def forward_(self, input, continuous_relax=False, temperature=1., hard=False):
-        if continuous_relax or self.training:
-            raise NotImplementedError("only the frozen eval-mode tokenizer path is implemented (argmax + lookup)")
-        ids = self.nearest_code(input.contiguous())
-        quantize = self.embed_code(ids)
-        diff = (quantize - input).pow(2).mean()
+        if continuous_relax:
+            raise NotImplementedError("continuous_relax=True: the Gumbel-softmax branch of Quantize.forward_ (vqvae/vqvae_zc.py:55-65, "
+                                      ":88-92) is not implemented; only argmax + lookup is")
+        x = input.contiguous()
+        ids = self.nearest_code(x.detach())
+        quantize = self.embed_code(ids)                  # from the codebook BEFORE the update, as in the reference
+        if self.training:
+            self.ema_update(x.detach(), ids)
+        if torch.is_grad_enabled() and x.requires_grad:
+            quantize, diff = _StraightThrough.apply(x, quantize)
+        else:
+            diff = (quantize - input).pow(2).mean()
         return quantize, diff, ids
+
+    def invalidate_cache(self):
+        """Forget E^T / |E|^2: they are keyed on embed._version, which a write through the buffer's storage (the EMA kernels,
+        the reference-style embed.data.copy_) does not advance."""
+        self._cache = None
+
+    def ema_update(self, x_nhwc, ids):
+        """The training branch of vqvae/vqvae_zc.py:67-83 on the device: per-code pixel count and vector sum (inverted index,
+        no one-hot product), then cluster_size / embed_avg decay, Laplace smoothing and the new embed, in place."""
+        with torch.no_grad():
+            flat = x_nhwc.reshape(-1, self.dim)
+            count, total = ops.vq_code_stats(ids.reshape(-1), flat, self.n_embed)
+            ops.vq_ema_update(count, total, self.cluster_size, self.embed_avg, self.embed, self.decay, self.eps)
+        self.invalidate_cache()
 
 
 class _ConvStack(nn.Module):
@@ -253,6 +323,103 @@ def run_block_list(blocks, x, cache):
     return x
 
 
+def _dgrad_weight(m, kind, cin_x, cout_p):
+    """(kind, packed weight) of the layer that computes the DATA gradient of convolution module m (forward kind `kind`): it
+    reads the cout_p channels of the output gradient and writes the cin_x channels of the input gradient.
+      Conv2d k4 s2 p1, W [Cout, Cin, 4, 4]          -> transposed convolution whose [in, out, 4, 4] weight is W itself
+      ConvTranspose2d k4 s2 p1, W [Cin, Cout, 4, 4] -> convolution whose [out, in, 4, 4] weight is W itself
+      1x1                                            -> 1x1 with the transposed matrix"""
+    w = m.weight.detach().float()
+    if kind == L.CONV_4X4_S2:
+        k2, wp = L.CONVT_4X4_S2, pack_convt_weight(w)
+    elif kind == L.CONVT_4X4_S2:
+        k2, wp = L.CONV_4X4_S2, pack_conv_weight(w)
+    else:
+        k2, wp = L.CONV_1X1, pack_conv_weight(w if isinstance(m, nn.ConvTranspose2d) else w.permute(1, 0, 2, 3))
+    wp = torch.nn.functional.pad(wp, (0, cout_p - wp.shape[-1], 0, 0, 0, cin_x - wp.shape[-3]))
+    return k2, wp.contiguous()
+
+
+class _ConvLayer(torch.autograd.Function):
+    """One convolution layer (+ the ReLU that follows it) of a training-mode stack.  Saves its input and, with a ReLU, its
+    post-ReLU output; backward launches the ReLU mask + bias gradient, the data gradient (the forward kernel on repacked
+    weights) and the weight gradient -- each only when something needs it."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, m, relu):
+        kind, wp, bp, _ = _pack_generic(m)
+        if x.shape[-1] > wp.shape[-1]:               # the previous layer's zero-padded output channels: zero weights for them
+            wp = torch.nn.functional.pad(wp, (0, x.shape[-1] - wp.shape[-1])).contiguous()
+        y = _conv(kind, x, wp, bp, bp.numel(), relu)
+        ctx.m, ctx.kind, ctx.relu = m, kind, relu
+        ctx.save_for_backward(x, y if relu else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, y = ctx.saved_tensors
+        m, kind = ctx.m, ctx.kind
+        need_x, need_w, need_b = ctx.needs_input_grad[:3]
+        g = g.contiguous()
+        db = None
+        if ctx.relu or need_b:
+            g, db = ops.relu_bias_bwd(g, y if ctx.relu else None)
+        dx = dw = None
+        if need_x:
+            k2, wp = _dgrad_weight(m, kind, x.shape[-1], g.shape[-1])
+            dx = _conv(k2, g, wp, None, x.shape[-1], False)
+        if need_w:
+            dwp = ops.conv_wgrad(kind, x, g)
+            if kind == L.CONVT_4X4_S2:
+                dw = unpack_convt_weight_grad(dwp, m.weight.shape)
+            elif isinstance(m, nn.ConvTranspose2d):       # 1x1 transposed: the parameter is the transposed matrix
+                dw = dwp[:m.out_channels, 0, :m.in_channels].t().reshape(m.weight.shape).contiguous()
+            else:
+                dw = unpack_conv_weight_grad(dwp, m.weight.shape)
+        if need_b:
+            db = db[:m.out_channels].contiguous()
+        return dx, dw, (db if need_b else None), None, None
+
+
+def _training_kind(m):
+    """The kernel kind of a module the training path supports; NotImplementedError naming what is missing otherwise."""
+    if isinstance(m, ResBlock):
+        raise NotImplementedError("training a ResBlock topology is not implemented: the ResBlock backward (3x3 weight gradient, "
+                                  "residual branch) is missing; n_res_block=0 topologies train")
+    if isinstance(m, nn.ConvTranspose2d):
+        if m.kernel_size == (1, 1) or (m.kernel_size == (4, 4) and m.stride == (2, 2) and m.padding == (1, 1)):
+            return
+    elif isinstance(m, nn.Conv2d):
+        ks, st, pd = m.kernel_size, m.stride, m.padding
+        if (ks == (4, 4) and st == (2, 2) and pd == (1, 1)) or (ks == (1, 1) and st == (1, 1) and pd == (0, 0)):
+            return
+        if ks == (3, 3):
+            raise NotImplementedError("training a topology with a 3x3 convolution is not implemented: the 3x3 weight gradient is "
+                                      "missing (stride 6 encoders and their decoders train)")
+    raise NotImplementedError(f"training through {m} is not implemented")
+
+
+def train_block_list(blocks, x):
+    """run_block_list for training mode: the same blocks on the same forward kernels, one _ConvLayer per convolution so that
+    autograd reaches the weights.  Every ReLU of the supported topologies follows a convolution and rides in its epilogue."""
+    mods = list(blocks)
+    for m in mods:
+        if not isinstance(m, nn.ReLU):
+            _training_kind(m)
+    i = 0
+    while i < len(mods):
+        m = mods[i]
+        if isinstance(m, nn.ReLU):
+            raise NotImplementedError("training: a ReLU that does not follow a convolution (ResBlock topologies) is not implemented")
+        fuse = i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
+        cin_p = (m.in_channels + 3) // 4 * 4
+        if x.shape[-1] < cin_p:
+            x = torch.nn.functional.pad(x, (0, cin_p - x.shape[-1]))
+        x = _ConvLayer.apply(x, m.weight, m.bias, m, fuse)
+        i += 2 if fuse else 1
+    return x
+
+
 class Encoder(_ConvStack):
     """vqvae/vqvae_zc.py:116-164.  Production (stride 6, simple, no ResBlocks): conv4x4s2+ReLU, conv4x4s2+ReLU, conv4x4s2, ReLU,
     conv1x1 on the fused fast path; every other topology through run_block_list."""
@@ -288,6 +455,9 @@ class Encoder(_ConvStack):
         [b, h/8, w/8, embed_dim]."""
         assert x4.dim() == 4 and x4.shape[3] == 4 and x4.dtype == torch.float32, "encoder expects NHWC4 fp32 input"
         x4 = x4.contiguous()
+        if self.training:
+            y = train_block_list(self.blocks, x4)
+            return y[..., :self.embed_dim].contiguous() if y.shape[-1] != self.embed_dim else y
         if not self._fast:
             y = run_block_list(self.blocks, x4, self._generic_cache)
             return y[..., :self.embed_dim].contiguous() if y.shape[-1] != self.embed_dim else y
@@ -324,8 +494,9 @@ class Decoder(_ConvStack):
         self._generic_cache = {}
 
     def forward_nhwc(self, q_nhwc, scale=None, shift=None):
-        if not self._fast:
-            y = run_block_list(self.blocks, q_nhwc.contiguous().float(), self._generic_cache)
+        if self.training or not self._fast:
+            run = train_block_list if self.training else (lambda b, x: run_block_list(b, x, self._generic_cache))
+            y = run(self.blocks, q_nhwc.contiguous().float())
             img = y[..., :self.out_channel].permute(0, 3, 1, 2).contiguous()
             if scale is not None:
                 img = img * torch.tensor(scale, device=img.device, dtype=img.dtype).view(1, -1, 1, 1)
@@ -377,6 +548,15 @@ class VQVAE(nn.Module):
     def encode_ids_nhwc4(self, x4):
         """encode_ids of an image that is NHWC4 already (ops.image_prep): no layout launch."""
         return self.quantize_t.nearest_code(self.enc_b.forward_nhwc4(x4))
+
+    def invalidate_caches(self):
+        """Forget every table derived from a parameter or buffer (packed weights, E^T, |E|^2).  They are keyed on the tensors'
+        version counters, which in-place operators advance but writes through `.data` or the storage do not; api.train_step
+        calls this after optimizer.step()."""
+        self.quantize_t.invalidate_cache()
+        for stack in (self.enc_b, self.dec):
+            stack._packed = None
+            stack._generic_cache.clear()
 
     def decode(self, code):
         return self.dec(code)

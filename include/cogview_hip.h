@@ -608,6 +608,58 @@ int cogv_embed_code_f32(const int64_t* ids, const float* embed_t, float* out, in
 int cogv_conv1x1_to_rgb_f32(const float* in, const float* w, const float* bias, float* out, int B, int H, int W,
                             int Cin, const float* scale3_host, const float* shift3_host, void* stream);
 
+/* ------------------------------------------------------------------ VQ-VAE tokenizer training (fp32, exact-fp32 MFMA)
+ * replaces the autograd of the conv stacks of vqvae/vqvae_zc.py:116-214 (F.conv2d / F.conv_transpose2d backward for the weights,
+ * the ReLU and bias backward) and the training branch of Quantize.forward_ :67-86 (EMA codebook, straight-through estimator).
+ * The DATA gradient of a layer is cogv_conv2d_nhwc_f32 with repacked weights (k4 s2 conv <-> k4 s2 transposed conv, 1x1 with
+ * W^T).  No floating-point atomics: every result is bitwise reproducible.
+ *
+ * Weight gradient of the layer a cogv_conv_desc with the same kind / B / IH / IW / Cin / Cout describes (F.conv2d's
+ * grad_weight at :121-129, F.conv_transpose2d's at :172-192):
+ *   dw[z][co][t][ci] = sum over the pixels m of the forward iteration grid of dy[out(m, z)][co] * x[in(m, t, z)][ci],
+ * taps outside the image contributing zero -- in the PACKED layout [parity][Cout][tap][Cin] the forward kernel reads.
+ *   x  [B][IH][IW][Cin] the layer's input, dy [B][OH][OW][Cout] the gradient of its pre-activation output, both NHWC fp32.
+ *   splits: the pixel range is cut into that many pieces, each summed into a slab of its own in `workspace`, and a second
+ *   launch adds the slabs in order; 0 = the plan's choice (enough to fill the chip).
+ * COGV_ERR_ARG: null or misaligned (16 B) pointers, Cin % 4, Cout % 8, odd IH / IW for the k4 s2 convolution, a workspace
+ * smaller than cogv_conv_wgrad_workspace_bytes; COGV_ERR_UNSUPPORTED: COGV_CONV_3X3_S1 (no weight gradient). */
+typedef struct cogv_conv_wgrad_desc {
+  int kind; int B, IH, IW, Cin, Cout;
+  int splits;
+  const void* x; const void* dy; void* dw;
+  void* workspace; size_t workspace_bytes;
+} cogv_conv_wgrad_desc;
+/* HOST ONLY (pointers are not looked at): plan = {splits, pixels per split, workgroups, Cout tiles, tap*Cin tiles, parities} */
+#define COGV_CONV_WGRAD_PLAN_INTS 6
+int cogv_conv_wgrad_plan(const cogv_conv_wgrad_desc* d, int* plan);
+/* HOST ONLY: bytes of slabs the plan needs (0 for one split or a refused descriptor) */
+size_t cogv_conv_wgrad_workspace_bytes(const cogv_conv_wgrad_desc* d);
+int cogv_conv_wgrad_nhwc_f32(const cogv_conv_wgrad_desc* d, void* stream);
+/* ReLU backward fused with the bias gradient (nn.ReLU / the bias of F.conv2d at :121-129, :172-192), rows of C floats:
+ *   dx[m][c] = act[m][c] > 0 ? dy[m][c] : 0   (act: the saved POST-ReLU activation; NULL: no mask; dx may be dy, or NULL)
+ *   db[c]    = sum_m of that -- the gradient of the layer's pre-activation output summed per channel (act == NULL: of dy).
+ * Per-workgroup partial sums in `workspace`, added in workgroup order by a second launch.  C % 4 == 0. */
+size_t cogv_relu_bias_bwd_workspace_bytes(int64_t M, int C);
+int cogv_relu_bias_bwd_f32(const float* dy, const float* act, float* dx, float* db, float* workspace, size_t workspace_bytes,
+                           int64_t M, int C, void* stream);
+/* Codebook statistics (:68-69 embed_onehot.sum(0), flatten.transpose(0, 1) @ embed_onehot) through an inverted index
+ * instead of the one-hot product: count[j] = #{m : ids[m] == j} (int32 [n_embed]), sum[j][:] = sum of x[m][:] over those m
+ * in ascending m ([n_embed][D], zeros for a code without pixels).  x [M][D]; D % 4 == 0, D <= 1024, n_embed <= 32768
+ * (COGV_ERR_UNSUPPORTED beyond); ids outside [0, n_embed) are ignored. */
+size_t cogv_vq_code_stats_workspace_bytes(int M, int D, int n_embed);
+int cogv_vq_code_stats_f32(const int64_t* ids, const float* x, int* count, float* sum, void* workspace, size_t workspace_bytes,
+                           int M, int D, int n_embed, void* stream);
+/* The EMA update :74-83 in place: cluster_size [n_embed], embed_avg and embed [D][n_embed] (the reference's layout);
+ *   cluster_size = cluster_size * decay + (1 - decay) * count;  embed_avg = embed_avg * decay + (1 - decay) * sum^T;
+ *   n = sum(cluster_size) -> n_out[0];  embed = embed_avg / ((cluster_size + eps) / (n + n_embed * eps) * n). */
+int cogv_vq_ema_update_f32(const int* count, const float* sum, float* cluster_size, float* embed_avg, float* embed, float* n_out,
+                           double decay, double eps, int D, int n_embed, void* stream);
+/* Backward of :85-86 (diff = (quantize.detach() - input).pow(2).mean(); quantize = input + (quantize - input).detach()):
+ *   g_x = g_q + g_diff[0] * 2 (x - q) / n;  g_q (may be NULL) arrives at the quantised map, g_diff (device scalar, may be
+ *   NULL) at diff; n = number of elements, n % 4 == 0. */
+int cogv_vq_ste_bwd_f32(const float* g_q, const float* g_diff, const float* x, const float* q, float* g_x, int64_t n,
+                        void* stream);
+
 /* ------------------------------------------------------------------ tokenizer ingest: raw uint8 images -> encoder input
  * replaces transforms.Resize(S) / CenterCrop(S) / ToTensor() / Normalize(mean, std) on PIL images at
  * data_utils/vqvae_tokenizer.py:72-82 (read_img) and preprocess_entry.py:87-106, and the layout launch
