@@ -135,6 +135,7 @@ class ConvDesc(C.Structure):
         ("in", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("out", C.c_void_p),
         ("rgb_w", C.c_void_p), ("rgb_partial", C.c_void_p),
         ("relu_in", C.c_int), ("residual", C.c_void_p), ("relu_residual", C.c_int),
+        ("precision", C.c_int), ("w_limbs", C.c_void_p),
     ]
 
 
@@ -174,6 +175,7 @@ class ScoreDesc(C.Structure):
 
 
 CONV_4X4_S2, CONV_1X1, CONVT_4X4_S2, CONV_3X3_S1 = 0, 1, 2, 3
+CONV_FP32, CONV_BF16X3 = 0, 1          # cogv_conv_desc.precision
 
 _vp, _i, _f, _u64, _i64, _sz = C.c_void_p, C.c_int, C.c_float, C.c_uint64, C.c_int64, C.c_size_t
 
@@ -240,6 +242,7 @@ SIGNATURES = {
     "cogv_cast_flat": (_i, [_i, _vp, _vp, _sz, _vp]),
     "cogv_cast_flat_back": (_i, [_i, _vp, _vp, _sz, _vp]),
     "cogv_conv2d_nhwc_f32": (_i, [C.POINTER(ConvDesc), _vp]),
+    "cogv_conv_split_weights": (_i, [_vp, _vp, _sz, _vp]),
     "cogv_rgb_finalize_f32": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), _vp]),
     "cogv_vq_argmin_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "cogv_nchw3_to_nhwc4_f32": (_i, [_vp, _vp, _i, _i, _i, _vp]),

@@ -11,9 +11,16 @@ _STD = (0.30379, 0.32279, 0.32800)
 _MEAN = (0.79093, 0.76271, 0.75340)
 
 
-def new_model():
-    """The pretrained tokenizer's architecture (vqvae/api.py:12-20)."""
-    return VQVAE(channel=512, n_res_block=0, n_res_channel=32, embed_dim=256, n_embed=8192, stride=6)
+def new_model(precision="fp32"):
+    """The pretrained tokenizer's architecture (vqvae/api.py:12-20).  precision: see set_precision."""
+    return VQVAE(channel=512, n_res_block=0, n_res_channel=32, embed_dim=256, n_embed=8192, stride=6).set_precision(precision)
+
+
+def set_precision(model, precision):
+    """"fp32" (default, the exact-fp32 convolutions) or "bf16x3" (VQVAE.set_precision: the eval-mode convolutions on the
+    split-bf16 kernel).  img2code, img2code_raw, code2img, code2img_u8 and save_image of a model's images honour it; the
+    nearest-code search, the embedding lookup, ingest, egress and train_step do not change with it.  Returns the model."""
+    return model.set_precision(precision)
 
 
 def img2code(model, img):

@@ -9,6 +9,11 @@ Every OTHER topology the reference's constructors can build (vqvae/vqvae_zc.py:1
 any number of ResBlocks) runs through a generic interpreter of the same block list on the same kernels (round 4: 3x3
 convolution, input ReLU and residual add in the convolution kernel) -- channel counts a multiple of 8.
 
+Precision (eval mode only): VQVAE.set_precision("bf16x3") runs every convolution of both stacks -- fast path and interpreter --
+on the split-bf16 kernel (cogview_amd/csrc/conv_split.hip: three bf16 limbs per fp32 operand, six products, fp32 accumulation);
+the default "fp32" is the exact-fp32 kernel.  The nearest-code search, the embedding lookup and every training launch are the
+same exact-fp32 code in both modes.
+
 Training (module.train(), vqvae/vqvae_zc.py:67-86): the default, non-relaxed path of every topology made of 4x4 stride-2
 convolutions, 4x4 stride-2 transposed convolutions, 1x1 convolutions and ReLU (new_model() and every n_res_block=0 stride-6
 configuration).  The stacks run layer by layer, each layer a torch.autograd.Function on the kernels of
@@ -33,10 +38,32 @@ def _p(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
-def _conv(kind, x, w, bias, cout, relu, rgb=None, relu_in=False, residual=None, relu_residual=False):
+PRECISIONS = ("fp32", "bf16x3")
+
+
+def split_weight_limbs(wp):
+    """The three bf16 limb planes of a packed fp32 weight (cogv_conv_split_weights): int16 [3, *wp.shape], plane 0 the most
+    significant; the planes sum back to wp bit for bit.  What _conv(precision="bf16x3") reads instead of wp."""
+    if not wp.is_cuda:
+        raise L.CogviewHipError("cogview_amd.vqvae runs only on an MI355X (HIP) device; there is no CPU fallback")
+    wp = wp.contiguous()
+    limbs = torch.empty((3,) + tuple(wp.shape), dtype=torch.int16, device=wp.device)
+    L.check(L.lib().cogv_conv_split_weights(_p(wp), _p(limbs), wp.numel(), _stream()), "cogv_conv_split_weights")
+    return limbs
+
+
+def _conv(kind, x, w, bias, cout, relu, rgb=None, relu_in=False, residual=None, relu_residual=False, precision="fp32",
+          w_limbs=None):
     """x NHWC fp32 contiguous -> NHWC fp32.  rgb = (w_rgb [3, cout], bias_rgb [3], scale, shift): the decoder's final
     1x1 convolution (and the de-normalisation of api.code2img) fused into this layer's epilogue -- the layer's own
-    output tensor is never written; returns the NCHW image [b, 3, oh, ow]."""
+    output tensor is never written; returns the NCHW image [b, 3, oh, ow].
+    precision: "fp32" (the exact-fp32 kernel; w_limbs ignored) or "bf16x3" (the split-bf16 kernel on w_limbs =
+    split_weight_limbs(w): fp32-class accuracy, not the exact path's bits).  The fused RGB projection's own arithmetic and
+    rgb_finalize are the same fp32 code in both."""
+    if precision not in PRECISIONS:
+        raise ValueError(f"precision must be one of {PRECISIONS}, not {precision!r}")
+    if precision == "bf16x3" and w_limbs is None:
+        raise ValueError('precision="bf16x3" needs w_limbs (split_weight_limbs of the packed weight)')
     if not x.is_cuda:
         raise L.CogviewHipError("cogview_amd.vqvae runs only on an MI355X (HIP) device; there is no CPU fallback")
     b, ih, iw, cin = x.shape
@@ -54,6 +81,9 @@ def _conv(kind, x, w, bias, cout, relu, rgb=None, relu_in=False, residual=None, 
         d.residual = residual.data_ptr()
     setattr(d, "in", x.data_ptr())
     d.w, d.bias = w.data_ptr(), (None if bias is None else bias.data_ptr())      # no bias: the data gradient of a layer
+    if precision == "bf16x3":
+        assert w_limbs.shape == (3,) + tuple(w.shape) and w_limbs.dtype == torch.int16 and w_limbs.is_contiguous()
+        d.precision, d.w_limbs = L.CONV_BF16X3, w_limbs.data_ptr()
     if rgb is None:
         out = torch.empty((b, oh, ow, cout), dtype=torch.float32, device=x.device)
         d.out = out.data_ptr()
@@ -65,7 +95,7 @@ def _conv(kind, x, w, bias, cout, relu, rgb=None, relu_in=False, residual=None, 
     taps = {L.CONV_4X4_S2: 16, L.CONV_1X1: 1, L.CONVT_4X4_S2: 4, L.CONV_3X3_S1: 9}[kind]
     npix_out = b * oh * ow
     with ops.timed_launch("conv", 2.0 * npix_out * cout * taps * cin, 4.0 * (x.numel() + w.numel() + out.numel()),
-                          f"kind{kind} {b}x{ih}x{iw}x{cin}->{cout}"):
+                          f"kind{kind} {b}x{ih}x{iw}x{cin}->{cout}" + (" bf16x3" if precision == "bf16x3" else "")):
         L.check(L.lib().cogv_conv2d_nhwc_f32(C.byref(d), _stream()), "cogv_conv2d_nhwc_f32")
     if rgb is not None:
         img = torch.empty((b, 3, oh, ow), dtype=torch.float32, device=x.device)
@@ -224,13 +254,24 @@ class _ConvStack(nn.Module):
         super().__init__()
         self.blocks = nn.Sequential(*blocks)
         self._packed = None
+        self._precision = "fp32"          # VQVAE.set_precision; eval-mode launches only
 
     def _weights(self, packers):
         key = tuple((m.weight.data_ptr(), m.weight._version) for m in self.blocks if hasattr(m, "weight"))
         if self._packed is None or self._packed[0] != key:
             mods = [m for m in self.blocks if hasattr(m, "weight")]
-            self._packed = (key, [(pk(m.weight), m.bias.detach().float().contiguous()) for pk, m in zip(packers, mods)])
+            self._packed = (key, [(pk(m.weight), m.bias.detach().float().contiguous()) for pk, m in zip(packers, mods)], None)
         return self._packed[1]
+
+    def _limbs(self, packers, n):
+        """split_weight_limbs of the first n packed weights of _weights(packers) (None in "fp32" mode).  They live in the
+        same cache entry under the same key: a weight update drops both."""
+        packed = self._weights(packers)
+        if self._precision != "bf16x3":
+            return [None] * n
+        if self._packed[2] is None:
+            self._packed = self._packed[:2] + ([split_weight_limbs(w) for w, _ in packed[:n]],)
+        return self._packed[2]
 
 
 class ResBlock(nn.Module):
@@ -280,11 +321,13 @@ def _pack_generic(m):
     return kind, wp.contiguous(), bias, cout
 
 
-def run_block_list(blocks, x, cache):
+def run_block_list(blocks, x, cache, precision="fp32"):
     """Interpret an nn.Sequential of the reference's block vocabulary (Conv2d 4x4s2 / 3x3 / 1x1, ConvTranspose2d 4x4s2 / 1x1,
     ReLU, ResBlock) on NHWC fp32 activations.  A ReLU that follows a convolution rides in that convolution's epilogue; a
     ReLU that follows a ResBlock (or opens one) is applied to the input of the next convolution inside the kernel.  Padded
-    output channels (zero filters) are carried as zeros and ignored by the next layer's zero-padded input channels."""
+    output channels (zero filters) are carried as zeros and ignored by the next layer's zero-padded input channels.
+    precision="bf16x3" runs every convolution on the split-bf16 kernel; the limb planes are made on first use and kept in
+    the cache entry of the packed weight they were made from."""
     mods = list(blocks)
     relu_pending = False
     i = 0
@@ -296,11 +339,17 @@ def run_block_list(blocks, x, cache):
             kind, wp, bias, _ = _pack_generic(m)
             if x.shape[-1] > wp.shape[-1]:               # the previous layer's zero-padded output channels: zero weights for them
                 wp = torch.nn.functional.pad(wp, (0, x.shape[-1] - wp.shape[-1])).contiguous()
-            cache[key] = (ver, (kind, wp, bias))
+            cache[key] = (ver, (kind, wp, bias), None)
         kind, wp, bias = cache[key][1]
+        limbs = None
+        if precision == "bf16x3":
+            if cache[key][2] is None:
+                cache[key] = cache[key][:2] + (split_weight_limbs(wp),)
+            limbs = cache[key][2]
         if x.shape[-1] < wp.shape[-1]:
             x = torch.nn.functional.pad(x, (0, wp.shape[-1] - x.shape[-1]))
-        return _conv(kind, x, wp, bias, bias.numel(), relu_out, relu_in=relu_in, residual=residual, relu_residual=relu_residual)
+        return _conv(kind, x, wp, bias, bias.numel(), relu_out, relu_in=relu_in, residual=residual, relu_residual=relu_residual,
+                     precision=precision, w_limbs=limbs)
 
     while i < len(mods):
         m = mods[i]
@@ -459,13 +508,15 @@ class Encoder(_ConvStack):
             y = train_block_list(self.blocks, x4)
             return y[..., :self.embed_dim].contiguous() if y.shape[-1] != self.embed_dim else y
         if not self._fast:
-            y = run_block_list(self.blocks, x4, self._generic_cache)
+            y = run_block_list(self.blocks, x4, self._generic_cache, self._precision)
             return y[..., :self.embed_dim].contiguous() if y.shape[-1] != self.embed_dim else y
         (w1, b1), (w2, b2), (w3, b3), (w4, b4) = self._weights([pack_conv_weight] * 4)
-        y = _conv(L.CONV_4X4_S2, x4, w1, b1, self.channel, True)
-        y = _conv(L.CONV_4X4_S2, y, w2, b2, self.channel, True)
-        y = _conv(L.CONV_4X4_S2, y, w3, b3, self.channel, True)     # ReLU of blocks[5] folded into this epilogue
-        return _conv(L.CONV_1X1, y, w4, b4, self.embed_dim, False)
+        l1, l2, l3, l4 = self._limbs([pack_conv_weight] * 4, 4)
+        pr = self._precision
+        y = _conv(L.CONV_4X4_S2, x4, w1, b1, self.channel, True, precision=pr, w_limbs=l1)
+        y = _conv(L.CONV_4X4_S2, y, w2, b2, self.channel, True, precision=pr, w_limbs=l2)
+        y = _conv(L.CONV_4X4_S2, y, w3, b3, self.channel, True, precision=pr, w_limbs=l3)     # ReLU of blocks[5] folded into this epilogue
+        return _conv(L.CONV_1X1, y, w4, b4, self.embed_dim, False, precision=pr, w_limbs=l4)
 
 
 class Decoder(_ConvStack):
@@ -495,7 +546,7 @@ class Decoder(_ConvStack):
 
     def forward_nhwc(self, q_nhwc, scale=None, shift=None):
         if self.training or not self._fast:
-            run = train_block_list if self.training else (lambda b, x: run_block_list(b, x, self._generic_cache))
+            run = train_block_list if self.training else (lambda b, x: run_block_list(b, x, self._generic_cache, self._precision))
             y = run(self.blocks, q_nhwc.contiguous().float())
             img = y[..., :self.out_channel].permute(0, 3, 1, 2).contiguous()
             if scale is not None:
@@ -503,13 +554,16 @@ class Decoder(_ConvStack):
             if shift is not None:
                 img = img + torch.tensor(shift, device=img.device, dtype=img.dtype).view(1, -1, 1, 1)
             return img
-        (w1, b1), (w2, b2), (w3, b3), (w4, b4) = self._weights([pack_convt_weight] * 3 + [lambda w: w.detach().float().reshape(3, -1).contiguous()])
-        y = _conv(L.CONVT_4X4_S2, q_nhwc.contiguous(), w1, b1, self.channel, True)
-        y = _conv(L.CONVT_4X4_S2, y, w2, b2, self.channel, True)
+        packers = [pack_convt_weight] * 3 + [lambda w: w.detach().float().reshape(3, -1).contiguous()]
+        (w1, b1), (w2, b2), (w3, b3), (w4, b4) = self._weights(packers)
+        l1, l2, l3 = self._limbs(packers, 3)             # the final 1x1 -> RGB stays fp32 arithmetic in both modes
+        pr = self._precision
+        y = _conv(L.CONVT_4X4_S2, q_nhwc.contiguous(), w1, b1, self.channel, True, precision=pr, w_limbs=l1)
+        y = _conv(L.CONVT_4X4_S2, y, w2, b2, self.channel, True, precision=pr, w_limbs=l2)
         if self.channel % 128 == 0:
             # production width: the last transposed convolution projects straight to RGB in its epilogue
-            return _conv(L.CONVT_4X4_S2, y, w3, b3, self.channel, True, rgb=(w4, b4, scale, shift))
-        y = _conv(L.CONVT_4X4_S2, y, w3, b3, self.channel, True)
+            return _conv(L.CONVT_4X4_S2, y, w3, b3, self.channel, True, rgb=(w4, b4, scale, shift), precision=pr, w_limbs=l3)
+        y = _conv(L.CONVT_4X4_S2, y, w3, b3, self.channel, True, precision=pr, w_limbs=l3)
         b, h, w, c = y.shape
         out = torch.empty((b, 3, h, w), dtype=torch.float32, device=y.device)
         sc = (C.c_float * 3)(*scale) if scale is not None else None
@@ -534,6 +588,24 @@ class VQVAE(nn.Module):
         self.quantize_t = Quantize(embed_dim, n_embed)
         self.dec = Decoder(in_channel=embed_dim, out_channel=in_channel, channel=channel, n_res_block=n_res_block,
                            n_res_channel=n_res_channel, stride=stride - 2, simple=simple)
+
+    @property
+    def precision(self):
+        """"fp32" or "bf16x3": what the eval-mode convolutions run on (set_precision)."""
+        return self.enc_b._precision
+
+    def set_precision(self, precision):
+        """"fp32" (default): every convolution on the exact-fp32 MFMA kernel.  "bf16x3": the eval-mode convolutions of the
+        encoder and the decoder (fast path and run_block_list alike) on the split-bf16 kernel -- three bf16 limbs per operand,
+        six products, fp32 accumulation: fp32-class accuracy at a higher matrix rate, but not the exact path's bits, so an id
+        whose two nearest codes are a near-tie may differ.  Deliberately unchanged by the mode: vq_argmin (the distance
+        product that decides an id stays exact fp32), embed_code, rgb_finalize, image_prep and image_grid; and every
+        training-mode launch -- train_block_list, _ConvLayer, the data gradient and conv_wgrad stay exact fp32, a model in
+        .train() ignores the mode.  Returns self."""
+        if precision not in PRECISIONS:
+            raise ValueError(f"precision must be one of {PRECISIONS}, not {precision!r}")
+        self.enc_b._precision = self.dec._precision = precision
+        return self
 
     def encode(self, input, continuous_relax=False, temperature=1., hard=False, KL=False):
         """-> (quantised NCHW, diff [1], ids [b, h/8, w/8]) as vqvae/vqvae_zc.py:251-259."""

@@ -576,6 +576,7 @@ int cogv_score_targets(const cogv_score_desc* d, void* stream);
  *                                              (the non-production encoders :147, :154 and ResBlock :105)
  *   COGV_CONVT_4X4_S2 (ConvTranspose2d k4 s2 p1) 4 parities z = py*2+px (output pixel (2y+py, 2x+px)), 4 taps
  *        W_packed[z][co][ty*2+tx][ci] = W[ci][co][ky][kx],  ky = (py ? 2*ty : 1+2*ty),  kx = (px ? 2*tx : 1+2*tx)
+ * Opt-in: cogv_conv_desc.precision = COGV_CONV_BF16X3 runs a layer on bf16 MFMA at fp32 accuracy (three bf16 limbs per operand).
  */
 #define COGV_CONV_4X4_S2 0
 #define COGV_CONV_1X1 1
@@ -593,8 +594,24 @@ typedef struct cogv_conv_desc {
    * (same NHWC shape as out, 16-byte aligned, may be NULL) is added after bias / ReLU, through max(., 0) when relu_residual is
    * set -- the reference's leading nn.ReLU(inplace=True) overwrites the block's input, so what it adds back is relu(input). */
   int relu_in; const void* residual; int relu_residual;
+  /* precision: COGV_CONV_FP32 (0: a zeroed field is the exact-fp32 path, v_mfma_f32_32x32x2_f32) or COGV_CONV_BF16X3 (the
+   * same layer, same epilogues, on v_mfma_f32_32x32x16_bf16: every fp32 operand is the exact sum of three bf16 limbs and the
+   * six limb products with i + j <= 2 are accumulated in fp32, smallest first, in a fixed order (the five small ones apart from
+   * x0*y0, joined at the end) -- fp32-class accuracy, NOT the bits of the exact path).  BF16X3 reads the weights from w_limbs (cogv_conv_split_weights of the same packed tensor `w`,
+   * 16-byte aligned); `w` must still be valid.  Any other precision, or BF16X3 with w_limbs NULL or misaligned: COGV_ERR_ARG
+   * before any launch. */
+  int precision; const void* w_limbs;
 } cogv_conv_desc;
+#define COGV_CONV_FP32 0
+#define COGV_CONV_BF16X3 1
 int cogv_conv2d_nhwc_f32(const cogv_conv_desc* d, void* stream);
+/* The three bf16 limb planes of a packed fp32 weight tensor of n elements (any of the layouts above; n % 4 == 0), for
+ * COGV_CONV_BF16X3 -- the fast mode of the F.conv2d / F.conv_transpose2d calls cogv_conv2d_nhwc_f32 replaces
+ * (vqvae/vqvae_zc.py:121-129, :159-164, :172-192, ResBlock :105-108).  limbs = 3 * n uint16 (6 n bytes, 16-byte aligned):
+ * plane p (0 = most significant) occupies elements [p * n, (p + 1) * n) in the element order of w, and holds the top 16
+ * bits of r_p, with r_0 = w, r_{p+1} = r_p - bf16bits(r_p) (truncation: every subtraction is exact, the limbs sum back to w
+ * exactly for |w| above about 2^-110, where the third limb is still inside bf16's exponent range -- and nothing can overflow). */
+int cogv_conv_split_weights(const float* w, void* limbs, size_t n, void* stream);
 /* out NCHW [B,3,H,W] = (sum over the ntiles partial planes + bias[c]) * scale[c] + shift[c] (scale/shift: 3 HOST floats or NULL) */
 int cogv_rgb_finalize_f32(const float* partial, int ntiles, const float* bias, float* out, int B, int H, int W,
                           const float* scale3_host, const float* shift3_host, void* stream);
