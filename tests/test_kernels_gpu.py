@@ -3,6 +3,7 @@
 Tolerances (relative L2 error ||hip - oracle|| / ||oracle||, oracle in fp32 on the inputs rounded to the
 storage type): fp16 3e-3, bf16 2e-2 for single kernels whose output is rounded once to 16 bits
 (bf16 has 8 significant bits: 2^-9 = 2e-3 per element before any accumulation effects).
+The Sandwich-LN kernels are judged element by element, every form and loop path, by tests/test_layernorm_cells_gpu.py.
 """
 import math
 import os

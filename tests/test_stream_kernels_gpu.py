@@ -9,6 +9,7 @@
 
 Tolerances: results stored in fp32 are compared at 2e-6 (they carry no storage rounding); 16-bit results at the
 single-kernel bars of test_kernels_gpu.py (fp16 3e-3, bf16 2e-2).
+The element-wise judge of the Sandwich-LN kernels (fp64 reference, guarded operands) is tests/test_layernorm_cells_gpu.py.
 """
 import pytest
 import torch
