@@ -19,30 +19,19 @@
 // The k-slot relabelling trick (attention.hip) lets one ds_read_b128 feed four MFMA k-steps.
 #include "common.cuh"
 #include "cogview_hip.h"
-#include "conv_args.cuh"
-#include "conv_taps.cuh"
+#include "conv_tile.cuh"
 
 #include <cstdlib>
 #include <type_traits>
 
 namespace {
 
-// BM / BN / BK / NT, ConvArgs and conv_fill_args (descriptor -> arguments, every refusal): conv_args.cuh, shared with conv_split.hip
-
+// BM / BN / BK / NT, ConvArgs and conv_fill_args (descriptor -> arguments, every refusal): conv_args.cuh
 // tap_offset(kind, z, tap, dy, dx): conv_taps.cuh (shared with the weight gradient, conv_bwd.hip)
+// ld4 / ld4_async, ConvTile / conv_tile, RowCtx / make_a_ctx / load_a and conv_epilogue: conv_tile.cuh (shared with conv_split.hip)
 
 __device__ __forceinline__ int swz(int row) { return ((row >> 1) & 7) ^ ((row >> 4) & 7); }
 
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-// Asynchronous 16-byte load: issued through inline asm so that the COMPILER does not track it -- its own vmcnt
-// bookkeeping turned "tile kt+1 is needed, tile kt+2 may stay in flight" into vmcnt(0) (it drained both register sets
-// before every park in LDS, and half of the older set before issuing the newer one).  The consumer must call
-// wait_loads<N>() on the destination registers before the first use (loads return in order: N = number of younger loads
-// that may remain outstanding).  Must not be spilled around (cogview_amd/csrc/build.py scan_asm_hazards: no scratch access
-// and no read of a destination register while the load is in flight).
-__device__ __forceinline__ void ld4_async(f32x4& dst, const float* p) {
-  asm volatile("global_load_dwordx4 %0, %1, off" : "=&v"(dst) : "v"(p) : "memory");
-}
 // all asynchronous loads retired; the operands tie BOTH register sets to the wait, so that the compiler cannot reuse
 // a register an in-flight load still targets (found by build.py's asm_load_hazards: the epilogue's address arithmetic
 // had been scheduled into those registers in front of a bare s_waitcnt)
@@ -59,33 +48,8 @@ __device__ __forceinline__ void wait_loads(f32x4 (&a)[4], f32x4 (&b)[4]) {
                : "n"(N) : "memory");
 }
 
-// Operand staging.  thread t -> (tile row t/8 + 32 q for q = 0..3, 16-byte chunk t%8 of the 128-byte k-slice).
-// Every load of a k-tile is UNCONDITIONAL, from a clamped (always valid) address, and the rows / taps that fall outside
-// the image are zeroed when the registers are parked in LDS: a `v = 0; if (inside) v = load` form makes the compiler
-// wait for each load before issuing the next one (the select needs the loaded value), which serialises eight memory
-// latencies per k-tile -- measured: MFMA pipe 57 % busy with the waves waiting on vmcnt.
-struct RowCtx {            // per thread, fixed for the whole tile: its four pixels (A) / rows (B)
-  const float* base[4];    // A: &in[b][0][0][0] of row q's image;   B: &w[n][4 * (t & 7)]
-  int y0[4], x0[4];        // A: y * in_mul, x * in_mul
-  uint32_t valid;          // bit q: the row exists (m < M / n < N)
-};
-__device__ __forceinline__ RowCtx make_a_ctx(const ConvArgs& p, int m0) {
-  RowCtx c; c.valid = 0u;
-  const int t = threadIdx.x;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int m = m0 + (t >> 3) + 32 * q;
-    const bool ok = m < p.M;
-    const int mm = ok ? m : 0;
-    const int b = mm / (p.GH * p.GW);
-    const int rem = mm - b * (p.GH * p.GW);
-    const int y = rem / p.GW, x = rem - y * p.GW;
-    c.base[q] = p.in + (size_t)b * p.IH * p.IW * p.Cin;
-    c.y0[q] = y * p.in_mul; c.x0[q] = x * p.in_mul;
-    c.valid |= ok ? (1u << q) : 0u;
-  }
-  return c;
-}
+// a RowCtx over the rows of a row-major [N][ldw] matrix (the weights; x and E^T in the nearest-code search): base = row
+// start, valid = n < N, no pixel coordinates
 __device__ __forceinline__ RowCtx make_b_ctx(const float* w, int ldw, int n0, int N) {
   RowCtx c; c.valid = 0u;
   const int t = threadIdx.x;
@@ -98,37 +62,6 @@ __device__ __forceinline__ RowCtx make_b_ctx(const float* w, int ldw, int n0, in
     c.valid |= ok ? (1u << q) : 0u;
   }
   return c;
-}
-// A tile: 128 pixels x 32 k; chunk = 4 consecutive k = 4 channels of one tap.  Returns the 4-bit keep mask.
-// Offsets inside one image are 32-bit (IH * IW * Cin < 2^31, checked by the launcher); the products use the
-// full-rate 24-bit multiplier (iy, ix < 2^15 and IW * Cin, Cin < 2^24, checked by the launcher).
-template <bool UNIFORM_TAP>
-__device__ __forceinline__ uint32_t load_a(const ConvArgs& p, const RowCtx& c, int z, int k0, f32x4 (&r)[4]) {
-  const int t = threadIdx.x;
-  int dy, dx, ci; bool kok;
-  if (UNIFORM_TAP) {           // Cin % 32 == 0: the whole k-tile lies inside one tap -> scalar arithmetic
-    const int tap = __builtin_amdgcn_readfirstlane(k0 / p.Cin);
-    kok = true;                                        // K % 32 == 0 as well
-    tap_offset(p.kind, z, tap, dy, dx);
-    ci = k0 - tap * p.Cin + (t & 7) * 4;
-  } else {
-    const int k = k0 + (t & 7) * 4;
-    kok = k < p.K;
-    const int tap = kok ? k / p.Cin : 0;
-    ci = kok ? k - tap * p.Cin : 0;
-    tap_offset(p.kind, z, tap, dy, dx);
-  }
-  const int row_pitch = p.IW * p.Cin;
-  uint32_t keep = 0u;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int iy = c.y0[q] + dy, ix = c.x0[q] + dx;
-    const bool ok = kok && ((c.valid >> q) & 1u) && (unsigned)iy < (unsigned)p.IH && (unsigned)ix < (unsigned)p.IW;
-    const int off = ok ? __mul24(iy, row_pitch) + __mul24(ix, p.Cin) + ci : 0;
-    ld4_async(r[q], c.base[q] + off);
-    keep |= ok ? (1u << q) : 0u;
-  }
-  return keep;
 }
 // B tile: 128 rows x 32 k from a row-major [N][ldw] matrix (weights W[z][co][K]; x / E^T in the nearest-code search)
 __device__ __forceinline__ uint32_t load_b(const RowCtx& c, int k0, int K, f32x4 (&r)[4]) {
@@ -190,27 +123,12 @@ __device__ __forceinline__ void mma_tile(const char* la, const char* lb, int wm,
   }
 }
 
-// Workgroup -> (pixel tile, channel tile, parity): the grid is one-dimensional and XCD-aware.  Hardware hands
-// consecutive workgroup ids to the 8 XCDs round-robin, each XCD has its own 4-MiB L2, and 64 workgroups run on an XCD at
-// a time (2 per CU).  An XCD therefore takes a contiguous chunk of pixel tiles and walks it with (channel tile, parity)
-// varying fastest: the 64 concurrent workgroups are 64 / (channel tiles x parities) neighbouring pixel tiles times ALL
-// their channel tiles / parities, so every activation line is fetched into that L2 once and hit by the other
-// workgroups, and the weight slices are shared by the pixel tiles in flight.  (With a plain 3-D grid the workgroups
-// that read the same activations sat on different XCDs or ran far apart in time: 50 % L2 hit rate, the input tensor
-// streamed from HBM once per channel tile and parity -- 16 times for the last transposed convolution.)
 template <bool UT, int EXP = 0>      // UT: Cin % 32 == 0 (every k-tile lies inside one tap); EXP: timing probes (wrong results)
 __global__ __launch_bounds__(NT, 2) void conv_kernel(const ConvArgs p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];     // 2 stages x (A 16K + B 16K) = 64 KiB
-  const int mtiles = (p.M + BM - 1) / BM, ntiles = (p.Cout + BN - 1) / BN;
-  const int per = ntiles * p.nz, chunk = (mtiles + 7) >> 3;
-  const int xcd = blockIdx.x & 7, local = blockIdx.x >> 3;
-  const int mt = xcd * chunk + local / per, yz = local % per;
-  if (mt >= mtiles) return;
-  const int z = yz / ntiles;
-  const int m0 = mt * BM, n0 = (yz - z * ntiles) * BN;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
-  const int fr = lane & 31, fg = lane >> 5;
+  const ConvTile tile = conv_tile(p);               // conv_tile.cuh: the XCD-aware walk of the one-dimensional grid
+  if (!tile.live) return;
+  const int z = tile.z(), m0 = tile.m0(), n0 = tile.n0(z), wm = tile.wm(), wn = tile.wn(), fr = tile.fr(), fg = tile.fg();
   const float* W = p.w + (size_t)z * p.w_parity_stride;
 
   f32x16 acc[2][2];
@@ -231,8 +149,8 @@ __global__ __launch_bounds__(NT, 2) void conv_kernel(const ConvArgs p) {
   // in-flight destination registers at the joins BEFORE the s_waitcnt of one branch -- stale data for nk == 1.
   f32x4 ra[2][4], rb[2][4];
   uint32_t ka[2], kb[2];
-  ka[0] = load_a<UT>(p, ctx, z, 0, ra[0]); kb[0] = load_b(bctx, 0, p.K, rb[0]);
-  ka[1] = load_a<UT>(p, ctx, z, min(1, nk - 1) * BK, ra[1]); kb[1] = load_b(bctx, min(1, nk - 1) * BK, p.K, rb[1]);
+  ka[0] = load_a<UT, true>(p, ctx, z, 0, ra[0]); kb[0] = load_b(bctx, 0, p.K, rb[0]);
+  ka[1] = load_a<UT, true>(p, ctx, z, min(1, nk - 1) * BK, ra[1]); kb[1] = load_b(bctx, min(1, nk - 1) * BK, p.K, rb[1]);
   wait_loads<8>(ra[0], rb[0]);
   const bool relu_in = p.relu_in != 0;
   store_tile(smem, ra[0], ka[0], relu_in); store_tile(smem + 16384, rb[0], kb[0]);
@@ -242,7 +160,7 @@ __global__ __launch_bounds__(NT, 2) void conv_kernel(const ConvArgs p) {
     constexpr int l = decltype(lc)::value, sset = decltype(sc)::value;
     if (!(EXP & 1)) {
       const int k2 = min(kt + 2, nk - 1) * BK;
-      ka[l] = load_a<UT>(p, ctx, z, k2, ra[l]); kb[l] = load_b(bctx, k2, p.K, rb[l]);
+      ka[l] = load_a<UT, true>(p, ctx, z, k2, ra[l]); kb[l] = load_b(bctx, k2, p.K, rb[l]);
     }
     __builtin_amdgcn_sched_barrier(0);     // nothing that needs tile kt+1's registers may move above the MFMAs
     mma_tile(smem + bo, smem + bo + 16384, wm, wn, fr, fg, acc);
@@ -267,63 +185,7 @@ __global__ __launch_bounds__(NT, 2) void conv_kernel(const ConvArgs p) {
 #pragma unroll
       for (int e = 0; e < 16; ++e)
         ct[(wm + 32 * i + (e & 3) + 8 * (e >> 2) + 4 * fg) * BN + wn + 32 * j + fr] = acc[i][j][e];
-  __syncthreads();
-  const int cchunk = (threadIdx.x & 15) * 8;
-#pragma unroll 1
-  for (int pass = 0; pass < 8; ++pass) {
-    const int row = pass * 16 + (threadIdx.x >> 4);
-    const int m = m0 + row, n = n0 + cchunk;
-    float rgb[3] = {0.f, 0.f, 0.f};
-    size_t pix = 0;
-    if (m < p.M && n < p.Cout) {
-      f32x4 x0 = ld4(ct + row * BN + cchunk), x1 = ld4(ct + row * BN + cchunk + 4);
-      if (p.bias) { const f32x4 b0 = ld4(p.bias + n), b1 = ld4(p.bias + n + 4); x0 += b0; x1 += b1; }
-      if (p.relu_out) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { x0[i] = fmaxf(x0[i], 0.f); x1[i] = fmaxf(x1[i], 0.f); }
-      }
-      const int b = m / (p.GH * p.GW);
-      const int rem = m - b * (p.GH * p.GW);
-      const int y = rem / p.GW, x = rem - y * p.GW;
-      const int oy = y * p.out_mul + (z >> 1), ox = x * p.out_mul + (z & 1);   // z = 0 unless transposed
-      if (!p.rgb_part) {
-        const size_t oidx = (((size_t)b * p.OH + oy) * p.OW + ox) * p.Cout + n;
-        if (p.residual) {      // residual block: out = conv(...) + [relu](input)  (vqvae/vqvae_zc.py:110-114, see cogview_hip.h)
-          f32x4 r0 = ld4(p.residual + oidx), r1 = ld4(p.residual + oidx + 4);
-          if (p.relu_res) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) { r0[i] = fmaxf(r0[i], 0.f); r1[i] = fmaxf(r1[i], 0.f); }
-          }
-          x0 += r0; x1 += r1;
-        }
-        float* o = p.out + oidx;
-        *reinterpret_cast<f32x4*>(o) = x0;
-        *reinterpret_cast<f32x4*>(o + 4) = x1;
-      } else {
-        // fused final 1x1 convolution (vqvae/vqvae_zc.py:190): this tile's 128 channels of the three output sums; the
-        // 134-MB-per-image activation of the last transposed convolution is never written
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          const f32x4 w0 = ld4(p.rgb_w + (size_t)c * p.Cout + n), w1 = ld4(p.rgb_w + (size_t)c * p.Cout + n + 4);
-          float r = 0.f;
-#pragma unroll
-          for (int i = 0; i < 4; ++i) { r = fmaf(x0[i], w0[i], r); r = fmaf(x1[i], w1[i], r); }
-          rgb[c] = r;
-        }
-        pix = ((size_t)b * p.OH + oy) * p.OW + ox;
-      }
-    }
-    if (p.rgb_part) {        // the 16 lanes of a row hold its 16 channel groups: fold them, lane 0 of the group stores
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        float r = rgb[c];
-        r += __shfl_xor(r, 1, 64); r += __shfl_xor(r, 2, 64); r += __shfl_xor(r, 4, 64); r += __shfl_xor(r, 8, 64);
-        rgb[c] = r;
-      }
-      if ((threadIdx.x & 15) == 0 && m < p.M)
-        *reinterpret_cast<f32x4*>(p.rgb_part + ((size_t)(n0 / BN) * ((size_t)p.B * p.OH * p.OW) + pix) * 4) = f32x4{rgb[0], rgb[1], rgb[2], 0.f};
-    }
-  }
+  conv_epilogue(p, ct, z, m0, n0);
 }
 
 // ---------------------------------------------------------------------------------------------------

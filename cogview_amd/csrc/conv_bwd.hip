@@ -9,12 +9,9 @@
 // No floating-point atomics: every sum has a fixed order, the same inputs give the same bits run after run.
 #include "common.cuh"
 #include "cogview_hip.h"
-#include "conv_taps.cuh"
+#include "conv_tile.cuh"      // ld4 / st4; NT, conv_geometry (conv_args.cuh); tap_offset (conv_taps.cuh)
 
 namespace {
-
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ void st4(float* p, const f32x4& v) { *reinterpret_cast<f32x4*>(p) = v; }
 
 // ---------------------------------------------------------------------------------------------------
 // Weight gradient.  As a GEMM: rows = output channels co, columns = k = tap * Cin + ci (the forward kernel's contraction
@@ -26,7 +23,6 @@ __device__ __forceinline__ void st4(float* p, const f32x4& v) { *reinterpret_cas
 // (pixel split s, parity z, co tile, k tile); split s writes slab s, wgrad_reduce_kernel adds the slabs in order.
 constexpr int TC = 128;      // channels per tile, both operands
 constexpr int KP = 32;       // pixels per contraction step
-constexpr int NT = 256;
 
 struct WgradArgs {
   const float* x; const float* dy; float* out;     // out: dW itself (one split) or the slabs
@@ -153,19 +149,13 @@ int wgrad_plan(const cogv_conv_wgrad_desc* d, WgradPlan& pl) {
   WgradArgs& a = pl.a;
   a.x = (const float*)d->x; a.dy = (const float*)d->dy; a.out = (float*)d->dw;
   a.B = d->B; a.IH = d->IH; a.IW = d->IW; a.Cin = d->Cin; a.Cout = d->Cout; a.kind = d->kind;
-  int ntaps;
-  a.nz = 1;
-  if (d->kind == COGV_CONV_4X4_S2) {
-    if ((d->IH & 1) || (d->IW & 1)) return COGV_ERR_ARG;
-    a.GH = a.OH = d->IH / 2; a.GW = a.OW = d->IW / 2; a.in_mul = 2; a.out_mul = 1; ntaps = 16;
-  } else if (d->kind == COGV_CONV_1X1) {
-    a.GH = a.OH = d->IH; a.GW = a.OW = d->IW; a.in_mul = 1; a.out_mul = 1; ntaps = 1;
-  } else if (d->kind == COGV_CONVT_4X4_S2) {
-    a.GH = d->IH; a.GW = d->IW; a.OH = 2 * d->IH; a.OW = 2 * d->IW; a.in_mul = 1; a.out_mul = 2; ntaps = 4; a.nz = 4;
-  } else return COGV_ERR_UNSUPPORTED;        // 3x3 (ResBlock, stride-4 / stride-2 encoders): no weight gradient
-  const long long M = (long long)a.B * a.GH * a.GW;
-  if (M >= (1ll << 31) - KP || (long long)ntaps * a.Cin >= (1 << 24)) return COGV_ERR_ARG;
-  a.M = (int)M; a.K = ntaps * a.Cin;
+  ConvGeom g;
+  const int rc = conv_geometry(d->kind, d->B, d->IH, d->IW, d->Cin, g);
+  if (rc != COGV_OK) return rc;
+  if (d->kind == COGV_CONV_3X3_S1) return COGV_ERR_UNSUPPORTED;        // 3x3 (ResBlock, stride-4 / stride-2 encoders): no weight gradient
+  if (g.M >= (1ll << 31) - KP || (long long)g.ntaps * a.Cin >= (1 << 24)) return COGV_ERR_ARG;
+  a.GH = g.GH; a.GW = g.GW; a.OH = g.OH; a.OW = g.OW; a.in_mul = g.in_mul; a.out_mul = g.out_mul; a.nz = g.nz;
+  a.M = (int)g.M; a.K = g.K;
   a.cot = (a.Cout + TC - 1) / TC; a.kt = (a.K + TC - 1) / TC;
   a.slab = (long long)a.nz * a.Cout * a.K;
   // when (tiles x parities) does not fill the chip -- the first and the last layer, small batches -- the pixel range is

@@ -1,7 +1,8 @@
 // Split-bf16 form of the tokenizer's implicit-GEMM convolution (COGV_CONV_BF16X3, see cogv_conv_desc in cogview_hip.h): the
 // layers of conv.hip -- same tap arithmetic (conv_taps.cuh), same NHWC fp32 activations, same packed weights
-// [parity][Cout][tap][Cin], same descriptor checks and grid (conv_args.cuh), same epilogues -- on v_mfma_f32_32x32x16_bf16
-// instead of the exact-fp32 v_mfma_f32_32x32x2_f32.
+// [parity][Cout][tap][Cin], same descriptor checks and grid (conv_args.cuh), and the very same tile walk, activation staging
+// and epilogue (conv_tile.cuh, one copy for both kernels) -- on v_mfma_f32_32x32x16_bf16 instead of the exact-fp32
+// v_mfma_f32_32x32x2_f32.
 //
 // Arithmetic.  Every fp32 operand x is the exact sum of three bf16 limbs, x = x0 + x1 + x2, made by truncation: x0 = the top
 // 16 bits of x, x1 = the top 16 bits of (x - x0), x2 = the top 16 bits of (x - x0 - x1).  Each subtraction is exact and the
@@ -24,11 +25,11 @@
 // against 1.12x for the double-buffered 96-KiB form (one workgroup per CU, one wave per SIMD, nothing to overlap).  A lane's
 // 8 k-values of one limb are one ds_read_b128; the 16-byte chunk index is XORed with (row >> 2) & 3, which spreads each of
 // the four 16-lane groups a ds_read_b128 is served in over all 64 banks (rows are 16 banks apart, 4 rows wrap around).
-// C/D lane map of 32x32x16_bf16 = that of 32x32x2_f32, so the epilogue is conv.hip's, statement for statement.
+// C/D lane map of 32x32x16_bf16 = that of 32x32x2_f32, so both kernels store their accumulators into the C tile the same
+// way and share one epilogue (conv_epilogue, conv_tile.cuh).
 #include "common.cuh"
 #include "cogview_hip.h"
-#include "conv_args.cuh"
-#include "conv_taps.cuh"
+#include "conv_tile.cuh"
 
 namespace {
 
@@ -42,80 +43,30 @@ struct SplitArgs {
   long long plane;           // elements per plane = nz * Cout * K
 };
 
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 __device__ __forceinline__ int swz(int row) { return (row >> 2) & 3; }
 
-// Operand staging: thread t -> (tile row t/8 + 32 q for q = 0..3, 4 consecutive k = piece t%8 of the 32-k slice), as conv.hip.
+// Operand staging: thread t -> (tile row t/8 + 32 q for q = 0..3, 4 consecutive k = piece t%8 of the 32-k slice).  The
+// activation side (RowCtx, make_a_ctx, load_a) is conv_tile.cuh's, with loads the compiler tracks; the weight side reads limb planes.
 // Every load is unconditional, from a clamped (always valid) address; what lies outside is zeroed when it is parked in LDS.
-struct RowCtx {
-  const float* base[4];      // A: &in[b][0][0][0] of row q's image
-  int y0[4], x0[4];          // A: y * in_mul, x * in_mul
-  long long wrow[4];         // B: element index of row q's first weight inside a plane
-  uint32_t valid;            // bit q: the row exists (m < M / n < Cout)
+struct WRowCtx {
+  long long wrow[4];         // element index of row q's first weight inside a plane
+  uint32_t valid;            // bit q: the row exists (n < Cout)
 };
-__device__ __forceinline__ RowCtx make_a_ctx(const ConvArgs& p, int m0) {
-  RowCtx c; c.valid = 0u;
-  const int t = threadIdx.x;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int m = m0 + (t >> 3) + 32 * q;
-    const bool ok = m < p.M;
-    const int mm = ok ? m : 0;
-    const int b = mm / (p.GH * p.GW);
-    const int rem = mm - b * (p.GH * p.GW);
-    const int y = rem / p.GW, x = rem - y * p.GW;
-    c.base[q] = p.in + (size_t)b * p.IH * p.IW * p.Cin;
-    c.y0[q] = y * p.in_mul; c.x0[q] = x * p.in_mul;
-    c.wrow[q] = 0;
-    c.valid |= ok ? (1u << q) : 0u;
-  }
-  return c;
-}
-__device__ __forceinline__ RowCtx make_b_ctx(const ConvArgs& p, int z, int n0) {
-  RowCtx c; c.valid = 0u;
+__device__ __forceinline__ WRowCtx make_b_ctx(const ConvArgs& p, int z, int n0) {
+  WRowCtx c; c.valid = 0u;
   const int t = threadIdx.x;
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const int n = n0 + (t >> 3) + 32 * q;
     const bool ok = n < p.Cout;
-    c.base[q] = nullptr; c.y0[q] = c.x0[q] = 0;
     c.wrow[q] = (long long)z * p.w_parity_stride + (long long)(ok ? n : 0) * p.K;
     c.valid |= ok ? (1u << q) : 0u;
   }
   return c;
 }
-// A tile: 128 pixels x 32 k of fp32; piece = 4 channels of one tap.  Returns the 4-bit keep mask (conv.hip load_a).
-template <bool UNIFORM_TAP>
-__device__ __forceinline__ uint32_t load_a(const ConvArgs& p, const RowCtx& c, int z, int k0, f32x4 (&r)[4]) {
-  const int t = threadIdx.x;
-  int dy, dx, ci; bool kok;
-  if (UNIFORM_TAP) {           // Cin % 32 == 0: the whole k-tile lies inside one tap -> scalar arithmetic
-    const int tap = __builtin_amdgcn_readfirstlane(k0 / p.Cin);
-    kok = true;
-    tap_offset(p.kind, z, tap, dy, dx);
-    ci = k0 - tap * p.Cin + (t & 7) * 4;
-  } else {
-    const int k = k0 + (t & 7) * 4;
-    kok = k < p.K;
-    const int tap = kok ? k / p.Cin : 0;
-    ci = kok ? k - tap * p.Cin : 0;
-    tap_offset(p.kind, z, tap, dy, dx);
-  }
-  const int row_pitch = p.IW * p.Cin;
-  uint32_t keep = 0u;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int iy = c.y0[q] + dy, ix = c.x0[q] + dx;
-    const bool ok = kok && ((c.valid >> q) & 1u) && (unsigned)iy < (unsigned)p.IH && (unsigned)ix < (unsigned)p.IW;
-    const int off = ok ? __mul24(iy, row_pitch) + __mul24(ix, p.Cin) + ci : 0;
-    r[q] = ld4(c.base[q] + off);
-    keep |= ok ? (1u << q) : 0u;
-  }
-  return keep;
-}
 // B tile: 128 weight rows x 32 k, three planes of bf16; piece = 4 k = 8 bytes (K % 4 == 0 keeps every piece inside its row
 // and 8-byte aligned).  A piece past the row's K columns loads the row start instead and is zeroed when parked.
-__device__ __forceinline__ uint32_t load_b(const SplitArgs& s, const RowCtx& c, int k0, u32x2 (&r)[4][3]) {
+__device__ __forceinline__ uint32_t load_b(const SplitArgs& s, const WRowCtx& c, int k0, u32x2 (&r)[4][3]) {
   const int kc = k0 + (threadIdx.x & 7) * 4;
   const bool kok = kc < s.c.K;
 #pragma unroll
@@ -209,21 +160,13 @@ __device__ __forceinline__ void mma_tile(const char* la, const char* lb, int wm,
         }
 }
 
-// Workgroup -> (pixel tile, channel tile, parity): the one-dimensional XCD-aware grid of conv.hip's conv_kernel.
 template <bool UT>      // UT: Cin % 32 == 0 (every k-tile lies inside one tap)
 __global__ __launch_bounds__(NT, 2) void conv_split_kernel(const SplitArgs s) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const ConvArgs& p = s.c;
-  const int mtiles = (p.M + BM - 1) / BM, ntiles = (p.Cout + BN - 1) / BN;
-  const int per = ntiles * p.nz, chunk = (mtiles + 7) >> 3;
-  const int xcd = blockIdx.x & 7, local = blockIdx.x >> 3;
-  const int mt = xcd * chunk + local / per, yz = local % per;
-  if (mt >= mtiles) return;
-  const int z = yz / ntiles;
-  const int m0 = mt * BM, n0 = (yz - z * ntiles) * BN;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
-  const int fr = lane & 31, fg = lane >> 5;
+  const ConvTile tile = conv_tile(p);               // conv_tile.cuh: the XCD-aware walk of the one-dimensional grid
+  if (!tile.live) return;
+  const int z = tile.z(), m0 = tile.m0(), n0 = tile.n0(z), wm = tile.wm(), wn = tile.wn(), fr = tile.fr(), fg = tile.fg();
 
   f32x16 acc[2][2], lo[2][2];             // acc: the x0*y0 sums (`hi`), lo: the five small products
 #pragma unroll
@@ -234,25 +177,26 @@ __global__ __launch_bounds__(NT, 2) void conv_split_kernel(const SplitArgs s) {
       for (int e = 0; e < 16; ++e) acc[i][j][e] = lo[i][j][e] = 0.f;
 
   const int nk = (p.K + BK - 1) / BK;
-  const RowCtx actx = make_a_ctx(p, m0), bctx = make_b_ctx(p, z, n0);
+  const RowCtx actx = make_a_ctx(p, m0);
+  const WRowCtx bctx = make_b_ctx(p, z, n0);
   const bool relu_in = p.relu_in != 0;
   // one k-tile in flight in registers: the loads of tile kt+1 are issued before the MFMAs of tile kt and parked in the
   // (single) LDS stage after them, between two barriers -- the CU's second workgroup runs its MFMAs meanwhile; the tile
   // index is clamped, so the last iteration parks a copy nobody reads
   f32x4 ra[4]; u32x2 rb[4][3];
-  uint32_t ka = load_a<UT>(p, actx, z, 0, ra), kb = load_b(s, bctx, 0, rb);
+  uint32_t ka = load_a<UT, false>(p, actx, z, 0, ra), kb = load_b(s, bctx, 0, rb);
   store_a(smem, ra, ka, relu_in); store_b(smem + OPER, rb, kb);
   __syncthreads();
 #pragma unroll 1
   for (int kt = 0; kt < nk; ++kt) {
     const int k1 = min(kt + 1, nk - 1) * BK;
-    ka = load_a<UT>(p, actx, z, k1, ra); kb = load_b(s, bctx, k1, rb);
+    ka = load_a<UT, false>(p, actx, z, k1, ra); kb = load_b(s, bctx, k1, rb);
     mma_tile(smem, smem + OPER, wm, wn, fr, fg, acc, lo);
     __syncthreads();
     store_a(smem, ra, ka, relu_in); store_b(smem + OPER, rb, kb);
     __syncthreads();
   }
-  // epilogue: conv.hip's (C tile through LDS, 8 channels per thread, bias, ReLU, residual, or the fused RGB partial sums)
+  // the two accumulator sets are joined on their way into the C tile; from there on the epilogue is conv_tile.cuh's
   float* ct = reinterpret_cast<float*>(smem);
 #pragma unroll
   for (int i = 0; i < 2; ++i)
@@ -261,61 +205,7 @@ __global__ __launch_bounds__(NT, 2) void conv_split_kernel(const SplitArgs s) {
 #pragma unroll
       for (int e = 0; e < 16; ++e)
         ct[(wm + 32 * i + (e & 3) + 8 * (e >> 2) + 4 * fg) * BN + wn + 32 * j + fr] = acc[i][j][e] + lo[i][j][e];
-  __syncthreads();
-  const int cchunk = (threadIdx.x & 15) * 8;
-#pragma unroll 1
-  for (int pass = 0; pass < 8; ++pass) {
-    const int row = pass * 16 + (threadIdx.x >> 4);
-    const int m = m0 + row, n = n0 + cchunk;
-    float rgb[3] = {0.f, 0.f, 0.f};
-    size_t pix = 0;
-    if (m < p.M && n < p.Cout) {
-      f32x4 x0 = ld4(ct + row * BN + cchunk), x1 = ld4(ct + row * BN + cchunk + 4);
-      if (p.bias) { const f32x4 b0 = ld4(p.bias + n), b1 = ld4(p.bias + n + 4); x0 += b0; x1 += b1; }
-      if (p.relu_out) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { x0[i] = fmaxf(x0[i], 0.f); x1[i] = fmaxf(x1[i], 0.f); }
-      }
-      const int b = m / (p.GH * p.GW);
-      const int rem = m - b * (p.GH * p.GW);
-      const int y = rem / p.GW, x = rem - y * p.GW;
-      const int oy = y * p.out_mul + (z >> 1), ox = x * p.out_mul + (z & 1);   // z = 0 unless transposed
-      if (!p.rgb_part) {
-        const size_t oidx = (((size_t)b * p.OH + oy) * p.OW + ox) * p.Cout + n;
-        if (p.residual) {
-          f32x4 r0 = ld4(p.residual + oidx), r1 = ld4(p.residual + oidx + 4);
-          if (p.relu_res) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) { r0[i] = fmaxf(r0[i], 0.f); r1[i] = fmaxf(r1[i], 0.f); }
-          }
-          x0 += r0; x1 += r1;
-        }
-        float* o = p.out + oidx;
-        *reinterpret_cast<f32x4*>(o) = x0;
-        *reinterpret_cast<f32x4*>(o + 4) = x1;
-      } else {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          const f32x4 w0 = ld4(p.rgb_w + (size_t)c * p.Cout + n), w1 = ld4(p.rgb_w + (size_t)c * p.Cout + n + 4);
-          float r = 0.f;
-#pragma unroll
-          for (int i = 0; i < 4; ++i) { r = fmaf(x0[i], w0[i], r); r = fmaf(x1[i], w1[i], r); }
-          rgb[c] = r;
-        }
-        pix = ((size_t)b * p.OH + oy) * p.OW + ox;
-      }
-    }
-    if (p.rgb_part) {        // the 16 lanes of a row hold its 16 channel groups: fold them, lane 0 of the group stores
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        float r = rgb[c];
-        r += __shfl_xor(r, 1, 64); r += __shfl_xor(r, 2, 64); r += __shfl_xor(r, 4, 64); r += __shfl_xor(r, 8, 64);
-        rgb[c] = r;
-      }
-      if ((threadIdx.x & 15) == 0 && m < p.M)
-        *reinterpret_cast<f32x4*>(p.rgb_part + ((size_t)(n0 / BN) * ((size_t)p.B * p.OH * p.OW) + pix) * 4) = f32x4{rgb[0], rgb[1], rgb[2], 0.f};
-    }
-  }
+  conv_epilogue(p, ct, z, m0, n0);
 }
 
 // w[n] -> three planes of bf16 bits (see cogv_conv_split_weights)

@@ -604,6 +604,9 @@ typedef struct cogv_conv_desc {
 } cogv_conv_desc;
 #define COGV_CONV_FP32 0
 #define COGV_CONV_BF16X3 1
+/* COGV_ERR_ARG before any launch also for: odd IH / IW with COGV_CONV_4X4_S2, Cin % 4, Cout % 8, and more pixels than the
+ * kernels index in int (B * GH * GW > 2^31 - 1 - 128, GH x GW the iteration grid: the input's for 1x1 / 3x3 / transposed, half
+ * of it for 4x4 stride 2); COGV_ERR_UNSUPPORTED for an unknown kind.  The geometry is the weight gradient's (below). */
 int cogv_conv2d_nhwc_f32(const cogv_conv_desc* d, void* stream);
 /* The three bf16 limb planes of a packed fp32 weight tensor of n elements (any of the layouts above; n % 4 == 0), for
  * COGV_CONV_BF16X3 -- the fast mode of the F.conv2d / F.conv_transpose2d calls cogv_conv2d_nhwc_f32 replaces

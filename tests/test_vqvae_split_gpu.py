@@ -49,11 +49,12 @@ def test_epilogues_against_fp64(kind, B, H, W, Cin, Cout, epilogue):
     _check_cell(c, S.device_cell(c), f"{kind} {(B, H, W, Cin, Cout)} {epilogue}", S.reference(c, epilogue), epilogue=epilogue)
 
 
-def test_fused_rgb_partials_against_fp64():
+@pytest.mark.parametrize("cell", S.RGB_CELLS, ids=lambda cell: "-".join(map(str, cell)))
+def test_fused_rgb_partials_against_fp64(cell):
     """The last decoder layer's form: ReLU(convT) projected to RGB in the epilogue, cogv_rgb_finalize_f32 with scale and shift."""
-    c = S.make_cell(*S.RGB_CELL)
+    c = S.make_cell(*cell)
     scale, shift = (0.30379, 0.32279, 0.32800), (0.79093, 0.76271, 0.75340)
-    _check_cell(c, S.device_cell(c), f"rgb {S.RGB_CELL}", S.reference_rgb(c, scale, shift), rgb=(scale, shift))
+    _check_cell(c, S.device_cell(c), f"rgb {cell}", S.reference_rgb(c, scale, shift), rgb=(scale, shift))
 
 
 @pytest.mark.parametrize("scale", [1e30, 1e-30])

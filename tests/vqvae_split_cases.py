@@ -17,6 +17,9 @@ CELLS = [
 EPILOGUE_CELLS = [(CONV, 2, 6, 10, 8, 40), (CONVT, 2, 5, 7, 8, 8)]
 EPILOGUES = ["relu", "relu_in", "residual", "relu_residual", "no_bias"]
 RGB_CELL = (CONVT, 1, 4, 6, 8, 128)
+# the second fused-RGB cell: 162 pixels per parity = two pixel tiles, the last one partial (the epilogue's m < M guard), and two
+# channel tiles (the partial sums' tile index n0 / 128 = 1)
+RGB_CELLS = [RGB_CELL, (CONVT, 2, 9, 9, 8, 256)]
 RANGE_CELL = (CONV, 2, 6, 10, 8, 40)
 # Relative Frobenius error against fp64 a cell must stay under.  One missing small product (x2y0, x1y1 or x0y2), a
 # two-limb kernel or a limb read from the wrong plane reads 2.4e-6 or more; a correct kernel emulated on the CPU at most 1.3e-7.
