@@ -72,6 +72,10 @@ class W8Weight(C.Structure):
     _fields_ = [("q", C.c_void_p), ("ldq", C.c_int), ("scale", C.c_void_p)]
 
 
+class W4Weight(C.Structure):
+    _fields_ = [("q", C.c_void_p), ("ldq", C.c_int), ("scale", C.c_void_p), ("lds", C.c_int)]
+
+
 class AttnDecodeDesc(C.Structure):
     _fields_ = [
         ("dtype", C.c_int), ("B", C.c_int), ("H", C.c_int), ("capacity", C.c_int), ("head_dim", C.c_int),
@@ -215,6 +219,11 @@ SIGNATURES = {
     "cogv_gemv_ln_w8": (_i, [C.POINTER(GemmDesc), C.POINTER(LnPrologue), C.POINTER(W8Weight), _vp]),
     "cogv_gemv_attn_w8": (_i, [C.POINTER(GemmDesc), C.POINTER(W8Weight), _vp, _i, _i, _vp]),
     "cogv_gemv_plan": (_i, [_i, C.POINTER(GemmDesc), C.POINTER(W8Weight), _i, C.POINTER(C.c_int)]),
+    "cogv_quantize_rows_mxfp4": (_i, [_i, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
+    "cogv_gemm_w4": (_i, [C.POINTER(GemmDesc), C.POINTER(W4Weight), _vp]),
+    "cogv_gemv_ln_w4": (_i, [C.POINTER(GemmDesc), C.POINTER(LnPrologue), C.POINTER(W4Weight), _vp]),
+    "cogv_gemv_attn_w4": (_i, [C.POINTER(GemmDesc), C.POINTER(W4Weight), _vp, _i, _i, _vp]),
+    "cogv_gemv_w4_plan": (_i, [_i, C.POINTER(GemmDesc), C.POINTER(W4Weight), _i, C.POINTER(C.c_int)]),
     "cogv_gemm_rows": (_i, [C.POINTER(GemmDesc), _vp]),
     "cogv_gemm_rows_plan": (_i, [C.POINTER(GemmDesc), C.POINTER(C.c_int)]),
     "cogv_kv_quantize_e4m3": (_i, [_i, _vp, _i64, _i64, _i, _i, _i, _vp, _i64, _vp, _i64, _i, _i, _vp]),
@@ -323,6 +332,19 @@ def gemv_plan(kind, dtype, M, N, K, w8=False, nsplit=1, ldb=None):
         w.q, w.ldq, w.scale = d.B, d.ldb, 0x4000
     out = (C.c_int * GEMV_PLAN_INTS)(*([-1] * GEMV_PLAN_INTS))
     rc = lib().cogv_gemv_plan(kind, C.byref(d), C.byref(w) if w8 else None, nsplit, out)
+    return rc, list(out)
+
+
+def gemv_w4_plan(kind, dtype, M, N, K, nsplit=1, ldq=None, lds=None):
+    """cogv_gemv_w4_plan for a contiguous product of `kind` on an MXFP4 weight: (error code, the 11 integers of gemv_plan).  Host
+    only.  ldq / lds: bytes between the rows of the codes (default K / 2) and of the block scales (default K / 32)."""
+    d = GemmDesc()
+    d.dtype, d.M, d.N, d.K, d.lda, d.ldb, d.ldc, d.splitk = dtype, M, N, K, K, K, N, 1
+    d.A, d.B, d.C = 0x1000, 0x2000, 0x3000
+    w = W4Weight()
+    w.q, w.ldq, w.scale, w.lds = 0x2000, K // 2 if ldq is None else ldq, 0x4000, K // 32 if lds is None else lds
+    out = (C.c_int * GEMV_PLAN_INTS)(*([-1] * GEMV_PLAN_INTS))
+    rc = lib().cogv_gemv_w4_plan(kind, C.byref(d), C.byref(w), nsplit, out)
     return rc, list(out)
 
 

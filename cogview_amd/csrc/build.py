@@ -46,6 +46,8 @@ EXTRA_UNITS = [("gemm.hip", f"gemm_w4_{k}.o", [f"-DCOGV_W4_TU={k}"]) for k in ra
 EXTRA_UNITS += [("gemv.hip", f"gemv_{k}.o", [f"-DCOGV_GEMV_TU={k}"]) for k in range(2)]
 # the same kernels on 8-bit (E4M3) weights: units of their own, so that the 16-bit units compile what they always did
 EXTRA_UNITS += [("gemv.hip", f"gemv_w8_{k}.o", [f"-DCOGV_GEMV_TU={k}", "-DCOGV_GEMV_W8=1"]) for k in range(2)]
+# and on 4-bit (MXFP4) weights
+EXTRA_UNITS += [("gemv.hip", f"gemv_w4_{k}.o", [f"-DCOGV_GEMV_TU={k}", "-DCOGV_GEMV_W4=1"]) for k in range(2)]
 # the wide products of the decode step (up to 64 rows), one unit per dtype (gemv_wide.hip holds only the entry points without the macro)
 EXTRA_UNITS += [("gemv_wide.hip", f"gemv_wide_{k}.o", [f"-DCOGV_GEMV_WIDE_TU={k}"]) for k in range(2)]
 

@@ -186,6 +186,8 @@ extern "C" __attribute__((visibility("hidden"))) int cogv_gemv2_run_0(int kind, 
 extern "C" __attribute__((visibility("hidden"))) int cogv_gemv2_run_1(int kind, const GvPlan* plan, const GvCall* call);
 extern "C" __attribute__((visibility("hidden"))) int cogv_gemv2_w8_run_0(int kind, const GvPlan* plan, const GvCall* call);
 extern "C" __attribute__((visibility("hidden"))) int cogv_gemv2_w8_run_1(int kind, const GvPlan* plan, const GvCall* call);
+extern "C" __attribute__((visibility("hidden"))) int cogv_gemv2_w4_run_0(int kind, const GvPlan* plan, const GvCall* call);
+extern "C" __attribute__((visibility("hidden"))) int cogv_gemv2_w4_run_1(int kind, const GvPlan* plan, const GvCall* call);
 
 template <typename T>
 void gemv1_launch(int kind, const GvPlan& pl, const GvCall& c) {
@@ -216,10 +218,11 @@ void gemv1_launch(int kind, const GvPlan& pl, const GvCall& c) {
 // the launch of a planned product.  (A second-generation launcher answers COGV_ERR_UNSUPPORTED only when the runtime refuses the
 // two-halves kernel its LDS: the first generation takes the product then, where there is one.)
 int gemv_launch(int kind, int fmt, int dtype, GvPlan pl, const GvCall& c) {
-  static int (*const RUN[2][2])(int, const GvPlan*, const GvCall*) = {{cogv_gemv2_run_0, cogv_gemv2_run_1}, {cogv_gemv2_w8_run_0, cogv_gemv2_w8_run_1}};
+  static int (*const RUN[3][2])(int, const GvPlan*, const GvCall*) = {{cogv_gemv2_run_0, cogv_gemv2_run_1}, {cogv_gemv2_w8_run_0, cogv_gemv2_w8_run_1},
+                                                                      {cogv_gemv2_w4_run_0, cogv_gemv2_w4_run_1}};
   if (pl.generation == 2) {
     const int rc = RUN[fmt][dtype == COGV_F16](kind, &pl, &c);
-    if (rc != COGV_ERR_UNSUPPORTED || fmt == GV_W8) return rc != COGV_OK ? rc : cogv_check_launch();
+    if (rc != COGV_ERR_UNSUPPORTED || fmt != GV_W16) return rc != COGV_OK ? rc : cogv_check_launch();
     const GemmArgs& a = *reinterpret_cast<const GemmArgs*>(c.args);          // (GemvLnArgs begins with its GemmArgs)
     pl = gv_plan_gen1(kind, pl.mt, a.N, a.K);
   }
@@ -360,6 +363,22 @@ static int build_w8_args(const cogv_gemm_desc* d, const cogv_w8_weight* w, int a
   return COGV_OK;
 }
 
+// the same with the 4-bit operand (MXFP4 codes and block scales: B / ldb / bscale / ldbs of the argument block)
+static int build_w4_args(const cogv_gemm_desc* d, const cogv_w4_weight* w, int allowed, bool has_a, GemmArgs& a) {
+  if (!d || !w || !w->q || !w->scale) return COGV_ERR_ARG;
+  if (d->M > GEMV_MAX_M || (d->N & 7) || (d->K & 511) || d->trans_a || d->trans_b || (d->flags & ~allowed) || d->out_f32 || d->splitk > 1)
+    return COGV_ERR_UNSUPPORTED;
+  if ((w->ldq & 15) || ((uintptr_t)w->q & 15) || w->lds < d->K / 32) return COGV_ERR_ARG;
+  cogv_gemm_desc dd = *d;
+  dd.B = w->q; dd.ldb = w->ldq;
+  if (!has_a) { dd.A = dd.B; dd.lda = dd.K; }          // (no A operand: keep build_gemm_args' pointer checks happy)
+  const int rc = build_gemm_args(&dd, a);
+  if (rc != COGV_OK) return rc;
+  a.bscale = reinterpret_cast<const uint8_t*>(w->scale);
+  a.ldbs = w->lds;
+  return COGV_OK;
+}
+
 static int gemv_ln_args(const cogv_ln_prologue* ln, GemvLnArgs& a) {
   if (!ln->z || !ln->gamma || !ln->beta) return COGV_ERR_ARG;
   if (ln->gamma_post && (!ln->beta_post || !ln->residual)) return COGV_ERR_ARG;
@@ -371,11 +390,16 @@ static int gemv_ln_args(const cogv_ln_prologue* ln, GemvLnArgs& a) {
 }
 
 // Descriptor of a product of `kind` (w: its 8-bit weight, or NULL) -> argument block and launch plan, or the entry point's
-// error: the front of cogv_gemv_ln, cogv_gemv_attn, the three _w8 calls and cogv_gemv_plan (cogv_gemm's is gemm_front).
+// error: the front of cogv_gemv_ln, cogv_gemv_attn, the three _w8 and the three _w4 calls and the two plan queries (cogv_gemm's
+// is gemm_front).  w4: the 4-bit weight (w is NULL then).
 static int gemv_front(int kind, const cogv_gemm_desc* d, const cogv_w8_weight* w, int nsplit, GemmArgs& a, GvPlan& pl,
-                      const cogv_ln_prologue* ln = nullptr, GemvLnArgs* la = nullptr) {
+                      const cogv_ln_prologue* ln = nullptr, GemvLnArgs* la = nullptr, const cogv_w4_weight* w4 = nullptr) {
   int rc;
-  if (w) {
+  if (w4) {
+    rc = build_w4_args(d, w4, COGV_EPI_BIAS | COGV_EPI_ABSMAX | (kind == GV_ATTN ? 0 : COGV_EPI_GELU), kind == GV_PLAIN, a);
+    if (rc == COGV_OK && kind != GV_ATTN && d->aux) rc = COGV_ERR_UNSUPPORTED;
+  }
+  else if (w) {
     rc = build_w8_args(d, w, COGV_EPI_BIAS | COGV_EPI_ABSMAX | (kind == GV_ATTN ? 0 : COGV_EPI_GELU), kind == GV_PLAIN, a);
     if (rc == COGV_OK && kind != GV_ATTN && d->aux) rc = COGV_ERR_UNSUPPORTED;
   }
@@ -390,39 +414,46 @@ static int gemv_front(int kind, const cogv_gemm_desc* d, const cogv_w8_weight* w
   a.splitk = 1;
   if (!gv_shape_taken(kind, a.M, a.N, a.K)) return COGV_ERR_UNSUPPORTED;
   if (ln && (rc = gemv_ln_args(ln, *la)) != COGV_OK) return rc;             // (a bad prologue is reported before a class's refusal)
-  return gv_plan(kind, w ? GV_W8 : GV_W16, a.M, a.N, a.K, a.ldb, nsplit, pl) ? COGV_OK : COGV_ERR_UNSUPPORTED;
+  return gv_plan(kind, w4 ? GV_W4 : w ? GV_W8 : GV_W16, a.M, a.N, a.K, a.ldb, nsplit, pl) ? COGV_OK : COGV_ERR_UNSUPPORTED;
 }
 
 // y = epilogue(LN_pre([res + LN_post(z)]) . B^T): the decode step's GEMV with its LayerNorms as prologue
-static int gemv_ln(const cogv_gemm_desc* d, const cogv_ln_prologue* ln, const cogv_w8_weight* w, void* stream) {
+static int gemv_ln(const cogv_gemm_desc* d, const cogv_ln_prologue* ln, const cogv_w8_weight* w, void* stream, const cogv_w4_weight* w4 = nullptr) {
   if (!ln) return COGV_ERR_ARG;
   GemvLnArgs a;
   GvPlan pl;
-  const int rc = gemv_front(GV_LN, d, w, 0, a.g, pl, ln, &a);
+  const int rc = gemv_front(GV_LN, d, w, 0, a.g, pl, ln, &a, w4);
   if (rc != COGV_OK) return rc;
-  return gemv_launch(GV_LN, w ? GV_W8 : GV_W16, d->dtype, pl, GvCall{&a, nullptr, 0, 0, ln->stream_f32 != 0, stream});
+  return gemv_launch(GV_LN, w4 ? GV_W4 : w ? GV_W8 : GV_W16, d->dtype, pl, GvCall{&a, nullptr, 0, 0, ln->stream_f32 != 0, stream});
 }
 extern "C" int cogv_gemv_ln(const cogv_gemm_desc* d, const cogv_ln_prologue* ln, void* stream) { return gemv_ln(d, ln, nullptr, stream); }
 extern "C" int cogv_gemv_ln_w8(const cogv_gemm_desc* d, const cogv_ln_prologue* ln, const cogv_w8_weight* w, void* stream) {
   return w ? gemv_ln(d, ln, w, stream) : COGV_ERR_ARG;
 }
+extern "C" int cogv_gemv_ln_w4(const cogv_gemm_desc* d, const cogv_ln_prologue* ln, const cogv_w4_weight* w, void* stream) {
+  return w ? gemv_ln(d, ln, nullptr, stream, w) : COGV_ERR_ARG;
+}
 
 // y = epilogue(att . B^T), att = the combination of cogv_attention_decode's split partials (skip_combine form)
-static int gemv_attn(const cogv_gemm_desc* d, const cogv_w8_weight* w, const void* partials, int heads, int capacity, void* stream) {
+static int gemv_attn(const cogv_gemm_desc* d, const cogv_w8_weight* w, const void* partials, int heads, int capacity, void* stream,
+                     const cogv_w4_weight* w4 = nullptr) {
   if (!partials || heads <= 0 || capacity <= 0 || capacity > 4096 || ((uintptr_t)partials & 15)) return COGV_ERR_ARG;
   const int nsplit = (capacity + 127) / 128;
   GemmArgs a;
   GvPlan pl;
-  const int rc = gemv_front(GV_ATTN, d, w, nsplit, a, pl);
+  const int rc = gemv_front(GV_ATTN, d, w, nsplit, a, pl, nullptr, nullptr, w4);
   if (rc != COGV_OK) return rc;
   if (a.K != heads * 64) return COGV_ERR_UNSUPPORTED;
-  return gemv_launch(GV_ATTN, w ? GV_W8 : GV_W16, d->dtype, pl, GvCall{&a, reinterpret_cast<const float*>(partials), heads, nsplit, 0, stream});
+  return gemv_launch(GV_ATTN, w4 ? GV_W4 : w ? GV_W8 : GV_W16, d->dtype, pl, GvCall{&a, reinterpret_cast<const float*>(partials), heads, nsplit, 0, stream});
 }
 extern "C" int cogv_gemv_attn(const cogv_gemm_desc* d, const void* partials, int heads, int capacity, void* stream) {
   return gemv_attn(d, nullptr, partials, heads, capacity, stream);
 }
 extern "C" int cogv_gemv_attn_w8(const cogv_gemm_desc* d, const cogv_w8_weight* w, const void* partials, int heads, int capacity, void* stream) {
   return w ? gemv_attn(d, w, partials, heads, capacity, stream) : COGV_ERR_ARG;
+}
+extern "C" int cogv_gemv_attn_w4(const cogv_gemm_desc* d, const cogv_w4_weight* w, const void* partials, int heads, int capacity, void* stream) {
+  return w ? gemv_attn(d, nullptr, partials, heads, capacity, stream, w) : COGV_ERR_ARG;
 }
 
 extern "C" int cogv_gemm_w8(const cogv_gemm_desc* d, const cogv_w8_weight* w, void* stream) {
@@ -433,16 +464,30 @@ extern "C" int cogv_gemm_w8(const cogv_gemm_desc* d, const cogv_w8_weight* w, vo
   return rc != COGV_OK ? rc : gemv_launch(GV_PLAIN, GV_W8, d->dtype, pl, GvCall{&a, nullptr, 0, 0, 0, stream});
 }
 
+extern "C" int cogv_gemm_w4(const cogv_gemm_desc* d, const cogv_w4_weight* w, void* stream) {
+  if (!w) return COGV_ERR_ARG;
+  GemmArgs a;
+  GvPlan pl;
+  const int rc = gemv_front(GV_PLAIN, d, nullptr, 0, a, pl, nullptr, nullptr, w);
+  return rc != COGV_OK ? rc : gemv_launch(GV_PLAIN, GV_W4, d->dtype, pl, GvCall{&a, nullptr, 0, 0, 0, stream});
+}
+
 // host-only: the plan the entry points above (and cogv_gemm's skinny case) would launch with
-extern "C" int cogv_gemv_plan(int kind, const cogv_gemm_desc* d, const cogv_w8_weight* w, int nsplit, int out[COGV_GEMV_PLAN_INTS]) {
+static int gemv_plan_query(int kind, const cogv_gemm_desc* d, const cogv_w8_weight* w, const cogv_w4_weight* w4, int nsplit, int* out) {
   if (!out || kind < COGV_GEMV_PLAIN || kind > COGV_GEMV_LN || (kind == COGV_GEMV_ATTN && nsplit < 1)) return COGV_ERR_ARG;
   GemmArgs a;
   GvPlan pl;
-  const int rc = gemv_front(1 << kind, d, w, nsplit, a, pl);
+  const int rc = gemv_front(1 << kind, d, w, nsplit, a, pl, nullptr, nullptr, w4);
   if (rc != COGV_OK) return rc;
   const int v[COGV_GEMV_PLAN_INTS] = {pl.generation, pl.form, pl.p0, pl.p1, pl.guard, pl.mt, pl.tw, pl.k2, pl.threads, pl.grid, pl.lds};
   for (int i = 0; i < COGV_GEMV_PLAN_INTS; ++i) out[i] = v[i];
   return COGV_OK;
+}
+extern "C" int cogv_gemv_plan(int kind, const cogv_gemm_desc* d, const cogv_w8_weight* w, int nsplit, int out[COGV_GEMV_PLAN_INTS]) {
+  return gemv_plan_query(kind, d, w, nullptr, nsplit, out);
+}
+extern "C" int cogv_gemv_w4_plan(int kind, const cogv_gemm_desc* d, const cogv_w4_weight* w, int nsplit, int out[COGV_GEMV_PLAN_INTS]) {
+  return w ? gemv_plan_query(kind, d, nullptr, w, nsplit, out) : COGV_ERR_ARG;
 }
 
 // Several GEMMs of the same dtype and layout in one persistent launch of the generation-4 kernel (see GroupArgs).

@@ -27,10 +27,15 @@ struct GemmArgs {
   union {               // (one slot: the skinny-M products never split K, so the layout of the block stays what it was)
     float* ws;            // split-K slabs [S][M][N] fp32
     const float* wscale;  // 8-bit weight operand (gemv.hip, W8): B is uint8 E4M3 [N][ldb], wscale [N] its row scales
+    const uint8_t* bscale;  // 4-bit weight operand (gemv.hip, W4): B is uint8 MXFP4 [N][ldb] (two codes per byte), bscale [N][ldbs] its E8M0 block scales
   };
   int splitk;
   int ktiles_per_split;
-  int tiles_m, tiles_n;
+  union {               // (one slot again: the tile kernels have no block scales, the skinny-M products no tiles)
+    int tiles_m;
+    int ldbs;             // bytes between the rows of bscale
+  };
+  int tiles_n;
 };
 
 // ---- fused epilogue on 8 consecutive columns of one row (fp32 in registers)

@@ -36,11 +36,16 @@
 // on W8 gives a wave twice the columns (8-byte slots: a lane keeps its 8 contraction elements), FormM on W8 gives a 16-column
 // tile half the waves (a 16-byte load is two MFMA fragments).  The classes of both formats: gemv_plan.h.
 //
-// Compiled as two translation units (-DCOGV_GEMV_TU=0: bf16, 1: fp16; build.py) for the 16-bit operand and two more with
-// -DCOGV_GEMV_W8 for the 8-bit operand; without the macro this file is empty.  The merge of the forms left the device code of
-// all four units what it was (tools/device_code_diff.py, profiles/r16_gemv_forms_parent_vs_head.log).
+// A third operand, W4 (OCP MXFP4 blocks, cogv_quantize_rows_mxfp4; the format: mxfp4_stream.cuh), halves the bytes again: see
+// the struct below for its slot and fragment mapping.
+//
+// Compiled as two translation units (-DCOGV_GEMV_TU=0: bf16, 1: fp16; build.py) for the 16-bit operand, two more with
+// -DCOGV_GEMV_W8 for the 8-bit operand and two with -DCOGV_GEMV_W4 for the 4-bit one; without the macro this file is empty.  The
+// merge of the forms left the device code of the first four units what it was (tools/device_code_diff.py,
+// profiles/r16_gemv_forms_parent_vs_head.log), and so did the 4-bit operand (profiles/r21_gemv_w4_parent_vs_head.log).
 #include "gemm_shared.cuh"
 #include "gemv_plan.h"
+#include "mxfp4_stream.cuh"
 
 #include <cstdlib>
 #include <type_traits>
@@ -84,7 +89,8 @@ struct W16 {
   typedef T_ T;
   typedef T_ Elem;
   typedef u32x4 Slot;
-  static constexpr int KL = 32, FR = 1;
+  static constexpr int KL = 32, FR = 1, EPL = 8, PK = 1;
+  template <int L> struct MRegs { u32x4 w[L]; };
   struct Scale {};
   static __device__ __forceinline__ Slot load(const Elem* q) { return ld_stream<u32x4>(q); }
   static __device__ __forceinline__ void unpack(const Slot& w, float* f) { unpack8<T>(w, f); }
@@ -115,7 +121,8 @@ struct W8 {
   typedef T_ T;
   typedef uint8_t Elem;
   typedef u32x2 Slot;
-  static constexpr int KL = 64, FR = 2;
+  static constexpr int KL = 64, FR = 2, EPL = 8, PK = 1;
+  template <int L> struct MRegs { u32x4 w[L]; };
   typedef Scale8 Scale;
   static __device__ __forceinline__ Slot load(const Elem* q) { return ld_stream<u32x2>(q); }
   static __device__ __forceinline__ void unpack(const Slot& w, float* f) { unpack8_e4m3(w[0], w[1], f); }
@@ -130,12 +137,55 @@ struct W8 {
   static __device__ __forceinline__ float mul(float x, const Factors& f, int i) { return x * f.s[i]; }      // the row scale, once, in front of the shared epilogue
 };
 
+// 4-bit weights (OCP MXFP4: mxfp4_stream.cuh): B is uint8 [N][ldb], two E2M1 codes per byte, p.bscale [N][ldbs] one E8M0 byte per
+// block of 32 contraction elements.  ONE 16-BYTE LOAD OF A LANE IS ONE BLOCK: 32 consecutive contraction elements of one weight row
+// and one scale byte, which is requested right behind it on the vector memory path (a per-lane address) and folded into the
+// conversion (v_cvt_scalef32_pk_*_fp4: two elements per instruction, what W8 pays) -- there is no per-column factor.
+//   FormV: a slot is the lane's block, EPL = 32 elements: a wave's load covers 2048 contraction elements of a column, and the x side
+//          reads the same 32 elements from LDS.  A column whose K is no multiple of 2048 ends inside a slot: the lanes past K
+//          re-read the row's last block (the same request as the lane that owns it: no byte of HBM more) against zeros for x.
+//   FormM: a load is FOUR fragments (KL = 128): lane l supplies row (l & 15), elements 32 (l >> 4) .. + 31 of the load's 128-element
+//          step, 8 to each v_mfma_f32_16x16x32, converted to T with the scale folded in (exact in bf16; in fp16 wherever code * 2^e
+//          is a multiple of 2^-24 below 65520); the x operand of each takes the same 8 elements of its row from LDS.
+// The alternative -- a 4-byte slot that keeps W8's 8-element mapping, a scale byte per slot -- asks FormV for four times the loads
+// and two registers per 8 elements where this one takes 5 per 32.
+template <typename T_>
+struct W4 {
+  typedef T_ T;
+  typedef uint8_t Elem;
+  struct Slot { u32x4 q; uint32_t s; };
+  static constexpr int KL = 128, FR = 4, EPL = 32, PK = 2;       // PK: contraction elements per Elem
+  template <int L> struct MRegs { u32x4 w[L]; uint32_t s[L]; };
+  struct Scale {};
+  // block kb (32 elements) of row n
+  static __device__ __forceinline__ uint32_t block_scale(const GemmArgs& p, int n, int kb) {
+    return *(const COGV_GLOBAL uint8_t*)(p.bscale + (size_t)n * p.ldbs + kb);
+  }
+  static __device__ __forceinline__ Slot load(const GemmArgs& p, int n, int kb) {
+    Slot w;
+    w.q = ld_stream<u32x4>(reinterpret_cast<const Elem*>(p.B) + (size_t)n * p.ldb + kb * 16);
+    w.s = block_scale(p, n, kb);
+    return w;
+  }
+  // elements 8 sub .. + 7 of a slot as floats
+  static __device__ __forceinline__ void unpack(const Slot& w, int sub, float* f) { unpack8_mxfp4(w.q[sub], mxfp4_scale_f32(w.s), f); }
+  static __device__ __forceinline__ typename HT<T>::v8 frag(const u32x4& w, uint32_t s, int f) {
+    return __builtin_bit_cast(typename HT<T>::v8, unpack8_mxfp4_to<T>(w[f], mxfp4_scale_f32(s)));
+  }
+  typedef Scale Factors;
+  static __device__ __forceinline__ Scale scale(const GemmArgs&, int, int) { return Scale{}; }
+  static __device__ __forceinline__ Factors factors(const Scale&) { return Factors{}; }
+  static __device__ __forceinline__ float mul(float x, const Factors&, int) { return x; }
+};
+
 // =====================================================================================================================
 // FormV: one row (MT = 1; the row-count template parameter is kept general).  A wave owns J whole columns.
 template <typename W, int J, int KCMAX, bool GUARD_, int MT, int NW_>
 struct FormV {
   typedef typename W::T T;
-  static constexpr int NW = NW_, COLS = NW_ * J, XPAD = 0, NS = KCMAX * J, XCHUNKS = KCMAX;
+  // CH contraction elements per slot of a wave, SC such slots per column (W16, W8: the 512-chunks themselves)
+  static constexpr int CH = 64 * W::EPL, SC = (KCMAX * 512 + CH - 1) / CH;
+  static constexpr int NW = NW_, COLS = NW_ * J, XPAD = 0, NS = SC * J, XCHUNKS = KCMAX;
   // NG groups of 8 columns, finished by lanes 0 .. GPW - 1 of every wave (J <= 8: GPW = 1, lane 0 of the first NG waves)
   static constexpr int NG = (NW_ * J) / 8, GPW = (NG + NW_ - 1) / NW_;
   static constexpr bool GUARD = GUARD_;
@@ -145,6 +195,7 @@ struct FormV {
   // past N (a wave at the ragged end of the matrix) re-read the last row; their results are never stored.
   template <int S0, int S1>
   static __device__ __forceinline__ void issue(Regs& r, const GemmArgs& p, int n0, int K, int wave, int lane) {
+    if constexpr (W::EPL == 8) {
     const typename W::Elem* B = reinterpret_cast<const typename W::Elem*>(p.B);
     const int nw = n0 + wave * J, kc = K >> 9;
 #pragma unroll
@@ -153,10 +204,55 @@ struct FormV {
       const int n = nw + j < p.N ? nw + j : p.N - 1;
       if (!GUARD || c < kc) r.w[s] = W::load(B + (size_t)n * p.ldb + c * 512 + lane * 8);
     }
+    } else {
+      // W4: the lane's block of slot-chunk c, or the row's last block where the column ends inside the chunk
+      const int nw = n0 + wave * J;
+#pragma unroll
+      for (int s = S0; s < S1; ++s) {
+        const int c = s / J, j = s % J;
+        const int n = nw + j < p.N ? nw + j : p.N - 1;
+        const int k = c * CH + lane * W::EPL;
+        if (!GUARD || c * CH < K) r.w[s] = W::load(p, n, (k < K ? k : K - W::EPL) >> 5);
+      }
+    }
   }
   // the group of 8 columns this lane finishes (lanes < GPW)
   static __device__ __forceinline__ int group(int wave, int lane) { return wave * GPW + (lane < GPW ? lane : 0); }
   static __device__ __forceinline__ u32x4 bias(const GemmArgs& p, int n0, int wave, int lane) { return gv2_bias<T>(p, n0 + group(wave, lane) * 8); }
+  // W4: the per-lane sums over the slot-chunks (a lane's 32 elements of each, ascending); lanes past the column's end add zeros
+  static __device__ __forceinline__ void sums4(const Regs& r, const T* xs, int XS, int K, int lane, float (&acc)[MT][J]) {
+#pragma unroll
+    for (int c = 0; c < SC; ++c) {
+      if (!GUARD || c * CH < K) {
+        const int k0 = c * CH + lane * W::EPL;
+        const bool ok = k0 < K;
+        const int k = ok ? k0 : K - W::EPL;
+        // (8 elements of x at a time against all J columns: 8 registers of x instead of 32; a column's chain stays ascending)
+#pragma unroll
+        for (int u = 0; u < W::EPL / 8; ++u) {
+          float x[MT][8];
+#pragma unroll
+          for (int m = 0; m < MT; ++m) {
+            unpack8<T>(*reinterpret_cast<const u32x4*>(xs + (size_t)m * XS + k + u * 8), x[m]);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) x[m][e] = ok ? x[m][e] : 0.f;
+          }
+#pragma unroll
+          for (int j = 0; j < J; ++j) {
+            float wf[8];
+            W::unpack(r.w[c * J + j], u, wf);
+#pragma unroll
+            for (int m = 0; m < MT; ++m) {
+              float t = acc[m][j];
+#pragma unroll
+              for (int e = 0; e < 8; ++e) t = fmaf(x[m][e], wf[e], t);
+              acc[m][j] = t;
+            }
+          }
+        }
+      }
+    }
+  }
   // acc[m][j] += sum over this lane's 8 elements of every chunk (ascending): x rows from LDS, 16 bytes per lane and row; then
   // one DPP wave sum per (row, column), LDS, and the finishing lane of group g runs the fused epilogue on columns n0 + 8g .. + 7.
   // The tail of these launches is a chain of dependent latencies on one lane, so the bias it needs is requested ahead.  A
@@ -174,6 +270,8 @@ struct FormV {
     for (int m = 0; m < MT; ++m)
 #pragma unroll
       for (int j = 0; j < J; ++j) acc[m][j] = 0.f;
+    if constexpr (W::EPL != 8) sums4(r, xs, XS, K, lane, acc);
+    else
 #pragma unroll
     for (int c = 0; c < KCMAX; ++c) {
       if (!GUARD || c < kc) {
@@ -244,17 +342,20 @@ struct FormM {
   static constexpr int KL = W::KL, FR = W::FR;
   static constexpr int NW = NWK * TW, COLS = 16 * TW, XPAD = 8, NS = LMAX, XCHUNKS = (LMAX * NWK * KL + 511) / 512;
   static constexpr bool GUARD = GUARD_;
-  struct Regs { u32x4 w[LMAX]; };
+  typedef typename W::template MRegs<LMAX> Regs;
   struct Shared { f32x4 red[NW][64]; float outp[TW][16][16]; };
   static __device__ __forceinline__ int kstep(int kw, int i) { return 2 * (kw + NWK * (i >> 1)) + (i & 1); }
   template <int S0, int S1>
   static __device__ __forceinline__ void issue(Regs& r, const GemmArgs& p, int n0, int K, int wave, int lane) {
     const int L = K / (KL * NWK), kw = wave % NWK, nt = n0 + (wave / NWK) * 16 + (lane & 15);
     const int n = nt < p.N ? nt : p.N - 1;
-    const typename W::Elem* row = reinterpret_cast<const typename W::Elem*>(p.B) + (size_t)n * p.ldb + (lane >> 4) * (KL / 4);
+    const typename W::Elem* row = reinterpret_cast<const typename W::Elem*>(p.B) + (size_t)n * p.ldb + (lane >> 4) * (KL / 4 / W::PK);
 #pragma unroll
     for (int i = S0; i < S1; ++i)
-      if (!GUARD || i < L) r.w[i] = gload16(row + KL * kstep(kw, i));     // (default policy: the non-temporal form measured 12-14 % SLOWER here, profiles/r05_decode_nt_ab.log)
+      if (!GUARD || i < L) {
+        r.w[i] = gload16(row + (KL / W::PK) * kstep(kw, i));     // (default policy: the non-temporal form measured 12-14 % SLOWER here, profiles/r05_decode_nt_ab.log)
+        if constexpr (W::PK == 2) r.s[i] = W::block_scale(p, n, (lane >> 4) + 4 * kstep(kw, i));      // W4: the load IS block 4 step + lane / 16 of its row
+      }
   }
   // lanes 0 .. 15 of a tile's first wave finish: lane t -> row t >> 1, columns (tile) + 8 (t & 1) ..
   static __device__ __forceinline__ int col(int n0, int wave, int lane) { return n0 + (wave / NWK) * 16 + (lane & 1) * 8; }
@@ -273,7 +374,10 @@ struct FormM {
 #pragma unroll
         for (int f = 0; f < FR; ++f) b[f] = *reinterpret_cast<const v8*>(xrow + KL * kstep(kw, i) + 8 * f);
 #pragma unroll
-        for (int f = 0; f < FR; ++f) acc = HT<T>::mfma16(W::frag(r.w[i], f), b[f], acc);
+        for (int f = 0; f < FR; ++f) {
+          if constexpr (W::PK == 2) acc = HT<T>::mfma16(W::frag(r.w[i], r.s[i], f), b[f], acc);
+          else acc = HT<T>::mfma16(W::frag(r.w[i], f), b[f], acc);
+        }
       }
     }
   }
@@ -699,7 +803,11 @@ using TT = std::conditional<COGV_GEMV_TU != 0, f16_t, bf16_t>::type;
 
 #define GV2_CAT2(a, b) a##b
 #define GV2_CAT(a, b) GV2_CAT2(a, b)
-#ifndef COGV_GEMV_W8
+#if defined(COGV_GEMV_W4)   // (units gemv_w4_<dtype>.o: the same kernels on the 4-bit operand)
+using WT = W4<TT>;
+#define GV2_CLASSES GV_CLASSES_4
+#define GV2_RUN GV2_CAT(cogv_gemv2_w4_run_, COGV_GEMV_TU)
+#elif !defined(COGV_GEMV_W8)
 using WT = W16<TT>;
 #define GV2_CLASSES GV_CLASSES_16
 #define GV2_RUN GV2_CAT(cogv_gemv2_run_, COGV_GEMV_TU)

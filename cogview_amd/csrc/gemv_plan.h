@@ -6,7 +6,7 @@
 #include <cstdlib>
 
 enum { GV_PLAIN = 1, GV_ATTN = 2, GV_LN = 4, GV_ALL = 7 };       // kind (bits: a class row names the kinds that take it)
-enum { GV_W16 = 0, GV_W8 = 1 };                                  // weight format: the dtype's 16 bits | E4M3 bytes + row scales
+enum { GV_W16 = 0, GV_W8 = 1, GV_W4 = 2 };                       // weight format: the dtype's 16 bits | E4M3 bytes + row scales | MXFP4 blocks
 enum { GV_FORM_V = 0, GV_FORM_M = 1 };                           // FormV: one row, vector ALU | FormM: 2 .. 8 rows, MFMA (either weight operand)
 
 // The classes.  A product of MT rows (1 | 2, 4, 8: the row count rounded up) takes the FIRST row of its format whose form
@@ -48,17 +48,42 @@ enum { GV_FORM_V = 0, GV_FORM_M = 1 };                           // FormV: one r
   X(B_M10240, M, 10240, 10240, 8,  20, false, GV_PLAIN,            0,       4 | 8, 1, 1)   \
   X(B_MG2,    M, 512,   2560,  2,  20, true,  GV_ALL,              0,       0,     2, 4)   \
   X(B_MG4,    M, 512,   5120,  4,  20, true,  GV_ALL,              0,       0,     2, 2)
+// The 4-bit rows (MXFP4: a lane's 16-byte load is one block of 32 contraction elements, gemv.hip W4).  V: KCMAX still counts the
+// 512-chunks of K (the x side's unit); a wave's slot covers 2048 elements of a column, so a column takes ceil(K / 2048) slots of
+// 16 + 1 bytes per lane and J is sized for 16-20 slots: 16-20 KB requested per wave (at K = 1024 and 2560 the lanes past the
+// column's end re-read its last block, so 8 and 10 KB of them are distinct -- twice the columns would need 160 registers of
+// slots; above K = 1024 the LayerNorm kind takes half the columns, 8 slots: its prologue lives next to them in the 168 registers
+// of three waves per SIMD).  M: a load is four fragments (KL = 128).  A tile of K = 2560 is 20 KB in all: one wave would hold it, but the
+// LayerNorm kind's prologue wants 4 or 8 waves, i.e. 8 one-wave tiles per workgroup at 4 and 8 rows -- 60 workgroups for the 4B
+// model's QKV product.  Measured in the captured 4B step: 2.38 / 3.08 / 4.36 ms at 2 / 4 / 8 rows with one wave per
+// tile against 2.33 / 2.65 / 4.12 with two (10 KB per wave, W8's workgroup shapes), so the rows up to K = 5120 take two waves per
+// tile and 2 or 4 tiles per LayerNorm workgroup; K = 10240 keeps 20 KB per wave on four.
+#define GV_CLASSES_4(X)                                                                    \
+  X(Q_V1024,  V, 1024,  1024,  16, 2,  false, GV_ALL,              0,       0,     1, 1)   \
+  X(Q_V2560,  V, 2560,  2560,  8,  5,  false, GV_PLAIN | GV_ATTN,  0,       0,     1, 1)   \
+  X(Q_VL2560, V, 2560,  2560,  4,  5,  false, GV_LN,               0,       0,     1, 1)   \
+  X(Q_V4096,  V, 4096,  4096,  8,  8,  false, GV_PLAIN,            0,       0,     1, 1)   \
+  X(Q_V10240, V, 10240, 10240, 4,  20, false, GV_PLAIN,            0,       0,     1, 1)   \
+  X(Q_VG8,    V, 512,   4096,  2,  8,  true,  GV_LN,               0,       0,     1, 1)   \
+  X(Q_VG20,   V, 512,   10240, 4,  20, true,  GV_PLAIN | GV_ATTN,  0,       0,     1, 1)   \
+  X(Q_M1024,  M, 1024,  1024,  2,  4,  false, GV_ALL,              0,       0,     2, 4)   \
+  X(Q_M2560,  M, 2560,  2560,  2,  10, false, GV_ALL,              0,       0,     2, 4)   \
+  X(Q_M4096,  M, 4096,  4096,  2,  16, false, GV_PLAIN,            0,       8,     1, 1)   \
+  X(Q_M10240, M, 10240, 10240, 4,  20, false, GV_PLAIN,            0,       4 | 8, 1, 1)   \
+  X(Q_MG2,    M, 512,   5120,  2,  20, true,  GV_ALL,              0,       0,     2, 4)
 
 #define GV_ENUM_ROW(NAME, ...) GVC_##NAME,
-enum GvClassId { GV_CLASSES_16(GV_ENUM_ROW) GV_CLASSES_8(GV_ENUM_ROW) GVC_COUNT };
+enum GvClassId { GV_CLASSES_16(GV_ENUM_ROW) GV_CLASSES_8(GV_ENUM_ROW) GV_CLASSES_4(GV_ENUM_ROW) GVC_COUNT };
 #undef GV_ENUM_ROW
 
 struct GvClass { int fmt, form, k_from, k_to, p0, p1, guard, kinds, stop, k2mts, lntw2, lntw48; };
 #define GV_ROW_16(NAME, FORM, KF, KT, P0, P1, G, KINDS, STOP, K2MTS, TW2, TW48) {GV_W16, GV_FORM_##FORM, KF, KT, P0, P1, G, KINDS, STOP, K2MTS, TW2, TW48},
 #define GV_ROW_8(NAME, FORM, KF, KT, P0, P1, G, KINDS, STOP, K2MTS, TW2, TW48) {GV_W8, GV_FORM_##FORM, KF, KT, P0, P1, G, KINDS, STOP, K2MTS, TW2, TW48},
-constexpr GvClass GV_CLASS_TABLE[GVC_COUNT] = {GV_CLASSES_16(GV_ROW_16) GV_CLASSES_8(GV_ROW_8)};
+#define GV_ROW_4(NAME, FORM, KF, KT, P0, P1, G, KINDS, STOP, K2MTS, TW2, TW48) {GV_W4, GV_FORM_##FORM, KF, KT, P0, P1, G, KINDS, STOP, K2MTS, TW2, TW48},
+constexpr GvClass GV_CLASS_TABLE[GVC_COUNT] = {GV_CLASSES_16(GV_ROW_16) GV_CLASSES_8(GV_ROW_8) GV_CLASSES_4(GV_ROW_4)};
 #undef GV_ROW_16
 #undef GV_ROW_8
+#undef GV_ROW_4
 
 // What a class means for a launch; gemv.hip asserts these against its forms' own constants (NW, COLS, XPAD).
 constexpr int gv_threads(int form, int p0, int tw) { return 64 * (form == GV_FORM_V ? 4 : p0 * tw); }
@@ -87,14 +112,15 @@ inline bool gv_gen2_enabled() {
 // false: the skinny-M kernels do not take the product at all (3, unsupported, from the entry points that have nothing else);
 // gv_shape_taken is the part of that answer no format or generation changes.
 // 16-bit weights always get a plan past the shape checks -- what the classes do not take is the first generation's; the 8-bit
-// format has no other kernel.  ldb: elements (bytes) between the weight's rows; nsplit: key splits the attention kind combines.
+// and the 4-bit format have no other kernel.  ldb: elements (bytes) between the weight's rows; nsplit: key splits the attention
+// kind combines.
 inline bool gv_shape_taken(int kind, int M, int N, int K) {
   return M >= 1 && M <= 8 && K >= 512 && (K & 511) == 0 && N >= 8 && (N & 7) == 0 && !(kind == GV_LN && K > GV_LN_MAX_K);
 }
 inline bool gv_plan(int kind, int fmt, int M, int N, int K, int ldb, int nsplit, GvPlan& pl) {
   if (!gv_shape_taken(kind, M, N, K)) return false;
   const int mt = gv_mt(M);
-  const bool gen2 = fmt == GV_W8 ? ldb >= K : gv_gen2_enabled();
+  const bool gen2 = fmt == GV_W8 ? ldb >= K : fmt == GV_W4 ? ldb >= K / 2 : gv_gen2_enabled();
   if (gen2 && !(kind == GV_ATTN && nsplit > GV_MAX_NSPLIT))
     for (int i = 0; i < GVC_COUNT; ++i) {
       const GvClass& c = GV_CLASS_TABLE[i];
@@ -108,7 +134,7 @@ inline bool gv_plan(int kind, int fmt, int M, int N, int K, int ldb, int nsplit,
       pl = GvPlan{2, c.form, c.p0, c.p1, c.guard, mt, tw, k2, gv_threads(c.form, c.p0, tw), (N + cols - 1) / cols, lds, i};
       return true;
     }
-  if (fmt == GV_W8) return false;
+  if (fmt != GV_W16) return false;
   pl = gv_plan_gen1(kind, mt, N, K);
   return true;
 }

@@ -1024,7 +1024,31 @@ class W8Weights:
         return [t for lw in self.layers for qs in lw for t in qs] + list(self.emb)
 
 
-def w8_decode_supported(tr, batch):
+class W4Weights(W8Weights):
+    """The 4-bit copies a decode step streams instead of the 16-bit weights (ops.quantize_rows_mxfp4; GraphDecoder(weights="mxfp4")):
+    W8Weights' interface, every pair (q [N, K / 2], scale [N, K / 32]) in OCP MXFP4."""
+
+    def __init__(self, tr, emb_weight):
+        quant = ops.quantize_rows_mxfp4
+        self.layers = [(quant(l.attention.query_key_value.weight), quant(l.attention.dense.weight),
+                        quant(l.mlp.dense_h_to_4h.weight), quant(l.mlp.dense_4h_to_h.weight)) for l in tr.layers]
+        self.emb = quant(emb_weight)
+        self.dtype = emb_weight.dtype
+
+
+def _quantized_products(wq):
+    """(gemv_ln, gemm, gemv_attn) of the format a W8Weights / W4Weights holds."""
+    if isinstance(wq, W4Weights):
+        return ops.gemv_ln_w4, ops.gemm_w4, ops.gemv_attn_w4
+    return ops.gemv_ln_w8, ops.gemm_w8, ops.gemv_attn_w8
+
+
+def w4_decode_supported(tr, batch):
+    """w8_decode_supported for the 4-bit weight stream: the same products, put to cogv_gemv_w4_plan."""
+    return w8_decode_supported(tr, batch, fmt="mxfp4")
+
+
+def w8_decode_supported(tr, batch, fmt="e4m3"):
     """The 8-bit decode step at this row count: every product it will issue -- the chain's (decode_chain) where
     decode_chain_supported, else the layer-by-layer step's (decode_layers_w8) -- is put to the library's own launch plan
     (cogv_gemv_plan: host only, nothing is touched).  The tied-logits product is asked with h columns: N decides a grid, never
@@ -1043,9 +1067,11 @@ def w8_decode_supported(tr, batch):
     else:
         products = [(plain, 3 * hp, h), (plain, h, hp), (plain, f, h), (plain, h, f), (plain, h, h)]
     dtype = _lib.BF16 if att.query_key_value.weight.dtype == torch.bfloat16 else _lib.F16
+    bits = 4 if fmt == "mxfp4" else 8
     for kind, n, k in products:
-        if _lib.gemv_plan(kind, dtype, batch, n, k, w8=True)[0] != _lib.OK:
-            return f"contraction length {k} at {batch} row(s) is outside the 8-bit kernels' classes ({('plain', 'combine-prologue', 'LayerNorm-prologue')[kind]} product, {n} columns)"
+        rc = _lib.gemv_w4_plan(kind, dtype, batch, n, k)[0] if bits == 4 else _lib.gemv_plan(kind, dtype, batch, n, k, w8=True)[0]
+        if rc != _lib.OK:
+            return f"contraction length {k} at {batch} row(s) is outside the {bits}-bit kernels' classes ({('plain', 'combine-prologue', 'LayerNorm-prologue')[kind]} product, {n} columns)"
     return None
 
 
@@ -1089,8 +1115,8 @@ def decode_chain(tr, h0, absmax0, slots, emb_weight, w8=None):
     layer.  Returns logits [b, m, V].  m = 1: one token per cache row.  m > 1 (a chunk step, b * m <= 8 rows): the same
     launches on b * m rows, rows b * m + j being the tokens of slots pos_index + j (ops.attention_decode_chunk in the attention
     slot); the Sandwich scale is the abs-max over all b * m rows, as in a multi-token model call.
-    w8 (W8Weights): launch for launch the same chain on the 8-bit copies of the weights, each product reading (q, scale) in
-    place of the 16-bit matrix (emb_weight is not read)."""
+    w8 (W8Weights, or W4Weights for the 4-bit format): launch for launch the same chain on the quantized copies of the weights, each
+    product reading (q, scale) in place of the 16-bit matrix (emb_weight is not read)."""
     b, s, h = h0.shape
     rows = b * s
     if w8 is None:
@@ -1101,10 +1127,10 @@ def decode_chain(tr, h0, absmax0, slots, emb_weight, w8=None):
         def gemv_attn(parts, npp, cap, w, bias):
             return ops.gemv_attn(parts, rows, npp, cap, w, bias=bias)
     else:
-        gemv_ln, gemm, logits_w, operands = ops.gemv_ln_w8, ops.gemm_w8, w8.emb, w8.layers
+        (gemv_ln, gemm, gemv_attn_q), logits_w, operands = _quantized_products(w8), w8.emb, w8.layers
 
         def gemv_attn(parts, npp, cap, w, bias):
-            return ops.gemv_attn_w8(parts, rows, npp, cap, w, w8.dtype, bias=bias)
+            return gemv_attn_q(parts, rows, npp, cap, w, w8.dtype, bias=bias)
     z, z_absmax, post, res = h0.view(rows, h), absmax0, None, None
     for layer, slot, (w_qkv, w_dense, w_h4h, w_4hh) in zip(tr.layers, slots, operands):
         att_m, mlp_m = layer.attention, layer.mlp
@@ -1139,8 +1165,8 @@ def decode_chain(tr, h0, absmax0, slots, emb_weight, w8=None):
 def decode_layers(tr, h0, absmax0, slots, emb_weight, w8=None, wide=False):
     """One decode step layer by layer: _layer_forward's inference chain on b * m <= 8 rows (every Sandwich-LN its own launch,
     decode attention with its combine, four plain skinny products per layer), the final LayerNorm and the tied-logits product.
-    h0 [b, m, h] -> logits [b, m, V]; m > 1: a chunk step, as in decode_chain.  w8 (W8Weights): the products read the 8-bit copies
-    (emb_weight is not read).  What a decoder runs above COGV_DECODE_CHAIN_MAX_ROWS for the 8-bit weights and for chunk steps, and
+    h0 [b, m, h] -> logits [b, m, V]; m > 1: a chunk step, as in decode_chain.  w8 (W8Weights | W4Weights): the products read the 8-bit
+    or 4-bit copies (emb_weight is not read).  What a decoder runs above COGV_DECODE_CHAIN_MAX_ROWS for the 8-bit weights and for chunk steps, and
     the comparison path of the chain.  wide=True (16-bit weights, up to 64 rows; decode_wide_supported): the five products go to
     ops.gemm_rows, the weight-streaming form above 8 rows; nothing else changes."""
     b, s, h = h0.shape
@@ -1152,7 +1178,7 @@ def decode_layers(tr, h0, absmax0, slots, emb_weight, w8=None, wide=False):
                     for l in tr.layers)
     else:
         assert not wide, "the wide step streams the 16-bit weights"
-        gemm, logits_w, operands = ops.gemm_w8, w8.emb, w8.layers
+        gemm, logits_w, operands = _quantized_products(w8)[1], w8.emb, w8.layers
     x, absmax_x = (h0 if h0.is_contiguous() else h0.contiguous()), absmax0
     for layer, slot, (w_qkv, w_dense, w_h4h, w_4hh) in zip(tr.layers, slots, operands):
         att_m, mlp_m = layer.attention, layer.mlp

@@ -16,7 +16,7 @@ from .. import ops
 from ..mpu.transformer import KV8Cache, StaticKVSlot
 
 
-WEIGHT_FORMATS = ("e4m3",)
+WEIGHT_FORMATS = ("e4m3", "mxfp4")
 KV_FORMATS = ("e4m3",)
 
 
@@ -68,13 +68,13 @@ def refuse_unsupported(weights=None, kv=None, ragged=False, args=None, model=Non
     dt = gpt.word_embeddings.weight.dtype
     # (a caller without the decoder's row count leaves weights= to the decoder, where the transformer is looked at anyway)
     if dt not in (torch.float16, torch.bfloat16) and (kv is not None or ragged or chunk or batch is not None):
-        raise NotImplementedError(f"a {dt} model{what}: the 8-bit formats, the per-row `first` slot and the chunk step are the fp16 / bf16 "
+        raise NotImplementedError(f"a {dt} model{what}: the 8-bit and 4-bit formats, the per-row `first` slot and the chunk step are the fp16 / bf16 "
                                   f"decode step's -- use {use}")
     if weights is not None and batch is not None:
         if gpt.word_embeddings.weight.shape[0] % 8:
             raise NotImplementedError(f"weights={weights!r}: a vocabulary of {gpt.word_embeddings.weight.shape[0]} rows (not a multiple of 8)")
         for rows in (batch, batch * chunk) if chunk else (batch,):
-            why = F_.w8_decode_supported(gpt.transformer, rows)
+            why = (F_.w4_decode_supported if weights == "mxfp4" else F_.w8_decode_supported)(gpt.transformer, rows)
             if why is not None:
                 raise NotImplementedError(f"weights={weights!r}: {why}")
 
@@ -90,6 +90,13 @@ class GraphDecoder:
         model's size in device memory (about 4 GB at 4B).  Logits differ from the 16-bit step's by the quantization of the
         weights.  One model-parallel partition, dense attention, fp16 / bf16, hidden sizes whose h and 4h the 8-bit kernels
         cover (the model family's: 1024 and 2560).  None (default): nothing is allocated, the step is what it was.
+        weights="mxfp4": the same step on 4-bit copies (OCP MXFP4: E2M1 codes with one E8M0 scale per 32 elements of a row,
+        ops.quantize_rows_mxfp4; held as self.w4) -- 0.53 bytes per weight, so the copies add about a quarter of the model's size.
+        The format's relative weight error is about four times row-scaled E4M3's (0.114 against 0.026 on Gaussian rows): the
+        logits differ from the 16-bit step's accordingly, and nothing is claimed about image quality.  Same limits as "e4m3",
+        composes with kv=, ragged= and chunk= the same way.  Measured on the captured 4B step: 2.07 / 2.33 / 2.64 /
+        4.09 ms at 1 / 2 / 4 / 8 rows against 2.32 / 2.50 / 2.82 / 4.41 on "e4m3" and 2.79 / 3.21 / 3.66 / 4.91 on 16-bit weights:
+        faster than the 8-bit step at every row count.
         kv="e4m3": the key/value caches hold OCP E4M3 bytes with one fp32 scale per (slot, head, K | V) (mpu.transformer.KV8Cache,
         ops.kv_quantize_e4m3 / ops.attention_decode_kv8) INSTEAD of the 16-bit caches: 0.53 of the bytes a step streams from them
         and of their resident memory.  The prefill stays 16-bit; its memories are quantized into the cache.  Logits differ from
@@ -109,12 +116,16 @@ class GraphDecoder:
         m = unwrap(model)
         self.gpt, tr = m, m.transformer
         assert capacity <= 4096
-        self.w8, self.kv, self.first = None, kv, None
+        self.w8, self.w4, self.kv, self.first = None, None, kv, None
         refuse_unsupported(weights, kv, ragged, model=m, batch=batch, chunk=chunk)
         self.chunk = int(chunk)
-        if weights is not None:
+        if weights == "mxfp4":
+            with torch.no_grad():
+                self.w4 = F_.W4Weights(tr, m.word_embeddings.weight)
+        elif weights is not None:
             with torch.no_grad():
                 self.w8 = F_.W8Weights(tr, m.word_embeddings.weight)
+        self.wq = self.w4 if self.w4 is not None else self.w8       # the quantized copies the step streams, if any
         p0 = tr.layers[0].attention.query_key_value.weight
         hp = tr.layers[0].attention.hidden_size_per_partition
         dev, dt = p0.device, p0.dtype
@@ -152,9 +163,9 @@ class GraphDecoder:
             if self.fused and F_.decode_chain_supported(tr, self.batch):
                 # five launches per layer: the LayerNorms ride as prologues of the GEMVs, the cache append inside the
                 # decode attention kernel (functional.decode_chain); w8: the same chain on the 8-bit copies of the weights
-                return F_.decode_chain(tr, h, h._cogv_absmax, self.slots, self.gpt.word_embeddings.weight, w8=self.w8)
-            if self.w8 is not None:
-                return F_.decode_layers_w8(tr, h, h._cogv_absmax, self.slots, self.w8)
+                return F_.decode_chain(tr, h, h._cogv_absmax, self.slots, self.gpt.word_embeddings.weight, w8=self.wq)
+            if self.wq is not None:
+                return F_.decode_layers_w8(tr, h, h._cogv_absmax, self.slots, self.wq)
             if F_.decode_wide_supported(tr, self.batch):
                 # 9 .. 64 rows on the 16-bit weights: layer by layer, the five products as weight streams (ops.gemm_rows)
                 return F_.decode_layers(tr, h, h._cogv_absmax, self.slots, self.gpt.word_embeddings.weight, wide=True)
@@ -171,8 +182,8 @@ class GraphDecoder:
         with ops.scalar_slab(self.slab):
             h = tr.embed(self.tok_chunk, self.pos_chunk, self.gpt.word_embeddings)
             if self.fused and F_.decode_chain_supported(tr, self.batch * self.chunk):
-                return F_.decode_chain(tr, h, h._cogv_absmax, self.slots, self.gpt.word_embeddings.weight, w8=self.w8)
-            return F_.decode_layers(tr, h, h._cogv_absmax, self.slots, self.gpt.word_embeddings.weight, w8=self.w8)
+                return F_.decode_chain(tr, h, h._cogv_absmax, self.slots, self.gpt.word_embeddings.weight, w8=self.wq)
+            return F_.decode_layers(tr, h, h._cogv_absmax, self.slots, self.gpt.word_embeddings.weight, w8=self.wq)
 
     def capture(self):
         """Warm up on a side stream (first-use allocations inside the library and the caching allocator), then capture."""

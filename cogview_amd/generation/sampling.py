@@ -531,7 +531,8 @@ def generate_on_device(model, seq, args, tokenizer=None, seed=0, capture=True, w
     Supported: dense attention (args.is_sparse == 0), one model-parallel partition, fp16 / bf16, <= 4096 positions.
     Returns (tokens [nb, len(seq)], scores [nb] fp32: the summed log-probabilities of the drawn ids), on seq's device.
     capture=False runs the same launches eagerly (the reference for the captured form).
-    weights="e4m3": the decode steps stream 8-bit copies of the weights (GraphDecoder's `weights`; the prefill stays 16-bit).
+    weights="e4m3" | "mxfp4": the decode steps stream 8-bit or 4-bit copies of the weights (GraphDecoder's `weights`; the prefill
+    stays 16-bit).
     kv="e4m3": the key/value caches hold 8-bit keys and values (GraphDecoder's `kv`); composes with `weights`."""
     tokenizer = tokenizer if tokenizer is not None else IdSpace()
     drv = _DeviceRun(model, args, seed, capture, weights, kv)

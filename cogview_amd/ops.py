@@ -844,6 +844,84 @@ def gemv_attn_w8(partials, batch, heads, capacity, qs, dtype, bias=None, absmax=
     return out
 
 
+# ------------------------------------------------------------------------------------------ 4-bit weights (decode step)
+_E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def quantize_rows_mxfp4(w):
+    """cogv_quantize_rows_mxfp4: w [N, K] fp16 / bf16 (K % 32 == 0, rows may be strided) -> (q [N, K / 2] uint8: two E2M1 codes per
+    byte, element 2i in the low nibble of byte i; scale [N, K / 32] uint8: one E8M0 exponent per block of 32, value 2^(scale - 127))
+    by the OCP MXFP4 rule of include/cogview_hip.h -- the weight operand of gemm_w4, gemv_ln_w4 and gemv_attn_w4.
+    dequantize_rows_mxfp4 reads the values back."""
+    _need_gpu(w)
+    assert w.dim() == 2 and w.stride(1) == 1 and w.shape[1] % 32 == 0
+    N, K = w.shape
+    q = torch.empty((N, K // 2), dtype=torch.uint8, device=w.device)
+    scale = torch.empty((N, K // 32), dtype=torch.uint8, device=w.device)
+    L.check(L.lib().cogv_quantize_rows_mxfp4(dt_code(w), _p(w), w.stride(0), N, K, _p(q), q.stride(0), _p(scale), scale.stride(0), _stream()),
+            "cogv_quantize_rows_mxfp4")
+    return q, scale
+
+
+def dequantize_rows_mxfp4(q, scale, dtype=torch.float32):
+    """The values an MXFP4 pair holds, in plain torch on any device: q [N, K / 2] uint8, scale [N, K / 32] uint8 -> [N, K] `dtype`
+    = sign * E2M1[code] * 2^(scale - 127).  Exact in fp32 (the default), fp64 and bf16; in fp16 wherever the value is a multiple
+    of 2^-24 below 65520."""
+    assert q.dtype == torch.uint8 and scale.dtype == torch.uint8 and q.dim() == 2 and q.shape[1] == scale.shape[1] * 16
+    nib = torch.stack((q & 15, q >> 4), dim=-1).reshape(q.shape[0], -1).long()
+    mag = torch.tensor(_E2M1, dtype=torch.float64, device=q.device)[nib & 7]
+    val = torch.where((nib & 8) != 0, -mag, mag)
+    return torch.ldexp(val, (scale.long() - 127).repeat_interleave(32, dim=1)).to(dtype)
+
+
+def _w4_call(x_dtype, M, K, qs, bias, gelu, absmax):
+    """(descriptor, operand, out) of a skinny-M product on the 4-bit weight qs = (q, scale)."""
+    q, scale = qs
+    _need_gpu(q, scale)
+    assert q.dim() == 2 and q.dtype == torch.uint8 and q.stride(1) == 1 and q.shape[1] * 2 == K, "q [N, K / 2] uint8 with K matching the input"
+    assert scale.dim() == 2 and scale.dtype == torch.uint8 and scale.stride(1) == 1 and scale.shape == (q.shape[0], K // 32)
+    N = q.shape[0]
+    assert bias is None or bias.dtype == x_dtype
+    out = torch.empty((M, N), dtype=x_dtype, device=q.device)
+    d = _skinny_desc(out, K, bias, gelu, absmax)
+    w = L.W4Weight()
+    w.q, w.ldq, w.scale, w.lds = q.data_ptr(), q.stride(0), scale.data_ptr(), scale.stride(0)
+    return d, w, out
+
+
+def gemm_w4(a, qs, bias=None, gelu=False, absmax=None):
+    """gemm's skinny case (a [M, K], M <= 8) on a 4-bit weight qs = (q [N, K / 2] uint8, scale [N, K / 32] uint8) from
+    quantize_rows_mxfp4 (cogv_gemm_w4): out [M, N] = epilogue(a . dequantize_rows_mxfp4(q, scale)^T + bias) in a's dtype.  Shapes
+    outside the kernels' classes raise: there is no other kernel behind this one."""
+    _need_gpu(a)
+    assert a.dim() == 2 and a.stride(1) == 1
+    M, K = a.shape
+    d, w, out = _w4_call(a.dtype, M, K, qs, bias, gelu, absmax)
+    d.A, d.lda = a.data_ptr(), a.stride(0)
+    L.check(L.lib().cogv_gemm_w4(C.byref(d), C.byref(w), _stream()), "cogv_gemm_w4")
+    return out
+
+
+def gemv_ln_w4(z, qs, bias, gamma, beta, eps, z_absmax=None, post=None, residual=None, want_t=False, gelu=False, absmax=None):
+    """gemv_ln on a 4-bit weight qs = (q, scale) (cogv_gemv_ln_w4); everything else as there.  The output takes gamma's dtype."""
+    _need_gpu(z, gamma)
+    assert z.dim() == 2 and z.is_contiguous()
+    M, K = z.shape
+    d, w, out = _w4_call(gamma.dtype, M, K, qs, bias, gelu, absmax)
+    ln, t = _ln_prologue(z, gamma, beta, eps, z_absmax, post, residual, want_t)
+    L.check(L.lib().cogv_gemv_ln_w4(C.byref(d), C.byref(ln), C.byref(w), _stream()), "cogv_gemv_ln_w4")
+    return out, t
+
+
+def gemv_attn_w4(partials, batch, heads, capacity, qs, dtype, bias=None, absmax=None):
+    """gemv_attn on a 4-bit weight qs = (q, scale) (cogv_gemv_attn_w4); `dtype`: the 16-bit type of the output (and bias)."""
+    _need_gpu(partials)
+    assert batch <= 8
+    d, w, out = _w4_call(dtype, batch, heads * 64, qs, bias, False, absmax)
+    L.check(L.lib().cogv_gemv_attn_w4(C.byref(d), C.byref(w), _p(partials), int(heads), int(capacity), _stream()), "cogv_gemv_attn_w4")
+    return out
+
+
 def _sparse_desc(d, kv_index, sparse, b, s_q):
     """Sparse training form in slot space: kv_index [b, s_q // w, n_slots] int32 (bit 31 = masked slot),
     sparse = (w, n_pivots, pivot_bias)."""

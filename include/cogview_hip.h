@@ -189,6 +189,43 @@ int cogv_gemv_attn_w8(const cogv_gemm_desc* d, const cogv_w8_weight* w, const vo
 #define COGV_GEMV_PLAN_INTS 11
 int cogv_gemv_plan(int kind, const cogv_gemm_desc* d, const cogv_w8_weight* w, int nsplit, int out[COGV_GEMV_PLAN_INTS]);
 
+/* ------------------------------------------------------------------ 4-bit weights for the decode step (OCP MXFP4: E2M1 codes, one E8M0 scale per 32)
+ * The second format of the decode step's weight stream (generation/sampling.py:139-148: one model call per generated token):
+ * 0.53 bytes per weight.  cogv_quantize_rows_mxfp4 stores a weight matrix W[N][K] (F16 | BF16, rows ldw elements apart) as
+ * q[N][K / 2] uint8 (rows ldq bytes apart; element 2i of a row is the low nibble of byte i, element 2i + 1 the high one; a nibble is
+ * the sign in bit 3 and a 3-bit E2M1 code of the magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6) and scale[N][K / 32] uint8 (rows lds
+ * bytes apart; an E8M0 exponent per block of 32 consecutive elements of a row, value 2^(scale - 127)).  Per block, amax = max |x|:
+ *     e = clamp(floor(log2(amax)) - 2, -126, 127), scale = e + 127 (127 for an all-zero block; never 0, never 255);
+ *     code = the E2M1 value nearest to float(x) / 2^e, ties to the even code, magnitudes above 6 saturate to 6
+ * -- integer arithmetic on the bit patterns, which a CPU reproduces exactly (ops.dequantize_rows_mxfp4 reads the result back).  A
+ * code of magnitude zero may carry either sign bit; NaN and infinity are outside the contract.  Deterministic, no atomics.
+ * K % 32 == 0, ldw % 8 == 0, ldq % 4 == 0, ldq >= K / 2, lds >= K / 32, w 16-byte and q 4-byte aligned, else 1; fp16 / bf16, else 3
+ * (the products below want ldq % 16 == 0 and q 16-byte aligned).  Replaces nothing in the reference (it keeps fp16 weights:
+ * mpu/layers.py:243,319); it prepares the operand of the three products below. */
+int cogv_quantize_rows_mxfp4(int dtype, const void* w, int ldw, int N, int K, void* q, int ldq, void* scale, int lds, void* stream);
+/* The 4-bit weight operand: it takes the place of d->B / d->ldb (ignored) in the three calls below.  C[m][n] =
+ * epilogue(sum_k X[m][k] * code(q[n][k]) * 2^(scale[n][k / 32] - 127)): the codes are converted with their block scale folded in
+ * (exact in fp32 and bf16; in fp16 wherever the value is a multiple of 2^-24 below 65520), the sum is the fp32 sum of the 16-bit
+ * kernels, then the same fused epilogue (bias, GeLU, rounding to T, abs-max). */
+typedef struct cogv_w4_weight {
+  const void* q; int ldq;      /* [N][ldq] uint8: two E2M1 codes per byte */
+  const void* scale; int lds;  /* [N][lds] uint8: E8M0 block scales */
+} cogv_w4_weight;
+/* cogv_gemm's skinny case (M <= 8: F.linear at mpu/layers.py:243,319 and the tied logits model/gpt2_modeling.py:117 inside a
+ * decode step) on a 4-bit weight; trans_a = trans_b = 0, flags BIAS | GELU | ABSMAX.  1 for a NULL or misaligned operand or lds <
+ * K / 32; 3 (unsupported) outside the kernels' classes -- there is no other kernel to fall back to: M > 8, N % 8, K % 512,
+ * K > 10240, K not in {4096, 10240} above 5120 with M >= 2, more than 4 rows in a guarded class above K = 3072. */
+int cogv_gemm_w4(const cogv_gemm_desc* d, const cogv_w4_weight* w, void* stream);
+/* cogv_gemv_ln (mpu/sparse_transformer.py:326-341 fused into the consuming product) on a 4-bit weight; same arguments, errors
+ * and limits (K <= 4096; more than 4 rows: K <= 3072). */
+int cogv_gemv_ln_w4(const cogv_gemm_desc* d, const cogv_ln_prologue* ln, const cogv_w4_weight* w, void* stream);
+/* cogv_gemv_attn (the attention-output projection mpu/sparse_transformer.py:163-166 with the split combine as prologue) on a
+ * 4-bit weight; bit-identical to the combine launch followed by cogv_gemm_w4. */
+int cogv_gemv_attn_w4(const cogv_gemm_desc* d, const cogv_w4_weight* w, const void* partials, int heads, int capacity, void* stream);
+/* cogv_gemv_plan for the three calls above (w != NULL, else 1): host only, the same 11 integers, the same errors as the launches.
+ * The J of a one-row class counts columns per wave as ever; a wave's slot covers 2048 contraction elements of a column here. */
+int cogv_gemv_w4_plan(int kind, const cogv_gemm_desc* d, const cogv_w4_weight* w, int nsplit, int out[COGV_GEMV_PLAN_INTS]);
+
 /* Wide decode step: F.linear at mpu/layers.py:243,319 and the tied logits model/gpt2_modeling.py:117 inside a decode step of up
  * to 64 rows (9 and more: the reference's --max-inference-batch-size defaults to 12), as a weight stream like cogv_gemm's skinny
  * case: every byte of B is requested once, by one workgroup.  C[M][N] = epilogue(A[M][K] . B[N][K]^T) on 16-bit weights with

@@ -1,7 +1,7 @@
 """Single-token decode latency of the 4B model with a 1024-position memory: the captured HIP-graph decode step
 (generation.GraphDecoder), eager K/V-cache memories (kv_cache=True) and the reference-style layer-input memories (every
-step re-projects K and V of the whole memory).  `--weights e4m3`: in the same run, the captured step on the 8-bit copies of the
-weights (GraphDecoder(weights="e4m3")) next to the 16-bit one -- ms per token of each, and the relative L2 / largest difference
+step re-projects K and V of the whole memory).  `--weights e4m3` | `--weights mxfp4`: in the same run, the captured step on the 8-bit
+or 4-bit copies of the weights (GraphDecoder(weights=...)) next to the 16-bit one -- ms per token of each, and the relative L2 / largest difference
 of their logits on the step that was timed.  `--kv e4m3`: the same comparison for the 8-bit key/value cache
 (GraphDecoder(kv="e4m3")) against the 16-bit cache, both on the weights `--weights` names (default: 16-bit).  MB_DECODE_SKIP_EAGER=1
 skips the eager timing of the first decoder.  MB_DECODE_BATCH=b: b rows (up to 64).  From 9 rows on, three captured steps are timed
@@ -148,8 +148,13 @@ if WFMT is not None:
         dec8.prefill(tokens[:, :pre], pos[:, :pre])
         dec8.capture()
         ms, last = _alternate(dec, dec8, "16-bit weights", f"{WFMT} weights")
-    w8_bytes = sum(t.numel() * t.element_size() for t in dec8.w8.tensors())
-    _report(ms, last, "16-bit weights", f"{WFMT} weights", f"{WFMT} vs 16-bit", f"; 8-bit copies {w8_bytes / 2 ** 30:.2f} GiB")
+    wq_bytes = sum(t.numel() * t.element_size() for t in dec8.wq.tensors())
+    pairs = [qs for lw in dec8.wq.layers for qs in lw] + [dec8.wq.emb]
+    w16_bytes = 2 * sum(q.numel() for q, _ in pairs) * (2 if WFMT == "mxfp4" else 1)       # the same matrices in 16 bits
+    mq, m16 = min(ms[f"{WFMT} weights"]), min(ms["16-bit weights"])
+    _report(ms, last, "16-bit weights", f"{WFMT} weights", f"{WFMT} vs 16-bit",
+            f"; {WFMT} copies {wq_bytes / 2 ** 30:.2f} GiB; weight bytes per second {w16_bytes / m16 / 1e9:.2f} TB/s (16-bit, {w16_bytes / 1e9:.2f} GB) / "
+            f"{wq_bytes / mq / 1e9:.2f} TB/s ({WFMT}, {wq_bytes / 1e9:.2f} GB)")
     if KVFMT is not None:
         del dec
         dec = dec8                                               # the 8-bit cache is compared on the same weights
