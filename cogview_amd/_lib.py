@@ -226,6 +226,10 @@ SIGNATURES = {
     "cogv_gemv_w4_plan": (_i, [_i, C.POINTER(GemmDesc), C.POINTER(W4Weight), _i, C.POINTER(C.c_int)]),
     "cogv_gemm_rows": (_i, [C.POINTER(GemmDesc), _vp]),
     "cogv_gemm_rows_plan": (_i, [C.POINTER(GemmDesc), C.POINTER(C.c_int)]),
+    "cogv_gemm_rows_w8": (_i, [C.POINTER(GemmDesc), C.POINTER(W8Weight), _vp]),
+    "cogv_gemm_rows_w4": (_i, [C.POINTER(GemmDesc), C.POINTER(W4Weight), _vp]),
+    "cogv_gemm_rows_w8_plan": (_i, [C.POINTER(GemmDesc), C.POINTER(W8Weight), C.POINTER(C.c_int)]),
+    "cogv_gemm_rows_w4_plan": (_i, [C.POINTER(GemmDesc), C.POINTER(W4Weight), C.POINTER(C.c_int)]),
     "cogv_kv_quantize_e4m3": (_i, [_i, _vp, _i64, _i64, _i, _i, _i, _vp, _i64, _vp, _i64, _i, _i, _vp]),
     "cogv_attention_decode_kv8": (_i, [C.POINTER(AttnDecodeKv8Desc), _vp]),
     "cogv_attention_decode_workspace_bytes": (_sz, [_i, _i, _i]),
@@ -362,6 +366,41 @@ def gemm_rows_plan(dtype, M, N, K, desc=None):
         d.A, d.B, d.C = 0x1000, 0x2000, 0x3000
     out = (C.c_int * GEMM_ROWS_PLAN_INTS)(*([-1] * GEMM_ROWS_PLAN_INTS))
     rc = lib().cogv_gemm_rows_plan(C.byref(d), out)
+    return rc, list(out)
+
+
+def _rows_q_desc(dtype, M, N, K, desc):
+    d = desc
+    if d is None:
+        d = GemmDesc()
+        d.dtype, d.M, d.N, d.K, d.lda, d.ldb, d.ldc, d.splitk = dtype, M, N, K, K, K, N, 1
+        d.A, d.B, d.C = 0x1000, 0x2000, 0x3000
+    return d
+
+
+def gemm_rows_w8_plan(dtype, M, N, K, ldq=None, desc=None, w=None):
+    """cogv_gemm_rows_w8_plan for a contiguous product on an E4M3 weight (or for the GemmDesc `desc` / W8Weight `w` as they
+    stand): (error code, the integers of GEMM_ROWS_PLAN_FIELDS; all -1 where the call is refused).  Host only.  ldq: bytes
+    between the rows of the codes (default K)."""
+    d = _rows_q_desc(dtype, M, N, K, desc)
+    if w is None:
+        w = W8Weight()
+        w.q, w.ldq, w.scale = 0x2000, d.K if ldq is None else ldq, 0x4000
+    out = (C.c_int * GEMM_ROWS_PLAN_INTS)(*([-1] * GEMM_ROWS_PLAN_INTS))
+    rc = lib().cogv_gemm_rows_w8_plan(C.byref(d), C.byref(w), out)
+    return rc, list(out)
+
+
+def gemm_rows_w4_plan(dtype, M, N, K, ldq=None, lds=None, desc=None, w=None):
+    """cogv_gemm_rows_w4_plan for a contiguous product on an MXFP4 weight (or for `desc` / the W4Weight `w` as they stand):
+    (error code, the integers of GEMM_ROWS_PLAN_FIELDS; all -1 where the call is refused).  Host only.  ldq / lds: bytes between
+    the rows of the codes (default K / 2) and of the block scales (default K / 32)."""
+    d = _rows_q_desc(dtype, M, N, K, desc)
+    if w is None:
+        w = W4Weight()
+        w.q, w.ldq, w.scale, w.lds = 0x2000, d.K // 2 if ldq is None else ldq, 0x4000, d.K // 32 if lds is None else lds
+    out = (C.c_int * GEMM_ROWS_PLAN_INTS)(*([-1] * GEMM_ROWS_PLAN_INTS))
+    rc = lib().cogv_gemm_rows_w4_plan(C.byref(d), C.byref(w), out)
     return rc, list(out)
 
 

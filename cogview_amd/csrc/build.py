@@ -50,6 +50,9 @@ EXTRA_UNITS += [("gemv.hip", f"gemv_w8_{k}.o", [f"-DCOGV_GEMV_TU={k}", "-DCOGV_G
 EXTRA_UNITS += [("gemv.hip", f"gemv_w4_{k}.o", [f"-DCOGV_GEMV_TU={k}", "-DCOGV_GEMV_W4=1"]) for k in range(2)]
 # the wide products of the decode step (up to 64 rows), one unit per dtype (gemv_wide.hip holds only the entry points without the macro)
 EXTRA_UNITS += [("gemv_wide.hip", f"gemv_wide_{k}.o", [f"-DCOGV_GEMV_WIDE_TU={k}"]) for k in range(2)]
+# the same kernel on the 8-bit (E4M3) and 4-bit (MXFP4) weights, units of their own like gemv_w8_* / gemv_w4_*
+EXTRA_UNITS += [("gemv_wide.hip", f"gemv_wide_w8_{k}.o", [f"-DCOGV_GEMV_WIDE_TU={k}", "-DCOGV_GEMV_WIDE_W8=1"]) for k in range(2)]
+EXTRA_UNITS += [("gemv_wide.hip", f"gemv_wide_w4_{k}.o", [f"-DCOGV_GEMV_WIDE_TU={k}", "-DCOGV_GEMV_WIDE_W4=1"]) for k in range(2)]
 
 
 def units():

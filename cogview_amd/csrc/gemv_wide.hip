@@ -1,4 +1,5 @@
-// Wide products of the decode step: 1 .. 64 rows on the 16-bit weights (cogv_gemm_rows).
+// Wide products of the decode step: 1 .. 64 rows on the 16-bit weights (cogv_gemm_rows) and on the quantized weight operands of
+// gemv_operand.cuh (cogv_gemm_rows_w8: E4M3 bytes and a row scale; cogv_gemm_rows_w4: MXFP4 blocks) -- see THE WEIGHT OPERAND below.
 //
 //   C[M,N] = epilogue( A[M,K] * B[N,K]^T ),   1 <= M <= 64, trans_a = trans_b = 0, flags BIAS | GELU | ABSMAX
 //
@@ -32,9 +33,20 @@
 // and a row's bits do not depend on the other rows of the call.  The epilogue is gemm_shared.cuh's epilogue8: every rounding point
 // is the skinny case's.
 //
-// Compiled as one unit per dtype (-DCOGV_GEMV_WIDE_TU=0: bf16, 1: fp16; build.py) with the kernels; without the macro this file
-// holds the two entry points and nothing that runs on the device.
-#include "gemm_shared.cuh"
+//   THE WEIGHT OPERAND is a type parameter, as in gemv.hip's FormM (W16 | W8 | W4, gemv_operand.cuh).  A lane's 16-byte weight load
+//   covers KL = 32 / 64 / 128 contraction elements of its weight row = FR = 1 / 2 / 4 MFMA fragments: lane l supplies elements
+//   (KL / 4) (l >> 4) + 8 f .. + 7 of the load's block to fragment f, and the x fragments -- still 16-byte loads of the 16-bit x
+//   from L2, one per fragment and row group -- take the same elements of their rows.  W8: the bytes convert to T exactly, and the
+//   fp32 row scale (requested behind the first weights, clamped column) multiplies the finished column sum once, in front of
+//   epilogue8.  W4: the E8M0 byte of a load is requested right behind it and folded into the conversion (v_cvt_scalef32_pk_*_fp4).
+//   Columns past N re-read row N - 1, codes and scales alike.  The matrix core multiplies T by T: x is never quantized (the
+//   block-scaled MFMA would do that, and is a different feature).  The quantized classes and their plan: gemv_wide_plan.h,
+//   GWQ_CLASSES.  The 16-bit instantiations kept their instruction text (profiles/r22_gemv_wide_operand_parent_vs_head.log).
+//
+// Compiled as one unit per dtype and operand (-DCOGV_GEMV_WIDE_TU=0: bf16, 1: fp16; with -DCOGV_GEMV_WIDE_W8 / -DCOGV_GEMV_WIDE_W4
+// the quantized operands; build.py) with the kernels; without the macro this file holds the entry points and nothing that runs on
+// the device.
+#include "gemv_operand.cuh"
 #include "gemv_wide_plan.h"
 
 #include <type_traits>
@@ -51,16 +63,21 @@ __device__ __forceinline__ int gw_vzero() {
   return zero;
 }
 
-template <typename T, int RG, int CT, int NWK, int LP, int DP, bool GUARD>
+// W: what B holds (gemv_operand.cuh).  A wave's UNIT of the contraction is LU loads of W::KL elements: the load pair of the
+// 16-bit operand (2 x 32), two loads of the 8-bit one (2 x 64), one block load of the 4-bit one (1 x 128); LP, DP count units.
+template <typename W, int RG, int CT, int NWK, int LP, int DP, bool GUARD>
 __global__ __launch_bounds__(NWK * 64) void gemv_wide_kernel(const GemmArgs p) {
+  typedef typename W::T T;
+  typedef typename W::Elem Elem;
   typedef typename HT<T>::v8 v8;
+  constexpr int KL = W::KL, FR = W::FR, PK = W::PK, LU = PK == 2 ? 1 : 2, UE = LU * KL;
   constexpr int TILES = RG * CT, R = gw_round(NWK, TILES), ROUNDS = (TILES + R - 1) / R;
   static_assert(DP >= 1 && DP <= LP && (CT == 1 || R % CT == 0), "gemv_wide_plan.h");
   extern __shared__ __attribute__((aligned(16))) char gw_smem[];      // red [R][NWK][64] f32x4 | outp [R][16][16] float
   f32x4 (*red)[NWK][64] = reinterpret_cast<f32x4 (*)[NWK][64]>(gw_smem);
   float (*outp)[16][16] = reinterpret_cast<float (*)[16][16]>(gw_smem + R * NWK * 1024);
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int K = GUARD ? p.K : LP * NWK * 64, npairs = K >> 6;
+  const int K = GUARD ? p.K : LP * NWK * UE, npairs = K >> (UE == 64 ? 6 : 7);
   const int n0 = blockIdx.x * (16 * CT);
   // the bias of the 8 columns this lane finishes (lanes 0 .. 31 of the first R waves: wave w keeps column tile w % CT through all
   // rounds), requested ahead of everything; unconditional, with a stand-in address where there is none (gemv.hip, gv2_bias)
@@ -68,34 +85,45 @@ __global__ __launch_bounds__(NWK * 64) void gemv_wide_kernel(const GemmArgs p) {
   const T* bsrc = (p.flags & COGV_EPI_BIAS) ? reinterpret_cast<const T*>(p.bias) : reinterpret_cast<const T*>(p.B);
   const u32x4 bias_pre = gload16(bsrc + (nfin < p.N ? nfin : p.N - 8) + gw_vzero());
   // A operand = weights: lane l supplies column (tile) + (l & 15); B operand = x: lane l supplies row 16 rg + (l & 15); both the
-  // contraction slots 8 (l >> 4) .. + 7 of a 32-deep step
-  const T* wrow[CT];
+  // contraction slots 8 (l >> 4) .. + 7 of a 32-deep step -- of fragment f of a load, elements (KL / 4) (l >> 4) + 8 f .. + 7 of its
+  // KL-element block (FormM's mapping: the 16 bytes of a lane are consecutive elements of its weight row)
+  const Elem* wrow[CT];
+  const uint8_t* srow[CT];      // W4: the row's block scales, from this lane's block of a load on
   const T* xrow[RG];
 #pragma unroll
   for (int ct = 0; ct < CT; ++ct) {
     const int nt = n0 + ct * 16 + (lane & 15);
-    wrow[ct] = reinterpret_cast<const T*>(p.B) + (size_t)(nt < p.N ? nt : p.N - 1) * p.ldb + (lane >> 4) * 8;
+    wrow[ct] = reinterpret_cast<const Elem*>(p.B) + (size_t)(nt < p.N ? nt : p.N - 1) * p.ldb + (lane >> 4) * (KL / 4 / PK);
+    if constexpr (PK == 2) srow[ct] = p.bscale + (size_t)(nt < p.N ? nt : p.N - 1) * p.ldbs + (lane >> 4);
   }
 #pragma unroll
   for (int rg = 0; rg < RG; ++rg) {
     const int m = rg * 16 + (lane & 15);
-    xrow[rg] = reinterpret_cast<const T*>(p.A) + (size_t)(m < p.M ? m : p.M - 1) * p.lda + (lane >> 4) * 8;
+    xrow[rg] = reinterpret_cast<const T*>(p.A) + (size_t)(m < p.M ? m : p.M - 1) * p.lda + (lane >> 4) * (KL / 4);
   }
-  u32x4 xr[DP][2][RG], wr[DP][2][CT];
+  u32x4 xr[DP][LU][RG][FR], wr[DP][LU][CT];
+  uint32_t ws[DP][LU][PK == 2 ? CT : 1];      // W4: the E8M0 byte of each load, requested right behind it
   // pair i of this wave into ring slot i % DP
   auto issue = [&](int i) {
     int q = wave + NWK * i;
     if (GUARD) q = q < npairs ? q : npairs - 1;
 #pragma unroll
-    for (int s = 0; s < 2; ++s) {
+    for (int s = 0; s < LU; ++s) {
 #pragma unroll
-      for (int rg = 0; rg < RG; ++rg) xr[i % DP][s][rg] = gload16(xrow[rg] + 64 * q + 32 * s);
+      for (int rg = 0; rg < RG; ++rg)
 #pragma unroll
-      for (int ct = 0; ct < CT; ++ct) wr[i % DP][s][ct] = gload16(wrow[ct] + 64 * q + 32 * s);
+        for (int f = 0; f < FR; ++f) xr[i % DP][s][rg][f] = gload16(xrow[rg] + UE * q + KL * s + 8 * f);
+#pragma unroll
+      for (int ct = 0; ct < CT; ++ct) {
+        wr[i % DP][s][ct] = gload16(wrow[ct] + (UE / PK) * q + (KL / PK) * s);
+        if constexpr (PK == 2) ws[i % DP][s][ct] = *(const COGV_GLOBAL uint8_t*)(srow[ct] + 4 * (LU * q + s));
+      }
     }
   };
 #pragma unroll
   for (int i = 0; i < DP; ++i) issue(i);
+  // W8: the row scales of the 8 columns this lane finishes, behind the first weights and far ahead of the tail (clamped column)
+  const typename W::Scale sc = W::scale(p, n0 + (wave % CT) * 16, lane & 1);
   f32x4 acc[TILES];
 #pragma unroll
   for (int t = 0; t < TILES; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -106,12 +134,21 @@ __global__ __launch_bounds__(NWK * 64) void gemv_wide_kernel(const GemmArgs p) {
   for (int i = 0; i < LP; ++i) {
     if (!GUARD || wave + NWK * i < npairs) {
 #pragma unroll
-      for (int s = 0; s < 2; ++s)
+      for (int s = 0; s < LU; ++s)
 #pragma unroll
-        for (int rg = 0; rg < RG; ++rg)
+        for (int f = 0; f < FR; ++f) {
+          v8 a[CT];
 #pragma unroll
-          for (int ct = 0; ct < CT; ++ct)
-            acc[rg * CT + ct] = HT<T>::mfma16(__builtin_bit_cast(v8, wr[i % DP][s][ct]), __builtin_bit_cast(v8, xr[i % DP][s][rg]), acc[rg * CT + ct]);
+          for (int ct = 0; ct < CT; ++ct) {
+            if constexpr (PK == 2) a[ct] = W::frag(wr[i % DP][s][ct], ws[i % DP][s][ct], f);
+            else a[ct] = W::frag(wr[i % DP][s][ct], f);
+          }
+#pragma unroll
+          for (int rg = 0; rg < RG; ++rg)
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct)
+              acc[rg * CT + ct] = HT<T>::mfma16(a[ct], __builtin_bit_cast(v8, xr[i % DP][s][rg][f]), acc[rg * CT + ct]);
+        }
     }
     __builtin_amdgcn_sched_barrier(0);
     if (i + DP < LP) {
@@ -142,9 +179,10 @@ __global__ __launch_bounds__(NWK * 64) void gemv_wide_kernel(const GemmArgs p) {
       const int t = r * R + wave;
       const int m = (t / CT) * 16 + (lane >> 1), n = n0 + (t % CT) * 16 + (lane & 1) * 8;
       if (m < p.M && n < p.N) {
+        const typename W::Factors s8 = W::factors(sc);      // (W8: the row scale, once, in front of the shared epilogue)
         float v[8];
 #pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = outp[wave][lane >> 1][(lane & 1) * 8 + i];
+        for (int i = 0; i < 8; ++i) v[i] = W::mul(outp[wave][lane >> 1][(lane & 1) * 8 + i], s8, i);
         am = absmax_pk(am, epilogue8<T>(p, m, n, v, &bias_pre));
       }
     }
@@ -159,10 +197,34 @@ __global__ __launch_bounds__(NWK * 64) void gemv_wide_kernel(const GemmArgs p) {
 
 using TT = std::conditional<COGV_GEMV_WIDE_TU != 0, f16_t, bf16_t>::type;
 
+#define GW_CAT2(a, b) a##b
+#define GW_CAT(a, b) GW_CAT2(a, b)
+
+// the unit's operand, class list and entry point (build.py: -DCOGV_GEMV_WIDE_W8 / -DCOGV_GEMV_WIDE_W4 for the quantized units)
+#if defined(COGV_GEMV_WIDE_W4)
+using WT = W4<TT>;
+#define GW_UNIT_CLASSES GWQ_CLASSES
+#define GW_CLS(NAME) GWQC_##NAME
+#define GW_RUN GW_CAT(cogv_gemv_wide_w4_run_, COGV_GEMV_WIDE_TU)
+constexpr int gw_unit_depth(int, int rg, int ct, int lp) { return gwq_depth(GW_W4, rg, ct, lp); }
+#elif defined(COGV_GEMV_WIDE_W8)
+using WT = W8<TT>;
+#define GW_UNIT_CLASSES GWQ_CLASSES
+#define GW_CLS(NAME) GWQC_##NAME
+#define GW_RUN GW_CAT(cogv_gemv_wide_w8_run_, COGV_GEMV_WIDE_TU)
+constexpr int gw_unit_depth(int, int rg, int ct, int lp) { return gwq_depth(GW_W8, rg, ct, lp); }
+#else
+using WT = W16<TT>;
+#define GW_UNIT_CLASSES GW_CLASSES
+#define GW_CLS(NAME) GWC_##NAME
+#define GW_RUN GW_CAT(cogv_gemv_wide_run_, COGV_GEMV_WIDE_TU)
+constexpr int gw_unit_depth(int nwk, int rg, int ct, int lp) { return gw_depth(nwk, rg, ct, lp); }
+#endif
+
 template <int NWK, int LP, bool G, int RG, int CT>
 int gw_launch(const GwPlan& pl, const GemmArgs& a, void* stream) {
-  constexpr int DP = gw_depth(NWK, RG, CT, LP);
-  hipLaunchKernelGGL((gemv_wide_kernel<TT, RG, CT, NWK, LP, DP, G>), dim3(pl.grid), dim3(pl.threads), (size_t)pl.lds,
+  constexpr int DP = gw_unit_depth(NWK, RG, CT, LP);
+  hipLaunchKernelGGL((gemv_wide_kernel<WT, RG, CT, NWK, LP, DP, G>), dim3(pl.grid), dim3(pl.threads), (size_t)pl.lds,
                      reinterpret_cast<hipStream_t>(stream), a);
   return COGV_OK;
 }
@@ -170,21 +232,18 @@ int gw_launch(const GwPlan& pl, const GemmArgs& a, void* stream) {
 // (one row group never takes two tiles: gemv_wide_plan.h, gw_ct)
 #define GW_RUN_RG(NWK, LP, G, RG) (pl.ct == 2 ? gw_launch<NWK, LP, G, RG, 2>(pl, a, stream) : gw_launch<NWK, LP, G, RG, 1>(pl, a, stream))
 #define GW_RUN_ROW(NAME, KF, KT, NWK, LP, G)                                            \
-  case GWC_##NAME:                                                                      \
+  case GW_CLS(NAME):                                                                    \
     return pl.rg == 1 ? gw_launch<NWK, LP, G, 1, 1>(pl, a, stream)                      \
          : pl.rg == 2 ? GW_RUN_RG(NWK, LP, G, 2) : pl.rg == 3 ? GW_RUN_RG(NWK, LP, G, 3) : GW_RUN_RG(NWK, LP, G, 4);
-
-#define GW_CAT2(a, b) a##b
-#define GW_CAT(a, b) GW_CAT2(a, b)
 
 }  // namespace
 
 // the unit's one entry point: the kernel of plan `plan`; args = GemmArgs
-extern "C" __attribute__((visibility("hidden"))) int GW_CAT(cogv_gemv_wide_run_, COGV_GEMV_WIDE_TU)(const GwPlan* plan, const void* args, void* stream) {
+extern "C" __attribute__((visibility("hidden"))) int GW_RUN(const GwPlan* plan, const void* args, void* stream) {
   const GwPlan& pl = *plan;
   const GemmArgs& a = *reinterpret_cast<const GemmArgs*>(args);
   switch (pl.cls) {
-    GW_CLASSES(GW_RUN_ROW)
+    GW_UNIT_CLASSES(GW_RUN_ROW)
     default: return COGV_ERR_UNSUPPORTED;
   }
 }
@@ -193,12 +252,17 @@ extern "C" __attribute__((visibility("hidden"))) int GW_CAT(cogv_gemv_wide_run_,
 
 extern "C" __attribute__((visibility("hidden"))) int cogv_gemv_wide_run_0(const GwPlan* plan, const void* args, void* stream);
 extern "C" __attribute__((visibility("hidden"))) int cogv_gemv_wide_run_1(const GwPlan* plan, const void* args, void* stream);
+extern "C" __attribute__((visibility("hidden"))) int cogv_gemv_wide_w8_run_0(const GwPlan* plan, const void* args, void* stream);
+extern "C" __attribute__((visibility("hidden"))) int cogv_gemv_wide_w8_run_1(const GwPlan* plan, const void* args, void* stream);
+extern "C" __attribute__((visibility("hidden"))) int cogv_gemv_wide_w4_run_0(const GwPlan* plan, const void* args, void* stream);
+extern "C" __attribute__((visibility("hidden"))) int cogv_gemv_wide_w4_run_1(const GwPlan* plan, const void* args, void* stream);
 
 namespace {
 
 // Descriptor -> argument block and launch plan, or the call's error: bad arguments (1) as cogv_gemm reports them, then what this
 // kernel does not take (3).  Nothing a pointer points to is read.
-int gw_front(const cogv_gemm_desc* d, GemmArgs& a, GwPlan& pl) {
+// fmt: what B holds.  A quantized operand has taken the place of d->B / d->ldb (bytes) before this is called.
+int gw_front(const cogv_gemm_desc* d, GemmArgs& a, GwPlan& pl, int fmt = GW_W16) {
   if (!d) return COGV_ERR_ARG;
   if (d->dtype != COGV_F16 && d->dtype != COGV_BF16) return COGV_ERR_UNSUPPORTED;
   if (d->M <= 0 || d->N <= 0 || d->K <= 0) return COGV_ERR_ARG;
@@ -210,8 +274,8 @@ int gw_front(const cogv_gemm_desc* d, GemmArgs& a, GwPlan& pl) {
   if (d->trans_a || d->trans_b || (d->flags & ~(COGV_EPI_BIAS | COGV_EPI_GELU | COGV_EPI_ABSMAX)) || d->out_f32 || d->splitk > 1 ||
       d->kernel_variant != 0 || d->aux)
     return COGV_ERR_UNSUPPORTED;
-  if (d->lda < d->K || d->ldb < d->K || d->ldc < d->N) return COGV_ERR_ARG;
-  if (!gw_plan(d->M, d->N, d->K, pl)) return COGV_ERR_UNSUPPORTED;
+  if (d->lda < d->K || d->ldb < (fmt == GW_W4 ? d->K / 2 : d->K) || d->ldc < d->N) return COGV_ERR_ARG;
+  if (!(fmt == GW_W16 ? gw_plan(d->M, d->N, d->K, pl) : gwq_plan(fmt, d->M, d->N, d->K, pl))) return COGV_ERR_UNSUPPORTED;
   a = GemmArgs{};
   a.A = d->A; a.B = d->B; a.C = d->C;
   a.M = d->M; a.N = d->N; a.K = d->K;
@@ -223,7 +287,71 @@ int gw_front(const cogv_gemm_desc* d, GemmArgs& a, GwPlan& pl) {
   return COGV_OK;
 }
 
+// The fronts of the quantized products: the operand checks of cogv_gemm_w8 / cogv_gemm_w4 (a NULL or misaligned operand, ldq % 16,
+// lds < K / 32: bad argument), then gw_front with the operand in B's place.
+int gw_front_w8(const cogv_gemm_desc* d, const cogv_w8_weight* w, GemmArgs& a, GwPlan& pl) {
+  if (!d || !w || !w->q || !w->scale) return COGV_ERR_ARG;
+  if ((w->ldq & 15) || (((uintptr_t)w->q | (uintptr_t)w->scale) & 15)) return COGV_ERR_ARG;
+  cogv_gemm_desc dd = *d;
+  dd.B = w->q; dd.ldb = w->ldq;
+  const int rc = gw_front(&dd, a, pl, GW_W8);
+  if (rc != COGV_OK) return rc;
+  a.wscale = w->scale;
+  return COGV_OK;
+}
+
+int gw_front_w4(const cogv_gemm_desc* d, const cogv_w4_weight* w, GemmArgs& a, GwPlan& pl) {
+  if (!d || !w || !w->q || !w->scale) return COGV_ERR_ARG;
+  if ((w->ldq & 15) || ((uintptr_t)w->q & 15) || d->K <= 0 || w->lds < d->K / 32) return COGV_ERR_ARG;
+  cogv_gemm_desc dd = *d;
+  dd.B = w->q; dd.ldb = w->ldq;
+  const int rc = gw_front(&dd, a, pl, GW_W4);
+  if (rc != COGV_OK) return rc;
+  a.bscale = reinterpret_cast<const uint8_t*>(w->scale);
+  a.ldbs = w->lds;
+  return COGV_OK;
+}
+
+int gw_plan_out(int rc, const GwPlan& pl, int loads, int* out) {
+  if (rc != COGV_OK) return rc;
+  const int v[COGV_GEMM_ROWS_PLAN_INTS] = {pl.rg, pl.nwk, pl.ct, loads * pl.lp * pl.ct, pl.guard, 0, pl.threads, pl.grid, pl.lds, pl.depth};
+  for (int i = 0; i < COGV_GEMM_ROWS_PLAN_INTS; ++i) out[i] = v[i];
+  return COGV_OK;
+}
+
 }  // namespace
+
+extern "C" int cogv_gemm_rows_w8(const cogv_gemm_desc* d, const cogv_w8_weight* w, void* stream) {
+  GemmArgs a;
+  GwPlan pl;
+  const int rc = gw_front_w8(d, w, a, pl);
+  if (rc != COGV_OK) return rc;
+  const int rr = d->dtype == COGV_F16 ? cogv_gemv_wide_w8_run_1(&pl, &a, stream) : cogv_gemv_wide_w8_run_0(&pl, &a, stream);
+  return rr != COGV_OK ? rr : cogv_check_launch();
+}
+
+extern "C" int cogv_gemm_rows_w4(const cogv_gemm_desc* d, const cogv_w4_weight* w, void* stream) {
+  GemmArgs a;
+  GwPlan pl;
+  const int rc = gw_front_w4(d, w, a, pl);
+  if (rc != COGV_OK) return rc;
+  const int rr = d->dtype == COGV_F16 ? cogv_gemv_wide_w4_run_1(&pl, &a, stream) : cogv_gemv_wide_w4_run_0(&pl, &a, stream);
+  return rr != COGV_OK ? rr : cogv_check_launch();
+}
+
+extern "C" int cogv_gemm_rows_w8_plan(const cogv_gemm_desc* d, const cogv_w8_weight* w, int out[COGV_GEMM_ROWS_PLAN_INTS]) {
+  if (!out) return COGV_ERR_ARG;
+  GemmArgs a;
+  GwPlan pl;
+  return gw_plan_out(gw_front_w8(d, w, a, pl), pl, gwq_loads(GW_W8), out);
+}
+
+extern "C" int cogv_gemm_rows_w4_plan(const cogv_gemm_desc* d, const cogv_w4_weight* w, int out[COGV_GEMM_ROWS_PLAN_INTS]) {
+  if (!out) return COGV_ERR_ARG;
+  GemmArgs a;
+  GwPlan pl;
+  return gw_plan_out(gw_front_w4(d, w, a, pl), pl, gwq_loads(GW_W4), out);
+}
 
 extern "C" int cogv_gemm_rows(const cogv_gemm_desc* d, void* stream) {
   GemmArgs a;
@@ -238,11 +366,7 @@ extern "C" int cogv_gemm_rows_plan(const cogv_gemm_desc* d, int out[COGV_GEMM_RO
   if (!out) return COGV_ERR_ARG;
   GemmArgs a;
   GwPlan pl;
-  const int rc = gw_front(d, a, pl);
-  if (rc != COGV_OK) return rc;
-  const int v[COGV_GEMM_ROWS_PLAN_INTS] = {pl.rg, pl.nwk, pl.ct, 2 * pl.lp * pl.ct, pl.guard, 0, pl.threads, pl.grid, pl.lds, pl.depth};
-  for (int i = 0; i < COGV_GEMM_ROWS_PLAN_INTS; ++i) out[i] = v[i];
-  return COGV_OK;
+  return gw_plan_out(gw_front(d, a, pl), pl, 2, out);
 }
 
 #endif  // COGV_GEMV_WIDE_TU

@@ -70,3 +70,62 @@ inline bool gw_plan(int M, int N, int K, GwPlan& pl) {
   }
   return false;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The same kernel on the quantized weight operands of gemv_operand.cuh (cogv_gemm_rows_w8: E4M3 bytes and a row scale,
+// cogv_gemm_rows_w4: MXFP4 blocks).  A 16-byte load of a lane holds 16 (W8) or 32 (W4) contraction elements of its weight row, so a
+// wave's UNIT -- what the 16-bit kernel calls a load pair -- is 128 contraction elements for both formats: two loads of 2 fragments
+// (W8), one load of 4 fragments and its scale byte (W4).  Per unit and lane: 16 x registers per row group (4 fragments of 16 bytes),
+// 8 (W8) or 5 (W4) weight registers per column tile.  Half or a quarter of the bytes per contraction element take half the waves
+// per tile to keep the same weight bytes in flight per workgroup column; every class has at most 8 waves, so a wave has 256
+// registers and no class spills (the table per instantiation class).
+//   X(name, K from, K to, NWK, LP units per wave, guarded)     -- the class depends on K ALONE, as above
+#define GWQ_CLASSES(X)                     \
+  X(K1024,  1024,  1024,  4,  2,  false)   \
+  X(K2560,  2560,  2560,  4,  5,  false)   \
+  X(K4096,  4096,  4096,  8,  4,  false)   \
+  X(K10240, 10240, 10240, 8,  10, false)   \
+  X(G2,     512,   1024,  4,  2,  true)    \
+  X(G5,     512,   2560,  4,  5,  true)    \
+  X(G10,    512,   10240, 8,  10, true)
+
+#define GWQ_ENUM_ROW(NAME, ...) GWQC_##NAME,
+enum GwqClassId { GWQ_CLASSES(GWQ_ENUM_ROW) GWQC_COUNT };
+#undef GWQ_ENUM_ROW
+#define GW_ROW(NAME, KF, KT, NWK, LP, G) {KF, KT, NWK, LP, G},
+constexpr GwClass GWQ_CLASS_TABLE[GWQC_COUNT] = {GWQ_CLASSES(GW_ROW)};
+#undef GW_ROW
+
+enum GwFormat { GW_W16 = 0, GW_W8 = 1, GW_W4 = 2 };
+// Two column tiles from 2 row groups on where N reaches this bound: the 16-bit rule (GW_CT2_MIN_N) unless an A/B build says
+// otherwise (tools/mb_gemm_rows_q.py; DESIGN 4.5.8 has the measurement that keeps it).
+#ifndef GWQ_CT2_MIN_N
+#define GWQ_CT2_MIN_N GW_CT2_MIN_N
+#endif
+constexpr int gwq_ct(int rg, int N) { return rg >= 2 && N >= GWQ_CT2_MIN_N ? 2 : 1; }
+constexpr int GWQ_UNIT = 128;                                         // contraction elements of a unit
+constexpr int gwq_loads(int fmt) { return fmt == GW_W4 ? 1 : 2; }     // 16-byte weight loads of a lane per unit and column tile
+// x bytes a workgroup requests from L2 per weight byte: 4 fragments of 16 bytes per row group against 2 (W8) or 1 (W4) loads of 16
+// bytes per column tile = 2 RG / CT and 4 RG / CT, twice and four times the 16-bit kernel's RG / CT.  The column tiles follow the
+// 16-bit rule (gwq_ct: two from 2 row groups on where N >= 4096); four tiles or x staged in LDS were not built -- DESIGN 4.5.8 has
+// the ratio per plan and what was and was not measured.
+// Units a wave keeps in flight, from its 256 registers: the accumulators, 40 for addresses and the epilogue, 8 for the row scales
+// of a finishing lane (W8), and 16 for a unit's conversion (8 floats and the packed fragment of one column tile at a time).
+constexpr int gwq_depth(int fmt, int rg, int ct, int lp) {
+  const int unit = 16 * rg + (fmt == GW_W4 ? 5 : 8) * ct;
+  const int d = (256 - 4 * rg * ct - 40 - (fmt == GW_W8 ? 8 : 0) - 16) / unit;
+  return d < 1 ? 1 : d > lp ? lp : d;
+}
+
+// the plan of a product on a quantized operand (fmt: GW_W8 | GW_W4); cls indexes GWQ_CLASSES
+inline bool gwq_plan(int fmt, int M, int N, int K, GwPlan& pl) {
+  if (M < 1 || M > GW_MAX_M || N < 8 || (N & 7) || K < GW_MIN_K || K > GW_MAX_K || (K & 511)) return false;
+  for (int i = 0; i < GWQC_COUNT; ++i) {
+    const GwClass& c = GWQ_CLASS_TABLE[i];
+    if (K < c.k_from || K > c.k_to) continue;
+    const int rg = gw_rg(M), ct = gwq_ct(rg, N), cols = 16 * ct;
+    pl = GwPlan{rg, c.nwk, ct, c.lp, c.guard, gwq_depth(fmt, rg, ct, c.lp), 64 * c.nwk, (N + cols - 1) / cols, gw_lds(c.nwk, rg * ct), i};
+    return true;
+  }
+  return false;
+}

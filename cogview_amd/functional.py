@@ -1105,6 +1105,33 @@ def decode_wide_supported(tr, rows):
     return all(_lib.gemm_rows_plan(code, rows, n, k)[0] == _lib.OK for n, k in ((3 * hp, h), (h, hp), (f, h), (h, f), (h, h)))
 
 
+def decode_wide_q_supported(tr, rows, fmt):
+    """The wide decode step on quantized weights (decode_layers(w8=..., wide=True); fmt "e4m3" | "mxfp4") at this row count: None, or
+    the reason as a string.  9 .. 64 rows on one model-parallel partition in a 16-bit type, and every product the step issues
+    (QKV, attention output, h -> 4h, 4h -> h, logits) taken by the library's own launch plan (cogv_gemm_rows_w8_plan /
+    cogv_gemm_rows_w4_plan: host only, nothing is touched).  The tied-logits product is asked with h columns: N decides a grid,
+    never whether a class takes the product.  Opt-in (the `wide=True` of the decoders): neither COGV_DECODE_WIDE nor
+    COGV_DECODE_WIDE_MAX_ROWS, which bound the 16-bit step's default, is consulted."""
+    from . import _lib
+    if mp_world_size_or_1() != 1:
+        return "the wide step on quantized weights runs on one model-parallel partition"
+    if not DECODE_WIDE_MIN_ROWS <= rows <= DECODE_WIDE_KERNEL_ROWS:
+        return f"{rows} rows are outside the wide step's {DECODE_WIDE_MIN_ROWS} .. {DECODE_WIDE_KERNEL_ROWS}"
+    att = tr.layers[0].attention
+    dt = att.query_key_value.weight.dtype
+    if dt not in (torch.float16, torch.bfloat16):
+        return f"{dt} weights: the wide products take fp16 and bf16"
+    h = tr.layers[0].input_layernorm.weight.shape[0]
+    f = tr.layers[0].mlp.dense_h_to_4h.weight.shape[0]
+    hp = att.num_attention_heads_per_partition * 64
+    code = _lib.BF16 if dt == torch.bfloat16 else _lib.F16
+    query, bits = (_lib.gemm_rows_w4_plan, 4) if fmt == "mxfp4" else (_lib.gemm_rows_w8_plan, 8)
+    for n, k in ((3 * hp, h), (h, hp), (f, h), (h, f), (h, h)):
+        if query(code, rows, n, k)[0] != _lib.OK:
+            return f"contraction length {k} at {rows} rows is outside the {bits}-bit wide kernel's classes ({n} columns)"
+    return None
+
+
 def decode_chain(tr, h0, absmax0, slots, emb_weight, w8=None):
     """One decode step through all layers with FIVE launches per layer (round 3: the split-combine of the decode attention
     rides in the dense GEMV's prologue): QKV GEMV with [previous layer's
@@ -1167,8 +1194,9 @@ def decode_layers(tr, h0, absmax0, slots, emb_weight, w8=None, wide=False):
     decode attention with its combine, four plain skinny products per layer), the final LayerNorm and the tied-logits product.
     h0 [b, m, h] -> logits [b, m, V]; m > 1: a chunk step, as in decode_chain.  w8 (W8Weights | W4Weights): the products read the 8-bit
     or 4-bit copies (emb_weight is not read).  What a decoder runs above COGV_DECODE_CHAIN_MAX_ROWS for the 8-bit weights and for chunk steps, and
-    the comparison path of the chain.  wide=True (16-bit weights, up to 64 rows; decode_wide_supported): the five products go to
-    ops.gemm_rows, the weight-streaming form above 8 rows; nothing else changes."""
+    the comparison path of the chain.  wide=True (up to 64 rows): the five products go to the weight-streaming form above 8 rows --
+    ops.gemm_rows on the 16-bit weights (decode_wide_supported), ops.gemm_rows_w8 / ops.gemm_rows_w4 on the quantized copies
+    (decode_wide_q_supported); nothing else changes."""
     b, s, h = h0.shape
     rows = b * s
     dev = h0.device
@@ -1177,8 +1205,8 @@ def decode_layers(tr, h0, absmax0, slots, emb_weight, w8=None, wide=False):
         operands = ((l.attention.query_key_value.weight, l.attention.dense.weight, l.mlp.dense_h_to_4h.weight, l.mlp.dense_4h_to_h.weight)
                     for l in tr.layers)
     else:
-        assert not wide, "the wide step streams the 16-bit weights"
-        gemm, logits_w, operands = _quantized_products(w8)[1], w8.emb, w8.layers
+        gemm = (ops.gemm_rows_w4 if isinstance(w8, W4Weights) else ops.gemm_rows_w8) if wide else _quantized_products(w8)[1]
+        logits_w, operands = w8.emb, w8.layers
     x, absmax_x = (h0 if h0.is_contiguous() else h0.contiguous()), absmax0
     for layer, slot, (w_qkv, w_dense, w_h4h, w_4hh) in zip(tr.layers, slots, operands):
         att_m, mlp_m = layer.attention, layer.mlp

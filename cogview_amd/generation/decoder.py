@@ -29,13 +29,15 @@ def unwrap(model):
 MAX_STEP_ROWS = 8          # rows of one decode step: what the skinny products and the chunk attention take
 
 
-def refuse_unsupported(weights=None, kv=None, ragged=False, args=None, model=None, batch=None, use=None, chunk=0):
+def refuse_unsupported(weights=None, kv=None, ragged=False, args=None, model=None, batch=None, use=None, chunk=0, wide=False):
     """The one rule for what the decode step's options do not cover, applied before anything is allocated or quantized.
     Asked for: weights= / kv= (formats), ragged=True and chunk=C (a second step of C tokens per cache row: 2 <= C <= 8 and
     batch * C <= 8 rows, on the 16-bit cache).  Known, each optional: `args` (a caller's .is_sparse), `model` (its storage
     type), `batch` (the decoder's rows; with it the 8-bit weight stream is put to the kernels' launch plan).  `use`: what the message
     advises instead (a caller's host form; default: the decoder's own plain options).  Sparse generation and model parallelism > 1
-    are refused for every caller that hands in `args`, with or without options; a plain decoder refuses nothing."""
+    are refused for every caller that hands in `args`, with or without options; a plain decoder refuses nothing.
+    wide=True (opt-in; a later change makes it the default): with weights= set, 9 ... 64 rows are put to the wide products' launch
+    plan (functional.decode_wide_q_supported) instead of being refused as more than 8 rows.  False: every refusal is what it was."""
     from ..mpu.initialize import mp_world_size_or_1
     if weights is not None and weights not in WEIGHT_FORMATS:
         raise ValueError(f"weights={weights!r}: None (16-bit) or one of {WEIGHT_FORMATS}")
@@ -74,13 +76,16 @@ def refuse_unsupported(weights=None, kv=None, ragged=False, args=None, model=Non
         if gpt.word_embeddings.weight.shape[0] % 8:
             raise NotImplementedError(f"weights={weights!r}: a vocabulary of {gpt.word_embeddings.weight.shape[0]} rows (not a multiple of 8)")
         for rows in (batch, batch * chunk) if chunk else (batch,):
-            why = (F_.w4_decode_supported if weights == "mxfp4" else F_.w8_decode_supported)(gpt.transformer, rows)
+            if wide and rows > MAX_STEP_ROWS:
+                why = F_.decode_wide_q_supported(gpt.transformer, rows, weights)
+            else:
+                why = (F_.w4_decode_supported if weights == "mxfp4" else F_.w8_decode_supported)(gpt.transformer, rows)
             if why is not None:
                 raise NotImplementedError(f"weights={weights!r}: {why}")
 
 
 class GraphDecoder:
-    def __init__(self, model, batch=1, capacity=1152, weights=None, kv=None, ragged=False, chunk=0):
+    def __init__(self, model, batch=1, capacity=1152, weights=None, kv=None, ragged=False, chunk=0, wide=False):
         """model: GPT2Model (optionally inside FP16_Module) in eval mode, dense attention; capacity: slots per cache
         (<= 4096, the gathered form's limit).
         weights="e4m3": the decode step streams 8-bit copies of the weights (OCP E4M3 bytes with one fp32 scale per row,
@@ -112,12 +117,19 @@ class GraphDecoder:
         of slots *pos_index + j, appended to and attended over the same caches by ops.attention_decode_chunk; capture() captures
         it as a second graph.  The Sandwich-LN scale of a chunk step is the abs-max over all its rows, as in a multi-token model
         call, so its logits are not bit-equal to C one-token steps'.  Composes with weights= and ragged=; the 16-bit cache only.
-        0 (default): nothing is allocated or captured, the decoder is what it was."""
+        0 (default): nothing is allocated or captured, the decoder is what it was.
+        wide=True (opt-in; a later change makes it the default): with weights= set and 9 ... 64 rows the step runs layer by layer on
+        the quantized copies through the wide weight-streaming products (ops.gemm_rows_w8 / ops.gemm_rows_w4; functional.decode_layers(
+        w8=..., wide=True)) instead of being refused as more than 8 rows.  Composes with kv= and ragged=; chunk= keeps batch * chunk
+        <= 8.  Captured 4B step: 5.13 / 6.87 / 7.85 / 12.75 ms on "e4m3" and 4.91 / 6.71 / 7.74 / 12.63 ms on "mxfp4" at 12 /
+        24 / 32 / 64 rows against 5.72 / 7.62 / 8.67 / 13.35 ms on the 16-bit wide step of the same process -- faster at every row
+        count measured; against the tile kernels, which the 16-bit decoder takes above 24 rows, not faster from 48 rows on.  With
+        16-bit weights, or up to 8 rows, the keyword has no effect.  False (default): every refusal and every launch is what it was."""
         m = unwrap(model)
         self.gpt, tr = m, m.transformer
         assert capacity <= 4096
         self.w8, self.w4, self.kv, self.first = None, None, kv, None
-        refuse_unsupported(weights, kv, ragged, model=m, batch=batch, chunk=chunk)
+        refuse_unsupported(weights, kv, ragged, model=m, batch=batch, chunk=chunk, wide=wide)
         self.chunk = int(chunk)
         if weights == "mxfp4":
             with torch.no_grad():
@@ -126,6 +138,7 @@ class GraphDecoder:
             with torch.no_grad():
                 self.w8 = F_.W8Weights(tr, m.word_embeddings.weight)
         self.wq = self.w4 if self.w4 is not None else self.w8       # the quantized copies the step streams, if any
+        self.wide_q = bool(wide) and self.wq is not None and batch > MAX_STEP_ROWS      # the step takes the wide products on them
         p0 = tr.layers[0].attention.query_key_value.weight
         hp = tr.layers[0].attention.hidden_size_per_partition
         dev, dt = p0.device, p0.dtype
@@ -164,6 +177,9 @@ class GraphDecoder:
                 # five launches per layer: the LayerNorms ride as prologues of the GEMVs, the cache append inside the
                 # decode attention kernel (functional.decode_chain); w8: the same chain on the 8-bit copies of the weights
                 return F_.decode_chain(tr, h, h._cogv_absmax, self.slots, self.gpt.word_embeddings.weight, w8=self.wq)
+            if self.wide_q:
+                # 9 .. 64 rows on the quantized copies: the five products as weight streams (ops.gemm_rows_w8 / ops.gemm_rows_w4)
+                return F_.decode_layers(tr, h, h._cogv_absmax, self.slots, None, w8=self.wq, wide=True)
             if self.wq is not None:
                 return F_.decode_layers_w8(tr, h, h._cogv_absmax, self.slots, self.wq)
             if F_.decode_wide_supported(tr, self.batch):
@@ -312,9 +328,10 @@ class SamplingDecoder(GraphDecoder):
     and a run of them needs no host work.  Reference path: generation/sampling.py:139-186 (model call, filter, multinomial,
     beam score) once per token.  Use start() + generate() (step() feeds tokens from the host and is not for this mode)."""
 
-    def __init__(self, model, batch=1, capacity=1152, weights=None, kv=None, ragged=False, chunk=0):
-        """chunk=C: generate(n, widths=...) may feed runs of given ids as chunk steps (GraphDecoder's `chunk`; _step_chunk below)."""
-        super().__init__(model, batch, capacity, weights=weights, kv=kv, ragged=ragged, chunk=chunk)
+    def __init__(self, model, batch=1, capacity=1152, weights=None, kv=None, ragged=False, chunk=0, wide=False):
+        """chunk=C: generate(n, widths=...) may feed runs of given ids as chunk steps (GraphDecoder's `chunk`; _step_chunk below).
+        wide: GraphDecoder's (opt-in: quantized weights at 9 ... 64 rows)."""
+        super().__init__(model, batch, capacity, weights=weights, kv=kv, ragged=ragged, chunk=chunk, wide=wide)
         self.sampling = None
         self.chunk_steps = 0         # chunk steps run by generate() so far
 

@@ -463,11 +463,15 @@ class _DeviceRun:
     generate_batch_on_device use one for one call; DeviceGenerator, DeviceFiller and DeviceBatchFiller keep theirs call after call.
     .out [batch, width] receives the id drawn for sequence position out_base + j in column j; .given (DeviceFiller: [capacity],
     DeviceBatchFiller: [rows, capacity]) is the sampler's given table.  batch: the decoder's rows where the caller knows them
-    before the first call (the refusal rule then also judges chunk= and weights= at that row count)."""
+    before the first call (the refusal rule then also judges chunk= and weights= at that row count).  wide: SamplingDecoder's
+    opt-in keyword (quantized weights at 9 ... 64 rows), handed on only where it is set."""
     given = None
 
-    def __init__(self, model, args, seed=0, capture=True, weights=None, kv=None, ragged=False, chunk=0, batch=None):
-        decoder.refuse_unsupported(weights, kv, ragged, args=args, model=model, use="filling_sequence", chunk=chunk, batch=batch)
+    def __init__(self, model, args, seed=0, capture=True, weights=None, kv=None, ragged=False, chunk=0, batch=None, wide=False):
+        if wide:
+            decoder.refuse_unsupported(weights, kv, ragged, args=args, model=model, use="filling_sequence", chunk=chunk, batch=batch, wide=True)
+        else:
+            decoder.refuse_unsupported(weights, kv, ragged, args=args, model=model, use="filling_sequence", chunk=chunk, batch=batch)
         self.model, self.seed, self.capture, self.ragged, self.chunk = model, int(seed), capture, ragged, int(chunk)
         self.formats = {"weights": weights}           # only the keywords that are set: a default build issues the call it always did
         if kv is not None:
@@ -476,6 +480,8 @@ class _DeviceRun:
             self.formats["ragged"] = True
         if chunk:
             self.formats["chunk"] = self.chunk
+        if wide:
+            self.formats["wide"] = True
         self.dec, self.key, self.out = None, None, None
 
     def size(self, batch, capacity, width=None, out_base=0):
@@ -522,7 +528,7 @@ class _DeviceRun:
         return dec.scores.clone()
 
 
-def generate_on_device(model, seq, args, tokenizer=None, seed=0, capture=True, weights=None, kv=None):
+def generate_on_device(model, seq, args, tokenizer=None, seed=0, capture=True, weights=None, kv=None, wide=False):
     """filling_sequence for one run of generated tokens with the sampling on the device: prefill of the context (one row,
     its keys / values broadcast into the nb cache rows), nb independent first draws from its last logits, then one
     captured decode graph per token (generation/decoder.py SamplingDecoder) whose last launch filters, draws, and feeds
@@ -533,9 +539,11 @@ def generate_on_device(model, seq, args, tokenizer=None, seed=0, capture=True, w
     capture=False runs the same launches eagerly (the reference for the captured form).
     weights="e4m3" | "mxfp4": the decode steps stream 8-bit or 4-bit copies of the weights (GraphDecoder's `weights`; the prefill
     stays 16-bit).
-    kv="e4m3": the key/value caches hold 8-bit keys and values (GraphDecoder's `kv`); composes with `weights`."""
+    kv="e4m3": the key/value caches hold 8-bit keys and values (GraphDecoder's `kv`); composes with `weights`.
+    wide=True (opt-in; a later change makes it the default): with `weights` set, nb = 9 ... 64 rows run on the wide products of the
+    quantized copies (GraphDecoder's `wide`) instead of being refused; no effect with 16-bit weights or up to 8 rows."""
     tokenizer = tokenizer if tokenizer is not None else IdSpace()
-    drv = _DeviceRun(model, args, seed, capture, weights, kv)
+    drv = _DeviceRun(model, args, seed, capture, weights, kv, wide=wide)
     assert seq.dim() == 1
     plan = plan_device_generation(seq.tolist(), tokenizer, drv.vocab())
     n, run, nb = plan["context"], plan["run"], plan["nb"]
@@ -576,7 +584,7 @@ def _batch_run(drv, seqs, plan, args):
     return res, scores.view(len(seqs), nb).to(seqs[0].device)
 
 
-def generate_batch_on_device(model, seqs, args, tokenizer=None, seed=0, capture=True, weights=None, kv=None):
+def generate_batch_on_device(model, seqs, args, tokenizer=None, seed=0, capture=True, weights=None, kv=None, wide=False):
     """generate_on_device for G prompts at once on ONE decode graph (the reference's generate_images_continually walks a file
     of prompts one after another, generate_samples.py:202-221; a decode step is a weight stream that costs little more for
     eight rows than for one).  seqs: list of 1-D tensors, each a context of given ids followed by one run of equal marks; the
@@ -584,14 +592,16 @@ def generate_batch_on_device(model, seqs, args, tokenizer=None, seed=0, capture=
     right-aligned in the caches (SamplingDecoder(ragged=True)): one prefill under a per-prompt mask, then every replay draws
     one token for all G * nb rows -- row g * nb + j is candidate j of prompt g.
     Returns (list of G tensors [nb, len(seq_g)] without padding, scores [G, nb] fp32), on the sequences' device.
-    One prompt is generate_on_device itself (the plain decoder: same launches, same bits).  weights / kv / capture / seed as there."""
+    One prompt is generate_on_device itself (the plain decoder: same launches, same bits).  weights / kv / capture / seed / wide
+    (opt-in: quantized weights at 9 ... 64 rows; a later change makes it the default) as there."""
     tokenizer = tokenizer if tokenizer is not None else IdSpace()
     seqs = list(seqs)
     assert seqs and all(seq.dim() == 1 for seq in seqs)
     if len(seqs) == 1:
-        tokens, scores = generate_on_device(model, seqs[0], args, tokenizer=tokenizer, seed=seed, capture=capture, weights=weights, kv=kv)
+        more = {"wide": True} if wide else {}
+        tokens, scores = generate_on_device(model, seqs[0], args, tokenizer=tokenizer, seed=seed, capture=capture, weights=weights, kv=kv, **more)
         return [tokens], scores.view(1, -1)
-    drv = _DeviceRun(model, args, seed, capture, weights, kv, ragged=True)
+    drv = _DeviceRun(model, args, seed, capture, weights, kv, ragged=True, wide=wide)
     plan = plan_device_batch([seq.tolist() for seq in seqs], tokenizer, drv.vocab())
     drv.size(plan["rows"], plan["capacity"], width=plan["run"], out_base=plan["P"])
     return _batch_run(drv, seqs, plan, args)
@@ -604,10 +614,11 @@ class DeviceGenerator(_DeviceRun):
     is device data: the caches, `first`, the token / position / slot buffers, the generator offset (it keeps counting across
     calls, so every call draws fresh numbers) and the output buffer ([rows, capacity], column = slot).  Temperature, top-k /
     top-p and the drawable range are baked into the capture: a call with other values re-arms the sampler and captures again.
-    A single prompt (G = 1) runs on the same ragged decoder with first = 0.  capture / weights / kv as generate_on_device's."""
+    A single prompt (G = 1) runs on the same ragged decoder with first = 0.  capture / weights / kv / wide as generate_on_device's
+    (wide=True: opt-in, quantized weights at 9 ... 64 rows; a later change makes it the default)."""
 
-    def __init__(self, model, args, rows, capacity=1152, seed=0, capture=True, weights=None, kv=None):
-        super().__init__(model, args, seed, capture, weights, kv, ragged=True)
+    def __init__(self, model, args, rows, capacity=1152, seed=0, capture=True, weights=None, kv=None, wide=False):
+        super().__init__(model, args, seed, capture, weights, kv, ragged=True, wide=wide)
         self.size(rows, capacity)
         if rows < 1:
             raise ValueError(f"rows = {rows} must be positive")
@@ -711,11 +722,13 @@ class DeviceBatchFiller(_DeviceRun):
     re-arms and captures again); the generator offset keeps counting across calls.
     capture / weights / kv as DeviceFiller's.  chunk=C: runs of given ids are fed as chunk steps on a second graph (rows * C <= 8
     rows per step, 16-bit cache only).  Above 8 rows the decoder takes the wide step (9 ... 24 rows) or the tile kernels by
-    itself; weights="e4m3" covers up to 8 rows, so it is refused above them.  Dense attention, one model-parallel partition,
-    fp16 / bf16, P + replays + 1 <= capacity slots."""
+    itself; weights="e4m3" covers up to 8 rows, so it is refused above them -- unless wide=True (opt-in; a later change makes it
+    the default): 9 ... 64 rows then run on the wide products of the quantized copies (GraphDecoder's `wide`: 1.05-1.17x the 16-bit
+    wide step's speed at 12 ... 64 rows of the captured 4B step, not faster than the tile kernels from 48 rows on).  Dense attention, one model-parallel partition, fp16 / bf16, P + replays + 1 <= capacity
+    slots."""
 
-    def __init__(self, model, args, rows, capacity=1408, seed=0, capture=True, weights=None, kv=None, chunk=0):
-        super().__init__(model, args, seed, capture, weights, kv, ragged=True, chunk=chunk, batch=rows)
+    def __init__(self, model, args, rows, capacity=1408, seed=0, capture=True, weights=None, kv=None, chunk=0, wide=False):
+        super().__init__(model, args, seed, capture, weights, kv, ragged=True, chunk=chunk, batch=rows, wide=wide)
         if rows < 1:
             raise ValueError(f"rows = {rows} must be positive")
         self.size(rows, capacity)

@@ -359,6 +359,52 @@ def gemm_rows(a, w, bias=None, gelu=False, absmax=None, out=None):
     return out
 
 
+def _rows_q(a, K, N, bias, gelu, absmax, out):
+    """(descriptor, out) of a wide product on a quantized weight with N rows: the operand itself is the caller's."""
+    _need_gpu(a)
+    assert a.dim() == 2 and a.stride(1) == 1 and a.shape[1] == K, "a [M, K] with K matching the weight"
+    assert bias is None or bias.dtype == a.dtype
+    M = a.shape[0]
+    if out is None:
+        out = torch.empty((M, N), dtype=a.dtype, device=a.device)
+    assert out.shape == (M, N) and out.dtype == a.dtype and out.stride(1) == 1
+    d = _skinny_desc(out, K, bias, gelu, absmax)
+    d.ldc = out.stride(0)
+    d.A, d.lda = a.data_ptr(), a.stride(0)
+    return d, out
+
+
+def gemm_rows_w8(a, qs, bias=None, gelu=False, absmax=None, out=None):
+    """gemm_rows on an 8-bit weight qs = (q [N, K] uint8, scale [N] fp32) from quantize_rows_e4m3 (cogv_gemm_rows_w8): out [M, N] =
+    epilogue(scale * (a . e4m3(q)^T) + bias) in a's dtype for 1 <= M <= 64 rows; gemm_w8 stops at 8.  Rows of a, q and a given
+    `out` may be strided (q: a multiple of 16 bytes).  Shapes outside raise: there is no other kernel."""
+    q, scale = qs
+    _need_gpu(q, scale)
+    assert q.dim() == 2 and q.dtype == torch.uint8 and q.stride(1) == 1, "q [N, K] uint8"
+    assert scale.dtype == torch.float32 and scale.is_contiguous() and scale.numel() == q.shape[0]
+    d, out = _rows_q(a, q.shape[1], q.shape[0], bias, gelu, absmax, out)
+    w = L.W8Weight()
+    w.q, w.ldq, w.scale = q.data_ptr(), q.stride(0), scale.data_ptr()
+    L.check(L.lib().cogv_gemm_rows_w8(C.byref(d), C.byref(w), _stream()), "cogv_gemm_rows_w8")
+    return out
+
+
+def gemm_rows_w4(a, qs, bias=None, gelu=False, absmax=None, out=None):
+    """gemm_rows on a 4-bit weight qs = (q [N, K / 2] uint8, scale [N, K / 32] uint8) from quantize_rows_mxfp4 (cogv_gemm_rows_w4):
+    out [M, N] = epilogue(a . dequantize_rows_mxfp4(q, scale)^T + bias) in a's dtype for 1 <= M <= 64 rows; gemm_w4 stops at 8.
+    Rows of a, q (a multiple of 16 bytes), scale and a given `out` may be strided.  Shapes outside raise: there is no other kernel."""
+    q, scale = qs
+    _need_gpu(q, scale)
+    assert q.dim() == 2 and q.dtype == torch.uint8 and q.stride(1) == 1, "q [N, K / 2] uint8"
+    K = q.shape[1] * 2
+    assert scale.dim() == 2 and scale.dtype == torch.uint8 and scale.stride(1) == 1 and scale.shape == (q.shape[0], K // 32)
+    d, out = _rows_q(a, K, q.shape[0], bias, gelu, absmax, out)
+    w = L.W4Weight()
+    w.q, w.ldq, w.scale, w.lds = q.data_ptr(), q.stride(0), scale.data_ptr(), scale.stride(0)
+    L.check(L.lib().cogv_gemm_rows_w4(C.byref(d), C.byref(w), _stream()), "cogv_gemm_rows_w4")
+    return out
+
+
 def _ln_prologue(z, gamma, beta, eps, z_absmax, post, residual, want_t):
     """(cogv_ln_prologue, t [M, K] or None) of gemv_ln / gemv_ln_w8; z and (post-LN form) gamma share the product's 16-bit type."""
     # fp32 residual stream (see sandwich_ln_fwd): the residual of the post-LN form, or z itself in the plain-input form

@@ -243,6 +243,25 @@ int cogv_gemm_rows(const cogv_gemm_desc* d, void* stream);
  * tiles): every load is requested at the top) }. */
 #define COGV_GEMM_ROWS_PLAN_INTS 10
 int cogv_gemm_rows_plan(const cogv_gemm_desc* d, int out[COGV_GEMM_ROWS_PLAN_INTS]);
+/* cogv_gemm_rows (F.linear at mpu/layers.py:243,319 and the tied logits model/gpt2_modeling.py:117 inside a decode step of 9 to 64
+ * rows) on an 8-bit weight: the operand of cogv_gemm_w8 in d->B / d->ldb's place (ignored), C[m][n] = epilogue(scale[n] * sum_k
+ * A[m][k] * e4m3(q[n][k])) with the bytes converted exactly and the scale multiplied into the finished fp32 sum once.  The
+ * arguments, limits, errors and guarantees of cogv_gemm_rows (1 <= M <= 64, 512 <= K <= 10240, K % 512 == 0, flags BIAS | GELU |
+ * ABSMAX; deterministic, a row's bits do not depend on the other rows, no floating-point atomics), and 1 for a NULL operand, q or
+ * scale not 16-byte aligned, ldq % 16 or ldq < K.  cogv_gemm_w8 keeps refusing M > 8: above 8 rows this is the entry point. */
+int cogv_gemm_rows_w8(const cogv_gemm_desc* d, const cogv_w8_weight* w, void* stream);
+/* cogv_gemm_rows (mpu/layers.py:243,319, model/gpt2_modeling.py:117 inside a decode step of 9 to 64 rows) on a 4-bit weight: the
+ * operand of cogv_gemm_w4, C[m][n] = epilogue(sum_k A[m][k] * code(q[n][k]) * 2^(scale[n][k / 32] - 127)), the block scale folded
+ * into the conversion as there.  As cogv_gemm_rows_w8; 1 for a NULL operand, q not 16-byte aligned, ldq % 16, ldq < K / 2 or
+ * lds < K / 32. */
+int cogv_gemm_rows_w4(const cogv_gemm_desc* d, const cogv_w4_weight* w, void* stream);
+/* cogv_gemm_rows_plan for the two calls above (the products of mpu/layers.py:243,319 and model/gpt2_modeling.py:117 on a quantized
+ * weight): host only, no device is touched and no pointer of d or w is dereferenced; the same 10 integers from the function the
+ * launches use (csrc/gemv_wide_plan.h, GWQ_CLASSES), exactly the error the launch would return.  A wave's unit of the contraction
+ * is 128 elements here (two 16-byte loads of E4M3 bytes, one of MXFP4 codes): out[3] counts 16-byte weight loads per lane as
+ * ever, out[9] the units a wave keeps in flight. */
+int cogv_gemm_rows_w8_plan(const cogv_gemm_desc* d, const cogv_w8_weight* w, int out[COGV_GEMM_ROWS_PLAN_INTS]);
+int cogv_gemm_rows_w4_plan(const cogv_gemm_desc* d, const cogv_w4_weight* w, int out[COGV_GEMM_ROWS_PLAN_INTS]);
 
 /* ------------------------------------------------------------------ Sandwich-LN
  * y = [residual +] LayerNorm_{eps*(amax/8)^2}(x) * gamma + beta ; amax = *absmax_in (NULL: plain LN).

@@ -7,7 +7,10 @@ of their logits on the step that was timed.  `--kv e4m3`: the same comparison fo
 skips the eager timing of the first decoder.  MB_DECODE_BATCH=b: b rows (up to 64).  From 9 rows on, three captured steps are timed
 in turn in this process, on the cache `--kv` names: the wide step (ops.gemm_rows), the step with the switch off (what
 COGV_DECODE_WIDE=0 runs: the tile kernels) and the 8-row step -- ms per step and per row of each, and the relative L2 / largest
-difference of the first two's logits on the timed step."""
+difference of the first two's logits on the timed step.  With `--weights F` a fourth step joins that alternation: the captured step
+on the quantized copies through the wide products (GraphDecoder(weights=F, wide=True)) -- its ms per step against the 16-bit wide
+step and the switch-off step of the same process, and its logits' difference from the 16-bit wide step's.  (The 8-row comparison
+of `--weights` below is for up to 8 rows and is skipped then.)"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 os.environ.setdefault("MASTER_ADDR", "127.0.0.1"); os.environ.setdefault("MASTER_PORT", "29589")
@@ -92,8 +95,8 @@ def _captured(d, wide):
     return d
 
 
-def _prefilled(batch, kv):
-    d = GraphDecoder(model, batch=batch, capacity=1152, kv=kv)
+def _prefilled(batch, kv, **more):
+    d = GraphDecoder(model, batch=batch, capacity=1152, kv=kv, **more)
     with torch.no_grad():
         d.prefill(tokens[:batch, :pre], pos[:batch, :pre])
     return d
@@ -127,8 +130,12 @@ if B >= 9:
     # (ops.workspace, regrown on demand) is baked into its graph -- a later prefill that needs a larger one (8 x 1024 rows: 252 MB
     # for the 4h -> h product) would replace the buffer under the captured graph.
     made = [_prefilled(B, KVFMT) if KVFMT is not None else dec, _prefilled(B, KVFMT), _prefilled(8, KVFMT)]
+    if WFMT is not None:
+        made.append(_prefilled(B, KVFMT, weights=WFMT, wide=True))
     legs = {"wide": _captured(made[0], True) if KVFMT is not None else dec, "COGV_DECODE_WIDE=0": _captured(made[1], False),
             "8 rows": _captured(made[2], True)}
+    if WFMT is not None:
+        legs[f"{WFMT} wide"] = _captured(made[3], True)
     del made
     with torch.no_grad():
         ms, last = _time_legs(legs)
@@ -140,6 +147,17 @@ if B >= 9:
     a, b = last["COGV_DECODE_WIDE=0"], last["wide"]
     print(f"logits wide vs COGV_DECODE_WIDE=0 on the timed step: rel-L2 {((b - a).norm() / a.norm()).item():.3e}, "
           f"max |difference| {(b - a).abs().max().item():.3e} (max |logit| {a.abs().max().item():.3f})", flush=True)
+    if WFMT is not None:
+        q, dq = min(ms[f"{WFMT} wide"]), legs[f"{WFMT} wide"]
+        q_bytes = sum(t.numel() * t.element_size() for t in dq.wq.tensors())
+        c = last[f"{WFMT} wide"]
+        print(f"captured graph, {B} rows, {cache}: {WFMT} wide step {q:.2f} ms (wide=True: gemm_rows_{'w4' if WFMT == 'mxfp4' else 'w8'}); 16-bit wide step "
+              f"{w:.2f} ms ({w / q:.2f}x); COGV_DECODE_WIDE=0 step {n:.2f} ms ({n / q:.2f}x); per row {q / B:.3f} ms; {WFMT} copies {q_bytes / 1e9:.2f} GB, "
+              f"{q_bytes / q / 1e9:.2f} TB/s (runs {['%.2f' % v for v in ms[f'{WFMT} wide']]})", flush=True)
+        print(f"logits {WFMT} wide vs 16-bit wide on the timed step: rel-L2 {((c - b).norm() / b.norm()).item():.3e}, "
+              f"max |difference| {(c - b).abs().max().item():.3e} (max |logit| {b.abs().max().item():.3f})", flush=True)
+        del dq, c
+        WFMT = None              # (the comparisons below build an 8-row-at-most quantized decoder)
     del legs, last
     torch.cuda.empty_cache()
 if WFMT is not None:
