@@ -41,6 +41,7 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const LT* logits, const int
 #pragma unroll
     for (int k = 1; k < 8; ++k) bm = fmaxf(bm, v[k]);
     if (bm > m) { s *= __expf(m - bm); m = bm; }
+    if (m == -INFINITY) continue;     // only -inf so far: the running sum is empty (-inf - -inf would make it NaN for good)
 #pragma unroll
     for (int k = 0; k < 8; ++k) s += __expf(v[k] - m);
   }

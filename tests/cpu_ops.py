@@ -116,6 +116,13 @@ def colsum(dy, out=None, accumulate=False):
     return out
 
 
+def colsum_finalize(partial, out, accumulate=False):
+    """cogv_colsum_finalize: out (+)= the sum of the fp32 partial rows [rows, N]."""
+    s = partial.float().sum(0)
+    out.copy_(s + out.float() if accumulate else s)
+    return out
+
+
 def sandwich_ln_fwd(x, gamma, beta, eps, absmax_in, residual=None, absmax_out=None, save_stats=True):
     h = x.shape[-1]
     xf = x.reshape(-1, h).float()
