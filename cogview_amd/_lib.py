@@ -323,33 +323,45 @@ def gemm_plan(descs, count=0, num_cus=0):
     return rc, [dict(zip(GEMM_PLAN_FIELDS, out[i * GEMM_PLAN_INTS:(i + 1) * GEMM_PLAN_INTS])) for i in range(n if rc == OK else 0)]
 
 
+def _stand_in_desc(dtype, M, N, K, ldb=None):
+    """the descriptor of a contiguous product for a plan query: the pointers are aligned stand-ins that nothing reads"""
+    d = GemmDesc()
+    d.dtype, d.M, d.N, d.K, d.lda, d.ldb, d.ldc, d.splitk = dtype, M, N, K, K, K if ldb is None else ldb, N, 1
+    d.A, d.B, d.C = 0x1000, 0x2000, 0x3000
+    return d
+
+
+def _stand_in_w8(K, ldq=None):
+    w = W8Weight()
+    w.q, w.ldq, w.scale = 0x2000, K if ldq is None else ldq, 0x4000
+    return w
+
+
+def _stand_in_w4(K, ldq=None, lds=None):
+    w = W4Weight()
+    w.q, w.ldq, w.scale, w.lds = 0x2000, K // 2 if ldq is None else ldq, 0x4000, K // 32 if lds is None else lds
+    return w
+
+
+def _plan_query(name, ints, *args):
+    """(error code, the `ints` integers a plan query wrote: all -1 where it refused) of lib().<name>(*args, out)"""
+    out = (C.c_int * ints)(*([-1] * ints))
+    rc = getattr(lib(), name)(*args, out)
+    return rc, list(out)
+
+
 def gemv_plan(kind, dtype, M, N, K, w8=False, nsplit=1, ldb=None):
     """cogv_gemv_plan for a contiguous product of `kind` (GEMV_*): (error code, [generation, form, J | NWK, KCMAX | LMAX, guarded,
     MT, tiles per workgroup, two halves, threads, workgroups, dynamic LDS bytes]).  Host only: the pointers in the descriptors
     are aligned stand-ins that nothing reads.  w8: the product on an E4M3 weight; ldb: elements (bytes) between its rows."""
-    d = GemmDesc()
-    d.dtype, d.M, d.N, d.K, d.lda, d.ldb, d.ldc, d.splitk = dtype, M, N, K, K, K if ldb is None else ldb, N, 1
-    d.A, d.B, d.C = 0x1000, 0x2000, 0x3000
-    w = None
-    if w8:
-        w = W8Weight()
-        w.q, w.ldq, w.scale = d.B, d.ldb, 0x4000
-    out = (C.c_int * GEMV_PLAN_INTS)(*([-1] * GEMV_PLAN_INTS))
-    rc = lib().cogv_gemv_plan(kind, C.byref(d), C.byref(w) if w8 else None, nsplit, out)
-    return rc, list(out)
+    d = _stand_in_desc(dtype, M, N, K, ldb)
+    return _plan_query("cogv_gemv_plan", GEMV_PLAN_INTS, kind, C.byref(d), C.byref(_stand_in_w8(K, d.ldb)) if w8 else None, nsplit)
 
 
 def gemv_w4_plan(kind, dtype, M, N, K, nsplit=1, ldq=None, lds=None):
     """cogv_gemv_w4_plan for a contiguous product of `kind` on an MXFP4 weight: (error code, the 11 integers of gemv_plan).  Host
     only.  ldq / lds: bytes between the rows of the codes (default K / 2) and of the block scales (default K / 32)."""
-    d = GemmDesc()
-    d.dtype, d.M, d.N, d.K, d.lda, d.ldb, d.ldc, d.splitk = dtype, M, N, K, K, K, N, 1
-    d.A, d.B, d.C = 0x1000, 0x2000, 0x3000
-    w = W4Weight()
-    w.q, w.ldq, w.scale, w.lds = 0x2000, K // 2 if ldq is None else ldq, 0x4000, K // 32 if lds is None else lds
-    out = (C.c_int * GEMV_PLAN_INTS)(*([-1] * GEMV_PLAN_INTS))
-    rc = lib().cogv_gemv_w4_plan(kind, C.byref(d), C.byref(w), nsplit, out)
-    return rc, list(out)
+    return _plan_query("cogv_gemv_w4_plan", GEMV_PLAN_INTS, kind, C.byref(_stand_in_desc(dtype, M, N, K)), C.byref(_stand_in_w4(K, ldq, lds)), nsplit)
 
 
 GEMM_ROWS_PLAN_INTS = 10
@@ -359,49 +371,26 @@ GEMM_ROWS_PLAN_FIELDS = ("row_groups", "waves_per_tile", "tiles", "weight_loads"
 def gemm_rows_plan(dtype, M, N, K, desc=None):
     """cogv_gemm_rows_plan for a contiguous product (or for the GemmDesc `desc` as it stands): (error code, the integers of
     GEMM_ROWS_PLAN_FIELDS; all -1 where the call is refused).  Host only: the pointers are aligned stand-ins that nothing reads."""
-    d = desc
-    if d is None:
-        d = GemmDesc()
-        d.dtype, d.M, d.N, d.K, d.lda, d.ldb, d.ldc, d.splitk = dtype, M, N, K, K, K, N, 1
-        d.A, d.B, d.C = 0x1000, 0x2000, 0x3000
-    out = (C.c_int * GEMM_ROWS_PLAN_INTS)(*([-1] * GEMM_ROWS_PLAN_INTS))
-    rc = lib().cogv_gemm_rows_plan(C.byref(d), out)
-    return rc, list(out)
-
-
-def _rows_q_desc(dtype, M, N, K, desc):
-    d = desc
-    if d is None:
-        d = GemmDesc()
-        d.dtype, d.M, d.N, d.K, d.lda, d.ldb, d.ldc, d.splitk = dtype, M, N, K, K, K, N, 1
-        d.A, d.B, d.C = 0x1000, 0x2000, 0x3000
-    return d
+    d = _stand_in_desc(dtype, M, N, K) if desc is None else desc
+    return _plan_query("cogv_gemm_rows_plan", GEMM_ROWS_PLAN_INTS, C.byref(d))
 
 
 def gemm_rows_w8_plan(dtype, M, N, K, ldq=None, desc=None, w=None):
     """cogv_gemm_rows_w8_plan for a contiguous product on an E4M3 weight (or for the GemmDesc `desc` / W8Weight `w` as they
     stand): (error code, the integers of GEMM_ROWS_PLAN_FIELDS; all -1 where the call is refused).  Host only.  ldq: bytes
     between the rows of the codes (default K)."""
-    d = _rows_q_desc(dtype, M, N, K, desc)
-    if w is None:
-        w = W8Weight()
-        w.q, w.ldq, w.scale = 0x2000, d.K if ldq is None else ldq, 0x4000
-    out = (C.c_int * GEMM_ROWS_PLAN_INTS)(*([-1] * GEMM_ROWS_PLAN_INTS))
-    rc = lib().cogv_gemm_rows_w8_plan(C.byref(d), C.byref(w), out)
-    return rc, list(out)
+    d = _stand_in_desc(dtype, M, N, K) if desc is None else desc
+    w = _stand_in_w8(d.K, ldq) if w is None else w
+    return _plan_query("cogv_gemm_rows_w8_plan", GEMM_ROWS_PLAN_INTS, C.byref(d), C.byref(w))
 
 
 def gemm_rows_w4_plan(dtype, M, N, K, ldq=None, lds=None, desc=None, w=None):
     """cogv_gemm_rows_w4_plan for a contiguous product on an MXFP4 weight (or for `desc` / the W4Weight `w` as they stand):
     (error code, the integers of GEMM_ROWS_PLAN_FIELDS; all -1 where the call is refused).  Host only.  ldq / lds: bytes between
     the rows of the codes (default K / 2) and of the block scales (default K / 32)."""
-    d = _rows_q_desc(dtype, M, N, K, desc)
-    if w is None:
-        w = W4Weight()
-        w.q, w.ldq, w.scale, w.lds = 0x2000, d.K // 2 if ldq is None else ldq, 0x4000, d.K // 32 if lds is None else lds
-    out = (C.c_int * GEMM_ROWS_PLAN_INTS)(*([-1] * GEMM_ROWS_PLAN_INTS))
-    rc = lib().cogv_gemm_rows_w4_plan(C.byref(d), C.byref(w), out)
-    return rc, list(out)
+    d = _stand_in_desc(dtype, M, N, K) if desc is None else desc
+    w = _stand_in_w4(d.K, ldq, lds) if w is None else w
+    return _plan_query("cogv_gemm_rows_w4_plan", GEMM_ROWS_PLAN_INTS, C.byref(d), C.byref(w))
 
 
 CONV_WGRAD_PLAN_INTS = 6

@@ -345,38 +345,21 @@ extern "C" int cogv_gemm(const cogv_gemm_desc* d, void* stream) {
   return launch_tiles(d->dtype, &pl, 1, env, ga, reinterpret_cast<hipStream_t>(stream));
 }
 
-// ---- the skinny-M products with a prologue, and all three on an 8-bit weight operand (gemv.hip, FormV / FormM on W8: it travels in
-//      the argument block as B / ldb / wscale; no first-generation kernel stands behind those)
+// ---- the skinny-M products with a prologue, and all three on a quantized weight operand (gemv.hip, FormV / FormM on W8 / W4: it
+//      travels in the argument block as B / ldb and its scales, weight_operand.h; no first-generation kernel stands behind those)
 
-// the descriptor with the 8-bit operand in B's place -> argument block; `allowed`: the epilogue flags the product takes
-static int build_w8_args(const cogv_gemm_desc* d, const cogv_w8_weight* w, int allowed, bool has_a, GemmArgs& a) {
-  if (!d || !w || !w->q || !w->scale) return COGV_ERR_ARG;
+// the descriptor with the quantized operand in B's place -> argument block; `allowed`: the epilogue flags the product takes
+static int build_q_args(const cogv_gemm_desc* d, const WeightOperand& w, int allowed, bool has_a, GemmArgs& a) {
+  if (!d || weight_operand_null(w)) return COGV_ERR_ARG;
   if (d->M > GEMV_MAX_M || (d->N & 7) || (d->K & 511) || d->trans_a || d->trans_b || (d->flags & ~allowed) || d->out_f32 || d->splitk > 1)
     return COGV_ERR_UNSUPPORTED;
-  if ((w->ldq & 15) || (((uintptr_t)w->q | (uintptr_t)w->scale) & 15)) return COGV_ERR_ARG;
+  if (weight_operand_misplaced(w, d->K)) return COGV_ERR_ARG;
   cogv_gemm_desc dd = *d;
-  dd.B = w->q; dd.ldb = w->ldq;
+  dd.B = w.q; dd.ldb = w.ldq;
   if (!has_a) { dd.A = dd.B; dd.lda = dd.K; }          // (no A operand: keep build_gemm_args' pointer checks happy)
   const int rc = build_gemm_args(&dd, a);
-  if (rc != COGV_OK) return rc;
-  a.wscale = w->scale;
-  return COGV_OK;
-}
-
-// the same with the 4-bit operand (MXFP4 codes and block scales: B / ldb / bscale / ldbs of the argument block)
-static int build_w4_args(const cogv_gemm_desc* d, const cogv_w4_weight* w, int allowed, bool has_a, GemmArgs& a) {
-  if (!d || !w || !w->q || !w->scale) return COGV_ERR_ARG;
-  if (d->M > GEMV_MAX_M || (d->N & 7) || (d->K & 511) || d->trans_a || d->trans_b || (d->flags & ~allowed) || d->out_f32 || d->splitk > 1)
-    return COGV_ERR_UNSUPPORTED;
-  if ((w->ldq & 15) || ((uintptr_t)w->q & 15) || w->lds < d->K / 32) return COGV_ERR_ARG;
-  cogv_gemm_desc dd = *d;
-  dd.B = w->q; dd.ldb = w->ldq;
-  if (!has_a) { dd.A = dd.B; dd.lda = dd.K; }          // (no A operand: keep build_gemm_args' pointer checks happy)
-  const int rc = build_gemm_args(&dd, a);
-  if (rc != COGV_OK) return rc;
-  a.bscale = reinterpret_cast<const uint8_t*>(w->scale);
-  a.ldbs = w->lds;
-  return COGV_OK;
+  if (rc == COGV_OK) weight_operand_put(w, a);
+  return rc;
 }
 
 static int gemv_ln_args(const cogv_ln_prologue* ln, GemvLnArgs& a) {
@@ -389,18 +372,20 @@ static int gemv_ln_args(const cogv_ln_prologue* ln, GemvLnArgs& a) {
   return COGV_OK;
 }
 
-// Descriptor of a product of `kind` (w: its 8-bit weight, or NULL) -> argument block and launch plan, or the entry point's
-// error: the front of cogv_gemv_ln, cogv_gemv_attn, the three _w8 and the three _w4 calls and the two plan queries (cogv_gemm's
-// is gemm_front).  w4: the 4-bit weight (w is NULL then).
-static int gemv_front(int kind, const cogv_gemm_desc* d, const cogv_w8_weight* w, int nsplit, GemmArgs& a, GvPlan& pl,
-                      const cogv_ln_prologue* ln = nullptr, GemvLnArgs* la = nullptr, const cogv_w4_weight* w4 = nullptr) {
+// Descriptor of a product of `kind` (w: its quantized weight, or NULL: 16-bit weights in d->B) -> argument block and launch plan,
+// or the entry point's error: the front of cogv_gemv_ln, cogv_gemv_attn, the three _w8 and the three _w4 calls and the two plan
+// queries (cogv_gemm's is gemm_front).
+// The order of the checks on a quantized operand, which callers rely on (tests/test_weight_operand_cpu.py has it as a table): a
+// NULL descriptor, operand, q or scale (1); M, N, K % 512, the layout, the flags, out_f32, splitk (3); the operand's alignment,
+// ldq % 16 and the block scales' lds (1); build_gemm_args (1 | 3); aux on the plain and the LayerNorm kind (3); gv_shape_taken (3);
+// the prologue (1: a bad prologue is reported before a class's refusal); the plan (3) -- which is where an ldq shorter than a row of
+// K ends up, since gv_plan refuses it.  The wide front (gemv_wide.hip, gw_front) judges the whole operand BEFORE the descriptor
+// and answers 1 for a short ldq.
+static int gemv_front(int kind, const cogv_gemm_desc* d, const WeightOperand* w, int nsplit, GemmArgs& a, GvPlan& pl,
+                      const cogv_ln_prologue* ln = nullptr, GemvLnArgs* la = nullptr) {
   int rc;
-  if (w4) {
-    rc = build_w4_args(d, w4, COGV_EPI_BIAS | COGV_EPI_ABSMAX | (kind == GV_ATTN ? 0 : COGV_EPI_GELU), kind == GV_PLAIN, a);
-    if (rc == COGV_OK && kind != GV_ATTN && d->aux) rc = COGV_ERR_UNSUPPORTED;
-  }
-  else if (w) {
-    rc = build_w8_args(d, w, COGV_EPI_BIAS | COGV_EPI_ABSMAX | (kind == GV_ATTN ? 0 : COGV_EPI_GELU), kind == GV_PLAIN, a);
+  if (w) {
+    rc = build_q_args(d, *w, COGV_EPI_BIAS | COGV_EPI_ABSMAX | (kind == GV_ATTN ? 0 : COGV_EPI_GELU), kind == GV_PLAIN, a);
     if (rc == COGV_OK && kind != GV_ATTN && d->aux) rc = COGV_ERR_UNSUPPORTED;
   }
   else if (!d) rc = COGV_ERR_ARG;
@@ -413,81 +398,78 @@ static int gemv_front(int kind, const cogv_gemm_desc* d, const cogv_w8_weight* w
   if (rc != COGV_OK) return rc;
   a.splitk = 1;
   if (!gv_shape_taken(kind, a.M, a.N, a.K)) return COGV_ERR_UNSUPPORTED;
-  if (ln && (rc = gemv_ln_args(ln, *la)) != COGV_OK) return rc;             // (a bad prologue is reported before a class's refusal)
-  return gv_plan(kind, w4 ? GV_W4 : w ? GV_W8 : GV_W16, a.M, a.N, a.K, a.ldb, nsplit, pl) ? COGV_OK : COGV_ERR_UNSUPPORTED;
+  if (ln && (rc = gemv_ln_args(ln, *la)) != COGV_OK) return rc;
+  return gv_plan(kind, weight_format(w), a.M, a.N, a.K, a.ldb, nsplit, pl) ? COGV_OK : COGV_ERR_UNSUPPORTED;
 }
 
+// The entry points below turn their ABI operand into a WeightOperand (weight_operand: NULL stays NULL).  A _w8 / _w4 call without
+// its operand is a bad argument; cogv_gemv_plan without one is the 16-bit query.
+
 // y = epilogue(LN_pre([res + LN_post(z)]) . B^T): the decode step's GEMV with its LayerNorms as prologue
-static int gemv_ln(const cogv_gemm_desc* d, const cogv_ln_prologue* ln, const cogv_w8_weight* w, void* stream, const cogv_w4_weight* w4 = nullptr) {
+static int gemv_ln(const cogv_gemm_desc* d, const cogv_ln_prologue* ln, const WeightOperand* w, void* stream) {
   if (!ln) return COGV_ERR_ARG;
   GemvLnArgs a;
   GvPlan pl;
-  const int rc = gemv_front(GV_LN, d, w, 0, a.g, pl, ln, &a, w4);
+  const int rc = gemv_front(GV_LN, d, w, 0, a.g, pl, ln, &a);
   if (rc != COGV_OK) return rc;
-  return gemv_launch(GV_LN, w4 ? GV_W4 : w ? GV_W8 : GV_W16, d->dtype, pl, GvCall{&a, nullptr, 0, 0, ln->stream_f32 != 0, stream});
+  return gemv_launch(GV_LN, weight_format(w), d->dtype, pl, GvCall{&a, nullptr, 0, 0, ln->stream_f32 != 0, stream});
 }
 extern "C" int cogv_gemv_ln(const cogv_gemm_desc* d, const cogv_ln_prologue* ln, void* stream) { return gemv_ln(d, ln, nullptr, stream); }
 extern "C" int cogv_gemv_ln_w8(const cogv_gemm_desc* d, const cogv_ln_prologue* ln, const cogv_w8_weight* w, void* stream) {
-  return w ? gemv_ln(d, ln, w, stream) : COGV_ERR_ARG;
+  WeightOperand o; return w ? gemv_ln(d, ln, weight_operand(w, o), stream) : COGV_ERR_ARG;
 }
 extern "C" int cogv_gemv_ln_w4(const cogv_gemm_desc* d, const cogv_ln_prologue* ln, const cogv_w4_weight* w, void* stream) {
-  return w ? gemv_ln(d, ln, nullptr, stream, w) : COGV_ERR_ARG;
+  WeightOperand o; return w ? gemv_ln(d, ln, weight_operand(w, o), stream) : COGV_ERR_ARG;
 }
 
 // y = epilogue(att . B^T), att = the combination of cogv_attention_decode's split partials (skip_combine form)
-static int gemv_attn(const cogv_gemm_desc* d, const cogv_w8_weight* w, const void* partials, int heads, int capacity, void* stream,
-                     const cogv_w4_weight* w4 = nullptr) {
+static int gemv_attn(const cogv_gemm_desc* d, const WeightOperand* w, const void* partials, int heads, int capacity, void* stream) {
   if (!partials || heads <= 0 || capacity <= 0 || capacity > 4096 || ((uintptr_t)partials & 15)) return COGV_ERR_ARG;
   const int nsplit = (capacity + 127) / 128;
   GemmArgs a;
   GvPlan pl;
-  const int rc = gemv_front(GV_ATTN, d, w, nsplit, a, pl, nullptr, nullptr, w4);
+  const int rc = gemv_front(GV_ATTN, d, w, nsplit, a, pl);
   if (rc != COGV_OK) return rc;
   if (a.K != heads * 64) return COGV_ERR_UNSUPPORTED;
-  return gemv_launch(GV_ATTN, w4 ? GV_W4 : w ? GV_W8 : GV_W16, d->dtype, pl, GvCall{&a, reinterpret_cast<const float*>(partials), heads, nsplit, 0, stream});
+  return gemv_launch(GV_ATTN, weight_format(w), d->dtype, pl, GvCall{&a, reinterpret_cast<const float*>(partials), heads, nsplit, 0, stream});
 }
 extern "C" int cogv_gemv_attn(const cogv_gemm_desc* d, const void* partials, int heads, int capacity, void* stream) {
   return gemv_attn(d, nullptr, partials, heads, capacity, stream);
 }
 extern "C" int cogv_gemv_attn_w8(const cogv_gemm_desc* d, const cogv_w8_weight* w, const void* partials, int heads, int capacity, void* stream) {
-  return w ? gemv_attn(d, w, partials, heads, capacity, stream) : COGV_ERR_ARG;
+  WeightOperand o; return w ? gemv_attn(d, weight_operand(w, o), partials, heads, capacity, stream) : COGV_ERR_ARG;
 }
 extern "C" int cogv_gemv_attn_w4(const cogv_gemm_desc* d, const cogv_w4_weight* w, const void* partials, int heads, int capacity, void* stream) {
-  return w ? gemv_attn(d, nullptr, partials, heads, capacity, stream, w) : COGV_ERR_ARG;
+  WeightOperand o; return w ? gemv_attn(d, weight_operand(w, o), partials, heads, capacity, stream) : COGV_ERR_ARG;
 }
 
-extern "C" int cogv_gemm_w8(const cogv_gemm_desc* d, const cogv_w8_weight* w, void* stream) {
+// cogv_gemm's skinny case on a quantized weight
+static int gemm_q(const cogv_gemm_desc* d, const WeightOperand* w, void* stream) {
   if (!w) return COGV_ERR_ARG;
   GemmArgs a;
   GvPlan pl;
   const int rc = gemv_front(GV_PLAIN, d, w, 0, a, pl);
-  return rc != COGV_OK ? rc : gemv_launch(GV_PLAIN, GV_W8, d->dtype, pl, GvCall{&a, nullptr, 0, 0, 0, stream});
+  return rc != COGV_OK ? rc : gemv_launch(GV_PLAIN, w->fmt, d->dtype, pl, GvCall{&a, nullptr, 0, 0, 0, stream});
 }
-
-extern "C" int cogv_gemm_w4(const cogv_gemm_desc* d, const cogv_w4_weight* w, void* stream) {
-  if (!w) return COGV_ERR_ARG;
-  GemmArgs a;
-  GvPlan pl;
-  const int rc = gemv_front(GV_PLAIN, d, nullptr, 0, a, pl, nullptr, nullptr, w);
-  return rc != COGV_OK ? rc : gemv_launch(GV_PLAIN, GV_W4, d->dtype, pl, GvCall{&a, nullptr, 0, 0, 0, stream});
-}
+extern "C" int cogv_gemm_w8(const cogv_gemm_desc* d, const cogv_w8_weight* w, void* stream) { WeightOperand o; return gemm_q(d, weight_operand(w, o), stream); }
+extern "C" int cogv_gemm_w4(const cogv_gemm_desc* d, const cogv_w4_weight* w, void* stream) { WeightOperand o; return gemm_q(d, weight_operand(w, o), stream); }
 
 // host-only: the plan the entry points above (and cogv_gemm's skinny case) would launch with
-static int gemv_plan_query(int kind, const cogv_gemm_desc* d, const cogv_w8_weight* w, const cogv_w4_weight* w4, int nsplit, int* out) {
+static int gemv_plan_query(int kind, const cogv_gemm_desc* d, const WeightOperand* w, int nsplit, int* out) {
   if (!out || kind < COGV_GEMV_PLAIN || kind > COGV_GEMV_LN || (kind == COGV_GEMV_ATTN && nsplit < 1)) return COGV_ERR_ARG;
   GemmArgs a;
   GvPlan pl;
-  const int rc = gemv_front(1 << kind, d, w, nsplit, a, pl, nullptr, nullptr, w4);
+  const int rc = gemv_front(1 << kind, d, w, nsplit, a, pl);
   if (rc != COGV_OK) return rc;
   const int v[COGV_GEMV_PLAN_INTS] = {pl.generation, pl.form, pl.p0, pl.p1, pl.guard, pl.mt, pl.tw, pl.k2, pl.threads, pl.grid, pl.lds};
   for (int i = 0; i < COGV_GEMV_PLAN_INTS; ++i) out[i] = v[i];
   return COGV_OK;
 }
 extern "C" int cogv_gemv_plan(int kind, const cogv_gemm_desc* d, const cogv_w8_weight* w, int nsplit, int out[COGV_GEMV_PLAN_INTS]) {
-  return gemv_plan_query(kind, d, w, nullptr, nsplit, out);
+  WeightOperand o; return gemv_plan_query(kind, d, weight_operand(w, o), nsplit, out);
 }
 extern "C" int cogv_gemv_w4_plan(int kind, const cogv_gemm_desc* d, const cogv_w4_weight* w, int nsplit, int out[COGV_GEMV_PLAN_INTS]) {
-  return w ? gemv_plan_query(kind, d, nullptr, w, nsplit, out) : COGV_ERR_ARG;
+  WeightOperand o; return w ? gemv_plan_query(kind, d, weight_operand(w, o), nsplit, out) : COGV_ERR_ARG;
 }
 
 // Several GEMMs of the same dtype and layout in one persistent launch of the generation-4 kernel (see GroupArgs).

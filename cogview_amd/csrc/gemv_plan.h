@@ -5,8 +5,9 @@
 #pragma once
 #include <cstdlib>
 
+#include "weight_operand.h"                                      // the weight formats GV_W16 | GV_W8 | GV_W4
+
 enum { GV_PLAIN = 1, GV_ATTN = 2, GV_LN = 4, GV_ALL = 7 };       // kind (bits: a class row names the kinds that take it)
-enum { GV_W16 = 0, GV_W8 = 1, GV_W4 = 2 };                       // weight format: the dtype's 16 bits | E4M3 bytes + row scales | MXFP4 blocks
 enum { GV_FORM_V = 0, GV_FORM_M = 1 };                           // FormV: one row, vector ALU | FormM: 2 .. 8 rows, MFMA (either weight operand)
 
 // The classes.  A product of MT rows (1 | 2, 4, 8: the row count rounded up) takes the FIRST row of its format whose form
@@ -120,7 +121,7 @@ inline bool gv_shape_taken(int kind, int M, int N, int K) {
 inline bool gv_plan(int kind, int fmt, int M, int N, int K, int ldb, int nsplit, GvPlan& pl) {
   if (!gv_shape_taken(kind, M, N, K)) return false;
   const int mt = gv_mt(M);
-  const bool gen2 = fmt == GV_W8 ? ldb >= K : fmt == GV_W4 ? ldb >= K / 2 : gv_gen2_enabled();
+  const bool gen2 = fmt == GV_W16 ? gv_gen2_enabled() : ldb >= weight_row(fmt, K);
   if (gen2 && !(kind == GV_ATTN && nsplit > GV_MAX_NSPLIT))
     for (int i = 0; i < GVC_COUNT; ++i) {
       const GvClass& c = GV_CLASS_TABLE[i];

@@ -206,13 +206,13 @@ using WT = W4<TT>;
 #define GW_UNIT_CLASSES GWQ_CLASSES
 #define GW_CLS(NAME) GWQC_##NAME
 #define GW_RUN GW_CAT(cogv_gemv_wide_w4_run_, COGV_GEMV_WIDE_TU)
-constexpr int gw_unit_depth(int, int rg, int ct, int lp) { return gwq_depth(GW_W4, rg, ct, lp); }
+constexpr int gw_unit_depth(int, int rg, int ct, int lp) { return gwq_depth(GV_W4, rg, ct, lp); }
 #elif defined(COGV_GEMV_WIDE_W8)
 using WT = W8<TT>;
 #define GW_UNIT_CLASSES GWQ_CLASSES
 #define GW_CLS(NAME) GWQC_##NAME
 #define GW_RUN GW_CAT(cogv_gemv_wide_w8_run_, COGV_GEMV_WIDE_TU)
-constexpr int gw_unit_depth(int, int rg, int ct, int lp) { return gwq_depth(GW_W8, rg, ct, lp); }
+constexpr int gw_unit_depth(int, int rg, int ct, int lp) { return gwq_depth(GV_W8, rg, ct, lp); }
 #else
 using WT = W16<TT>;
 #define GW_UNIT_CLASSES GW_CLASSES
@@ -261,59 +261,60 @@ namespace {
 
 // Descriptor -> argument block and launch plan, or the call's error: bad arguments (1) as cogv_gemm reports them, then what this
 // kernel does not take (3).  Nothing a pointer points to is read.
-// fmt: what B holds.  A quantized operand has taken the place of d->B / d->ldb (bytes) before this is called.
-int gw_front(const cogv_gemm_desc* d, GemmArgs& a, GwPlan& pl, int fmt = GW_W16) {
+// w: the quantized operand that takes the place of d->B / d->ldb, or NULL: 16-bit weights there.
+// The whole operand is judged BEFORE the descriptor -- NULL q or scale, alignment, ldq % 16, and with block scales K <= 0 and lds <
+// K / 32 are bad arguments (1) whatever the shape says -- and an ldq shorter than a row of K is one too, with lda and ldc.  (The
+// skinny front, gemm.hip's gemv_front, asks the shape between the operand's NULLs and its alignment, and leaves a short ldq to
+// its plan: 3.)
+int gw_front(const cogv_gemm_desc* d, const WeightOperand* w, GemmArgs& a, GwPlan& pl) {
   if (!d) return COGV_ERR_ARG;
+  if (w && (weight_operand_null(*w) || (WEIGHT_FORMATS[w->fmt].block_scales && d->K <= 0) || weight_operand_misplaced(*w, d->K))) return COGV_ERR_ARG;
+  const WeightOperand b = w ? *w : WeightOperand{GV_W16, d->B, d->ldb, nullptr, 0};
   if (d->dtype != COGV_F16 && d->dtype != COGV_BF16) return COGV_ERR_UNSUPPORTED;
   if (d->M <= 0 || d->N <= 0 || d->K <= 0) return COGV_ERR_ARG;
-  if ((d->N & 7) || (d->ldc & 7) || (d->lda & 7) || (d->ldb & 7) || (d->K & 7)) return COGV_ERR_ARG;
-  if (((uintptr_t)d->A | (uintptr_t)d->B | (uintptr_t)d->C) & 15) return COGV_ERR_ARG;
-  if (!d->A || !d->B || !d->C) return COGV_ERR_ARG;
+  if ((d->N & 7) || (d->ldc & 7) || (d->lda & 7) || (b.ldq & 7) || (d->K & 7)) return COGV_ERR_ARG;
+  if (((uintptr_t)d->A | (uintptr_t)b.q | (uintptr_t)d->C) & 15) return COGV_ERR_ARG;
+  if (!d->A || !b.q || !d->C) return COGV_ERR_ARG;
   if ((d->flags & COGV_EPI_BIAS) && (!d->bias || ((uintptr_t)d->bias & 15))) return COGV_ERR_ARG;
   if ((d->flags & COGV_EPI_ABSMAX) && !d->absmax) return COGV_ERR_ARG;
   if (d->trans_a || d->trans_b || (d->flags & ~(COGV_EPI_BIAS | COGV_EPI_GELU | COGV_EPI_ABSMAX)) || d->out_f32 || d->splitk > 1 ||
       d->kernel_variant != 0 || d->aux)
     return COGV_ERR_UNSUPPORTED;
-  if (d->lda < d->K || d->ldb < (fmt == GW_W4 ? d->K / 2 : d->K) || d->ldc < d->N) return COGV_ERR_ARG;
-  if (!(fmt == GW_W16 ? gw_plan(d->M, d->N, d->K, pl) : gwq_plan(fmt, d->M, d->N, d->K, pl))) return COGV_ERR_UNSUPPORTED;
+  if (d->lda < d->K || b.ldq < weight_row(b.fmt, d->K) || d->ldc < d->N) return COGV_ERR_ARG;
+  if (!gw_plan(b.fmt, d->M, d->N, d->K, pl)) return COGV_ERR_UNSUPPORTED;
   a = GemmArgs{};
-  a.A = d->A; a.B = d->B; a.C = d->C;
+  a.A = d->A; a.C = d->C;
   a.M = d->M; a.N = d->N; a.K = d->K;
-  a.lda = d->lda; a.ldb = d->ldb; a.ldc = d->ldc;
+  a.lda = d->lda; a.ldc = d->ldc;
   a.bias = d->bias; a.absmax = d->absmax;
   a.flags = d->flags;
   a.keep_scale = 1.0f;
   a.splitk = 1;
+  weight_operand_put(b, a);
   return COGV_OK;
 }
 
-// The fronts of the quantized products: the operand checks of cogv_gemm_w8 / cogv_gemm_w4 (a NULL or misaligned operand, ldq % 16,
-// lds < K / 32: bad argument), then gw_front with the operand in B's place.
-int gw_front_w8(const cogv_gemm_desc* d, const cogv_w8_weight* w, GemmArgs& a, GwPlan& pl) {
-  if (!d || !w || !w->q || !w->scale) return COGV_ERR_ARG;
-  if ((w->ldq & 15) || (((uintptr_t)w->q | (uintptr_t)w->scale) & 15)) return COGV_ERR_ARG;
-  cogv_gemm_desc dd = *d;
-  dd.B = w->q; dd.ldb = w->ldq;
-  const int rc = gw_front(&dd, a, pl, GW_W8);
+// the launch of a product, by the operand's format and the dtype
+int gw_run(const cogv_gemm_desc* d, const WeightOperand* w, void* stream) {
+  static int (*const RUN[3][2])(const GwPlan*, const void*, void*) = {{cogv_gemv_wide_run_0, cogv_gemv_wide_run_1},
+                                                                      {cogv_gemv_wide_w8_run_0, cogv_gemv_wide_w8_run_1},
+                                                                      {cogv_gemv_wide_w4_run_0, cogv_gemv_wide_w4_run_1}};
+  GemmArgs a;
+  GwPlan pl;
+  const int rc = gw_front(d, w, a, pl);
   if (rc != COGV_OK) return rc;
-  a.wscale = w->scale;
-  return COGV_OK;
+  const int rr = RUN[weight_format(w)][d->dtype == COGV_F16](&pl, &a, stream);
+  return rr != COGV_OK ? rr : cogv_check_launch();
 }
 
-int gw_front_w4(const cogv_gemm_desc* d, const cogv_w4_weight* w, GemmArgs& a, GwPlan& pl) {
-  if (!d || !w || !w->q || !w->scale) return COGV_ERR_ARG;
-  if ((w->ldq & 15) || ((uintptr_t)w->q & 15) || d->K <= 0 || w->lds < d->K / 32) return COGV_ERR_ARG;
-  cogv_gemm_desc dd = *d;
-  dd.B = w->q; dd.ldb = w->ldq;
-  const int rc = gw_front(&dd, a, pl, GW_W4);
+// host-only: the plan that launch would use
+int gw_query(const cogv_gemm_desc* d, const WeightOperand* w, int* out) {
+  if (!out) return COGV_ERR_ARG;
+  GemmArgs a;
+  GwPlan pl;
+  const int rc = gw_front(d, w, a, pl);
   if (rc != COGV_OK) return rc;
-  a.bscale = reinterpret_cast<const uint8_t*>(w->scale);
-  a.ldbs = w->lds;
-  return COGV_OK;
-}
-
-int gw_plan_out(int rc, const GwPlan& pl, int loads, int* out) {
-  if (rc != COGV_OK) return rc;
+  const int loads = GW_FORMATS[weight_format(w)].loads;
   const int v[COGV_GEMM_ROWS_PLAN_INTS] = {pl.rg, pl.nwk, pl.ct, loads * pl.lp * pl.ct, pl.guard, 0, pl.threads, pl.grid, pl.lds, pl.depth};
   for (int i = 0; i < COGV_GEMM_ROWS_PLAN_INTS; ++i) out[i] = v[i];
   return COGV_OK;
@@ -321,52 +322,20 @@ int gw_plan_out(int rc, const GwPlan& pl, int loads, int* out) {
 
 }  // namespace
 
+// (a _w8 / _w4 call without its operand is a bad argument; to gw_front a NULL operand means 16-bit weights)
+extern "C" int cogv_gemm_rows(const cogv_gemm_desc* d, void* stream) { return gw_run(d, nullptr, stream); }
 extern "C" int cogv_gemm_rows_w8(const cogv_gemm_desc* d, const cogv_w8_weight* w, void* stream) {
-  GemmArgs a;
-  GwPlan pl;
-  const int rc = gw_front_w8(d, w, a, pl);
-  if (rc != COGV_OK) return rc;
-  const int rr = d->dtype == COGV_F16 ? cogv_gemv_wide_w8_run_1(&pl, &a, stream) : cogv_gemv_wide_w8_run_0(&pl, &a, stream);
-  return rr != COGV_OK ? rr : cogv_check_launch();
+  WeightOperand o; return w ? gw_run(d, weight_operand(w, o), stream) : COGV_ERR_ARG;
 }
-
 extern "C" int cogv_gemm_rows_w4(const cogv_gemm_desc* d, const cogv_w4_weight* w, void* stream) {
-  GemmArgs a;
-  GwPlan pl;
-  const int rc = gw_front_w4(d, w, a, pl);
-  if (rc != COGV_OK) return rc;
-  const int rr = d->dtype == COGV_F16 ? cogv_gemv_wide_w4_run_1(&pl, &a, stream) : cogv_gemv_wide_w4_run_0(&pl, &a, stream);
-  return rr != COGV_OK ? rr : cogv_check_launch();
+  WeightOperand o; return w ? gw_run(d, weight_operand(w, o), stream) : COGV_ERR_ARG;
 }
-
+extern "C" int cogv_gemm_rows_plan(const cogv_gemm_desc* d, int out[COGV_GEMM_ROWS_PLAN_INTS]) { return gw_query(d, nullptr, out); }
 extern "C" int cogv_gemm_rows_w8_plan(const cogv_gemm_desc* d, const cogv_w8_weight* w, int out[COGV_GEMM_ROWS_PLAN_INTS]) {
-  if (!out) return COGV_ERR_ARG;
-  GemmArgs a;
-  GwPlan pl;
-  return gw_plan_out(gw_front_w8(d, w, a, pl), pl, gwq_loads(GW_W8), out);
+  WeightOperand o; return w ? gw_query(d, weight_operand(w, o), out) : COGV_ERR_ARG;
 }
-
 extern "C" int cogv_gemm_rows_w4_plan(const cogv_gemm_desc* d, const cogv_w4_weight* w, int out[COGV_GEMM_ROWS_PLAN_INTS]) {
-  if (!out) return COGV_ERR_ARG;
-  GemmArgs a;
-  GwPlan pl;
-  return gw_plan_out(gw_front_w4(d, w, a, pl), pl, gwq_loads(GW_W4), out);
-}
-
-extern "C" int cogv_gemm_rows(const cogv_gemm_desc* d, void* stream) {
-  GemmArgs a;
-  GwPlan pl;
-  const int rc = gw_front(d, a, pl);
-  if (rc != COGV_OK) return rc;
-  const int rr = d->dtype == COGV_F16 ? cogv_gemv_wide_run_1(&pl, &a, stream) : cogv_gemv_wide_run_0(&pl, &a, stream);
-  return rr != COGV_OK ? rr : cogv_check_launch();
-}
-
-extern "C" int cogv_gemm_rows_plan(const cogv_gemm_desc* d, int out[COGV_GEMM_ROWS_PLAN_INTS]) {
-  if (!out) return COGV_ERR_ARG;
-  GemmArgs a;
-  GwPlan pl;
-  return gw_plan_out(gw_front(d, a, pl), pl, 2, out);
+  WeightOperand o; return w ? gw_query(d, weight_operand(w, o), out) : COGV_ERR_ARG;
 }
 
 #endif  // COGV_GEMV_WIDE_TU

@@ -2,6 +2,7 @@
 // csrc/gemv_wide.hip's kernel.  Host code only.  cogv_gemm_rows asks gw_plan() before its launch, cogv_gemm_rows_plan answers from
 // the same function, and a unit of gemv_wide.hip turns the plan into its template instantiation by expanding the same list.
 #pragma once
+#include "weight_operand.h"      // the weight formats GV_W16 | GV_W8 | GV_W4
 
 // The classes.  A product takes the FIRST row whose K range holds K: the class depends on K ALONE, so the association of a
 // column's sum -- which contraction slots a wave adds up, and the order the waves' partial tiles are summed in -- does not depend
@@ -37,7 +38,7 @@ constexpr int GW_MAX_M = 64, GW_MIN_K = 512, GW_MAX_K = 10240;
 // and logits products of the model family; their N = h products keep one tile and N / 16 workgroups).
 constexpr int GW_CT2_MIN_N = 4096;
 constexpr int gw_rg(int M) { return (M + 15) / 16; }
-constexpr int gw_ct(int rg, int N) { return rg >= 2 && N >= GW_CT2_MIN_N ? 2 : 1; }
+constexpr int gw_ct(int rg, int N, int ct2_min_n = GW_CT2_MIN_N) { return rg >= 2 && N >= ct2_min_n ? 2 : 1; }
 // Load pairs a wave keeps in flight.  A pair is 2 * (RG + CT) loads of 16 bytes per lane = 8 (RG + CT) registers; a wave of a
 // 16-wave workgroup has 128 registers, of an 8- or 4-wave one 256 (two workgroups of 4 waves per CU).  What is left after the
 // RG * CT accumulators of 4 registers and 40 for addresses and the epilogue goes to the ring, up to all LP pairs (then every load
@@ -55,21 +56,8 @@ constexpr int gw_round(int nwk, int tiles) {
 }
 constexpr int gw_lds(int nwk, int tiles) { return gw_round(nwk, tiles) * (nwk + 1) * 1024; }
 
-// The plan of one launch: cls and (rg, ct) name the instantiation.
+// The plan of one launch: cls and (rg, ct) name the instantiation.  gw_plan(), below the quantized classes, makes it.
 struct GwPlan { int rg, nwk, ct, lp, guard, depth, threads, grid, lds, cls; };
-
-// false: the wide kernel does not take the product (unsupported)
-inline bool gw_plan(int M, int N, int K, GwPlan& pl) {
-  if (M < 1 || M > GW_MAX_M || N < 8 || (N & 7) || K < GW_MIN_K || K > GW_MAX_K || (K & 511)) return false;
-  for (int i = 0; i < GWC_COUNT; ++i) {
-    const GwClass& c = GW_CLASS_TABLE[i];
-    if (K < c.k_from || K > c.k_to) continue;
-    const int rg = gw_rg(M), ct = gw_ct(rg, N), cols = 16 * ct;
-    pl = GwPlan{rg, c.nwk, ct, c.lp, c.guard, gw_depth(c.nwk, rg, ct, c.lp), 64 * c.nwk, (N + cols - 1) / cols, gw_lds(c.nwk, rg * ct), i};
-    return true;
-  }
-  return false;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // The same kernel on the quantized weight operands of gemv_operand.cuh (cogv_gemm_rows_w8: E4M3 bytes and a row scale,
@@ -96,35 +84,46 @@ enum GwqClassId { GWQ_CLASSES(GWQ_ENUM_ROW) GWQC_COUNT };
 constexpr GwClass GWQ_CLASS_TABLE[GWQC_COUNT] = {GWQ_CLASSES(GW_ROW)};
 #undef GW_ROW
 
-enum GwFormat { GW_W16 = 0, GW_W8 = 1, GW_W4 = 2 };
 // Two column tiles from 2 row groups on where N reaches this bound: the 16-bit rule (GW_CT2_MIN_N) unless an A/B build says
 // otherwise (tools/mb_gemm_rows_q.py; DESIGN 4.5.8 has the measurement that keeps it).
 #ifndef GWQ_CT2_MIN_N
 #define GWQ_CT2_MIN_N GW_CT2_MIN_N
 #endif
-constexpr int gwq_ct(int rg, int N) { return rg >= 2 && N >= GWQ_CT2_MIN_N ? 2 : 1; }
 constexpr int GWQ_UNIT = 128;                                         // contraction elements of a unit
-constexpr int gwq_loads(int fmt) { return fmt == GW_W4 ? 1 : 2; }     // 16-byte weight loads of a lane per unit and column tile
 // x bytes a workgroup requests from L2 per weight byte: 4 fragments of 16 bytes per row group against 2 (W8) or 1 (W4) loads of 16
 // bytes per column tile = 2 RG / CT and 4 RG / CT, twice and four times the 16-bit kernel's RG / CT.  The column tiles follow the
-// 16-bit rule (gwq_ct: two from 2 row groups on where N >= 4096); four tiles or x staged in LDS were not built -- DESIGN 4.5.8 has
+// 16-bit rule (gw_ct: two from 2 row groups on where N >= 4096); four tiles or x staged in LDS were not built -- DESIGN 4.5.8 has
 // the ratio per plan and what was and was not measured.
 // Units a wave keeps in flight, from its 256 registers: the accumulators, 40 for addresses and the epilogue, 8 for the row scales
 // of a finishing lane (W8), and 16 for a unit's conversion (8 floats and the packed fragment of one column tile at a time).
 constexpr int gwq_depth(int fmt, int rg, int ct, int lp) {
-  const int unit = 16 * rg + (fmt == GW_W4 ? 5 : 8) * ct;
-  const int d = (256 - 4 * rg * ct - 40 - (fmt == GW_W8 ? 8 : 0) - 16) / unit;
+  const int unit = 16 * rg + (fmt == GV_W4 ? 5 : 8) * ct;
+  const int d = (256 - 4 * rg * ct - 40 - (fmt == GV_W8 ? 8 : 0) - 16) / unit;
   return d < 1 ? 1 : d > lp ? lp : d;
 }
+constexpr int gwq_depth_w8(int, int rg, int ct, int lp) { return gwq_depth(GV_W8, rg, ct, lp); }
+constexpr int gwq_depth_w4(int, int rg, int ct, int lp) { return gwq_depth(GV_W4, rg, ct, lp); }
 
-// the plan of a product on a quantized operand (fmt: GW_W8 | GW_W4); cls indexes GWQ_CLASSES
-inline bool gwq_plan(int fmt, int M, int N, int K, GwPlan& pl) {
+// ---------------------------------------------------------------------------------------------------------------------
+// What a weight format (GV_W16 | GV_W8 | GV_W4, weight_operand.h) means for the plan: its class list, the N from which 2 row groups
+// on take two column tiles, the pairs or units in flight, and the 16-byte weight loads of a lane per pair or unit and column tile.
+struct GwFormat { const GwClass* classes; int count, ct2_min_n; int (*depth)(int nwk, int rg, int ct, int lp); int loads; };
+constexpr GwFormat GW_FORMATS[3] = {
+    {GW_CLASS_TABLE, GWC_COUNT, GW_CT2_MIN_N, gw_depth, 2},
+    {GWQ_CLASS_TABLE, GWQC_COUNT, GWQ_CT2_MIN_N, gwq_depth_w8, 2},
+    {GWQ_CLASS_TABLE, GWQC_COUNT, GWQ_CT2_MIN_N, gwq_depth_w4, 1},
+};
+
+// the plan of a product on weights of format fmt; cls indexes the format's class list.  false: the wide kernel does not take the
+// product (unsupported)
+inline bool gw_plan(int fmt, int M, int N, int K, GwPlan& pl) {
   if (M < 1 || M > GW_MAX_M || N < 8 || (N & 7) || K < GW_MIN_K || K > GW_MAX_K || (K & 511)) return false;
-  for (int i = 0; i < GWQC_COUNT; ++i) {
-    const GwClass& c = GWQ_CLASS_TABLE[i];
+  const GwFormat& f = GW_FORMATS[fmt];
+  for (int i = 0; i < f.count; ++i) {
+    const GwClass& c = f.classes[i];
     if (K < c.k_from || K > c.k_to) continue;
-    const int rg = gw_rg(M), ct = gwq_ct(rg, N), cols = 16 * ct;
-    pl = GwPlan{rg, c.nwk, ct, c.lp, c.guard, gwq_depth(fmt, rg, ct, c.lp), 64 * c.nwk, (N + cols - 1) / cols, gw_lds(c.nwk, rg * ct), i};
+    const int rg = gw_rg(M), ct = gw_ct(rg, N, f.ct2_min_n), cols = 16 * ct;
+    pl = GwPlan{rg, c.nwk, ct, c.lp, c.guard, f.depth(c.nwk, rg, ct, c.lp), 64 * c.nwk, (N + cols - 1) / cols, gw_lds(c.nwk, rg * ct), i};
     return true;
   }
   return false;

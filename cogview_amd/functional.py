@@ -1008,15 +1008,21 @@ def decode_chain_supported(tr, batch):
             and tr.layers[0].input_layernorm.weight.dtype in (torch.float16, torch.bfloat16))
 
 
+def _linear_weights(layer):
+    """the four weight matrices of a layer, in the order a decode step multiplies by them"""
+    return layer.attention.query_key_value.weight, layer.attention.dense.weight, layer.mlp.dense_h_to_4h.weight, layer.mlp.dense_4h_to_h.weight
+
+
 class W8Weights:
     """The 8-bit copies a decode step streams instead of the 16-bit weights (ops.quantize_rows_e4m3; GraphDecoder(weights="e4m3")):
     per layer the (q, scale) pairs of the four Linear weights, and one of the word-embedding matrix for the tied-logits product.
     Biases, LayerNorm parameters and the embedding LOOKUP stay what they are."""
 
+    fmt = "e4m3"
+
     def __init__(self, tr, emb_weight):
-        quant = ops.quantize_rows_e4m3
-        self.layers = [(quant(l.attention.query_key_value.weight), quant(l.attention.dense.weight),
-                        quant(l.mlp.dense_h_to_4h.weight), quant(l.mlp.dense_4h_to_h.weight)) for l in tr.layers]
+        quant = _q_op(self.fmt, "quantize")
+        self.layers = [tuple(quant(w) for w in _linear_weights(l)) for l in tr.layers]
         self.emb = quant(emb_weight)
         self.dtype = emb_weight.dtype
 
@@ -1027,20 +1033,37 @@ class W8Weights:
 class W4Weights(W8Weights):
     """The 4-bit copies a decode step streams instead of the 16-bit weights (ops.quantize_rows_mxfp4; GraphDecoder(weights="mxfp4")):
     W8Weights' interface, every pair (q [N, K / 2], scale [N, K / 32]) in OCP MXFP4."""
-
-    def __init__(self, tr, emb_weight):
-        quant = ops.quantize_rows_mxfp4
-        self.layers = [(quant(l.attention.query_key_value.weight), quant(l.attention.dense.weight),
-                        quant(l.mlp.dense_h_to_4h.weight), quant(l.mlp.dense_4h_to_h.weight)) for l in tr.layers]
-        self.emb = quant(emb_weight)
-        self.dtype = emb_weight.dtype
+    fmt = "mxfp4"
 
 
-def _quantized_products(wq):
-    """(gemv_ln, gemm, gemv_attn) of the format a W8Weights / W4Weights holds."""
-    if isinstance(wq, W4Weights):
-        return ops.gemv_ln_w4, ops.gemm_w4, ops.gemv_attn_w4
-    return ops.gemv_ln_w8, ops.gemm_w8, ops.gemv_attn_w8
+# A weight format's row: the ops that quantize a weight and run the LayerNorm-prologue, plain, combine-prologue and wide products on
+# the pair, and the bits its refusals speak of.  A further format is a row here.
+_Q_OPS = {"e4m3": dict(quantize="quantize_rows_e4m3", gemv_ln="gemv_ln_w8", gemm="gemm_w8", gemv_attn="gemv_attn_w8", gemm_rows="gemm_rows_w8", bits=8),
+          "mxfp4": dict(quantize="quantize_rows_mxfp4", gemv_ln="gemv_ln_w4", gemm="gemm_w4", gemv_attn="gemv_attn_w4", gemm_rows="gemm_rows_w4", bits=4)}
+
+
+def _q_op(fmt, role):
+    """the op of `ops` that plays `role` (a key of _Q_OPS' rows) for a weight format, looked up when asked for"""
+    return getattr(ops, _Q_OPS[fmt][role])
+
+
+def _step_products(tr, chain):
+    """(kind, N, K) of every product a decode step issues, kind "plain" | "attn" | "ln" -- the chain's (decode_chain), or the five
+    plain ones of the layer-by-layer and the wide step (decode_layers): QKV, attention output, h -> 4h, 4h -> h, logits.  The
+    tied-logits product is listed with h columns: N decides a grid, never whether a class takes the product."""
+    h = tr.layers[0].input_layernorm.weight.shape[0]
+    f = tr.layers[0].mlp.dense_h_to_4h.weight.shape[0]
+    hp = tr.layers[0].attention.num_attention_heads_per_partition * 64
+    if chain:
+        # (the projection's form follows _decode_fuse_combine() at run time: both must be there)
+        return [("ln", 3 * hp, h), ("plain", h, hp)] + ([("attn", h, hp)] if hp % 512 == 0 else []) + [("ln", f, h), ("plain", h, f), ("ln", h, h)]
+    return [("plain", 3 * hp, h), ("plain", h, hp), ("plain", f, h), ("plain", h, f), ("plain", h, h)]
+
+
+def _dtype_code(tr):
+    """the library's code of the weights' 16-bit type, or None"""
+    from . import _lib
+    return {torch.float16: _lib.F16, torch.bfloat16: _lib.BF16}.get(tr.layers[0].attention.query_key_value.weight.dtype)
 
 
 def w4_decode_supported(tr, batch):
@@ -1050,28 +1073,20 @@ def w4_decode_supported(tr, batch):
 
 def w8_decode_supported(tr, batch, fmt="e4m3"):
     """The 8-bit decode step at this row count: every product it will issue -- the chain's (decode_chain) where
-    decode_chain_supported, else the layer-by-layer step's (decode_layers_w8) -- is put to the library's own launch plan
+    decode_chain_supported, else the layer-by-layer step's (decode_layers) -- is put to the library's own launch plan
     (cogv_gemv_plan: host only, nothing is touched).  The tied-logits product is asked with h columns: N decides a grid, never
     whether a class takes the product.  Returns None, or the reason as a string."""
     from . import _lib
-    att = tr.layers[0].attention
-    h = tr.layers[0].input_layernorm.weight.shape[0]
-    f = tr.layers[0].mlp.dense_h_to_4h.weight.shape[0]
-    hp = att.num_attention_heads_per_partition * 64
     if batch > 8:
         return f"batch {batch} > 8 rows"
-    plain, attn, ln = _lib.GEMV_PLAIN, _lib.GEMV_ATTN, _lib.GEMV_LN
-    if decode_chain_supported(tr, batch):
-        # (the projection's form follows _decode_fuse_combine() at run time: both must be there)
-        products = [(ln, 3 * hp, h), (plain, h, hp)] + ([(attn, h, hp)] if hp % 512 == 0 else []) + [(ln, f, h), (plain, h, f), (ln, h, h)]
-    else:
-        products = [(plain, 3 * hp, h), (plain, h, hp), (plain, f, h), (plain, h, f), (plain, h, h)]
-    dtype = _lib.BF16 if att.query_key_value.weight.dtype == torch.bfloat16 else _lib.F16
-    bits = 4 if fmt == "mxfp4" else 8
-    for kind, n, k in products:
-        rc = _lib.gemv_w4_plan(kind, dtype, batch, n, k)[0] if bits == 4 else _lib.gemv_plan(kind, dtype, batch, n, k, w8=True)[0]
+    kinds = {"plain": (_lib.GEMV_PLAIN, "plain"), "attn": (_lib.GEMV_ATTN, "combine-prologue"), "ln": (_lib.GEMV_LN, "LayerNorm-prologue")}
+    dtype = _lib.BF16 if _dtype_code(tr) == _lib.BF16 else _lib.F16
+    bits = _Q_OPS[fmt]["bits"]
+    for kind, n, k in _step_products(tr, decode_chain_supported(tr, batch)):
+        code, name = kinds[kind]
+        rc = _lib.gemv_w4_plan(code, dtype, batch, n, k)[0] if fmt == "mxfp4" else _lib.gemv_plan(code, dtype, batch, n, k, w8=True)[0]
         if rc != _lib.OK:
-            return f"contraction length {k} at {batch} row(s) is outside the {bits}-bit kernels' classes ({('plain', 'combine-prologue', 'LayerNorm-prologue')[kind]} product, {n} columns)"
+            return f"contraction length {k} at {batch} row(s) is outside the {bits}-bit kernels' classes ({name} product, {n} columns)"
     return None
 
 
@@ -1094,19 +1109,14 @@ def decode_wide_supported(tr, rows):
     from . import _lib
     if not _DECODE_WIDE or mp_world_size_or_1() != 1 or not DECODE_WIDE_MIN_ROWS <= rows <= _DECODE_WIDE_MAX_ROWS:
         return False
-    att = tr.layers[0].attention
-    dt = att.query_key_value.weight.dtype
-    if dt not in (torch.float16, torch.bfloat16):
+    code = _dtype_code(tr)
+    if code is None:
         return False
-    h = tr.layers[0].input_layernorm.weight.shape[0]
-    f = tr.layers[0].mlp.dense_h_to_4h.weight.shape[0]
-    hp = att.num_attention_heads_per_partition * 64
-    code = _lib.BF16 if dt == torch.bfloat16 else _lib.F16
-    return all(_lib.gemm_rows_plan(code, rows, n, k)[0] == _lib.OK for n, k in ((3 * hp, h), (h, hp), (f, h), (h, f), (h, h)))
+    return all(_lib.gemm_rows_plan(code, rows, n, k)[0] == _lib.OK for _, n, k in _step_products(tr, chain=False))
 
 
 def decode_wide_q_supported(tr, rows, fmt):
-    """The wide decode step on quantized weights (decode_layers(w8=..., wide=True); fmt "e4m3" | "mxfp4") at this row count: None, or
+    """The wide decode step on quantized weights (decode_layers(wq=..., wide=True); fmt "e4m3" | "mxfp4") at this row count: None, or
     the reason as a string.  9 .. 64 rows on one model-parallel partition in a 16-bit type, and every product the step issues
     (QKV, attention output, h -> 4h, 4h -> h, logits) taken by the library's own launch plan (cogv_gemm_rows_w8_plan /
     cogv_gemm_rows_w4_plan: host only, nothing is touched).  The tied-logits product is asked with h columns: N decides a grid,
@@ -1117,22 +1127,17 @@ def decode_wide_q_supported(tr, rows, fmt):
         return "the wide step on quantized weights runs on one model-parallel partition"
     if not DECODE_WIDE_MIN_ROWS <= rows <= DECODE_WIDE_KERNEL_ROWS:
         return f"{rows} rows are outside the wide step's {DECODE_WIDE_MIN_ROWS} .. {DECODE_WIDE_KERNEL_ROWS}"
-    att = tr.layers[0].attention
-    dt = att.query_key_value.weight.dtype
-    if dt not in (torch.float16, torch.bfloat16):
-        return f"{dt} weights: the wide products take fp16 and bf16"
-    h = tr.layers[0].input_layernorm.weight.shape[0]
-    f = tr.layers[0].mlp.dense_h_to_4h.weight.shape[0]
-    hp = att.num_attention_heads_per_partition * 64
-    code = _lib.BF16 if dt == torch.bfloat16 else _lib.F16
-    query, bits = (_lib.gemm_rows_w4_plan, 4) if fmt == "mxfp4" else (_lib.gemm_rows_w8_plan, 8)
-    for n, k in ((3 * hp, h), (h, hp), (f, h), (h, f), (h, h)):
+    code = _dtype_code(tr)
+    if code is None:
+        return f"{tr.layers[0].attention.query_key_value.weight.dtype} weights: the wide products take fp16 and bf16"
+    query, bits = _lib.gemm_rows_w4_plan if fmt == "mxfp4" else _lib.gemm_rows_w8_plan, _Q_OPS[fmt]["bits"]
+    for _, n, k in _step_products(tr, chain=False):
         if query(code, rows, n, k)[0] != _lib.OK:
             return f"contraction length {k} at {rows} rows is outside the {bits}-bit wide kernel's classes ({n} columns)"
     return None
 
 
-def decode_chain(tr, h0, absmax0, slots, emb_weight, w8=None):
+def decode_chain(tr, h0, absmax0, slots, emb_weight, wq=None):
     """One decode step through all layers with FIVE launches per layer (round 3: the split-combine of the decode attention
     rides in the dense GEMV's prologue): QKV GEMV with [previous layer's
     LN4 + residual, LN1] as prologue | decode attention, key splits (cache append fused) | dense GEMV with the combine as prologue | h->4h GEMV with [LN3 +
@@ -1142,22 +1147,16 @@ def decode_chain(tr, h0, absmax0, slots, emb_weight, w8=None):
     layer.  Returns logits [b, m, V].  m = 1: one token per cache row.  m > 1 (a chunk step, b * m <= 8 rows): the same
     launches on b * m rows, rows b * m + j being the tokens of slots pos_index + j (ops.attention_decode_chunk in the attention
     slot); the Sandwich scale is the abs-max over all b * m rows, as in a multi-token model call.
-    w8 (W8Weights, or W4Weights for the 4-bit format): launch for launch the same chain on the quantized copies of the weights, each
+    wq (W8Weights, or W4Weights for the 4-bit format): launch for launch the same chain on the quantized copies of the weights, each
     product reading (q, scale) in place of the 16-bit matrix (emb_weight is not read)."""
     b, s, h = h0.shape
     rows = b * s
-    if w8 is None:
-        gemv_ln, gemm, logits_w = ops.gemv_ln, ops.gemm, emb_weight
-        operands = ((l.attention.query_key_value.weight, l.attention.dense.weight, l.mlp.dense_h_to_4h.weight, l.mlp.dense_4h_to_h.weight)
-                    for l in tr.layers)
-
-        def gemv_attn(parts, npp, cap, w, bias):
-            return ops.gemv_attn(parts, rows, npp, cap, w, bias=bias)
+    if wq is None:
+        gemv_ln, gemm, gemv_attn, out_dtype = ops.gemv_ln, ops.gemm, ops.gemv_attn, ()
+        logits_w, operands = emb_weight, (_linear_weights(l) for l in tr.layers)
     else:
-        (gemv_ln, gemm, gemv_attn_q), logits_w, operands = _quantized_products(w8), w8.emb, w8.layers
-
-        def gemv_attn(parts, npp, cap, w, bias):
-            return gemv_attn_q(parts, rows, npp, cap, w, w8.dtype, bias=bias)
+        gemv_ln, gemm, gemv_attn = (_q_op(wq.fmt, role) for role in ("gemv_ln", "gemm", "gemv_attn"))
+        logits_w, operands, out_dtype = wq.emb, wq.layers, (wq.dtype,)       # (a quantized pair does not say what the output is)
     z, z_absmax, post, res = h0.view(rows, h), absmax0, None, None
     for layer, slot, (w_qkv, w_dense, w_h4h, w_4hh) in zip(tr.layers, slots, operands):
         att_m, mlp_m = layer.attention, layer.mlp
@@ -1175,7 +1174,7 @@ def decode_chain(tr, h0, absmax0, slots, emb_weight, w8=None):
         if hp % 512 == 0 and _decode_fuse_combine():
             # the key splits' partials are combined in the prologue of the attention-output GEMV (one launch less)
             parts = decode_attention(qkv.view(b, s, 3 * hp), slot, npp, combine=False)
-            ao = gemv_attn(parts, npp, slot.capacity, w_dense, att_m.dense.bias)
+            ao = gemv_attn(parts, rows, npp, slot.capacity, w_dense, *out_dtype, bias=att_m.dense.bias)
         else:
             att = decode_attention(qkv.view(b, s, 3 * hp), slot, npp)
             ao = gemm(att.view(rows, hp), w_dense, bias=att_m.dense.bias)
@@ -1189,10 +1188,10 @@ def decode_chain(tr, h0, absmax0, slots, emb_weight, w8=None):
     return logits.view(b, s, logits.shape[1])
 
 
-def decode_layers(tr, h0, absmax0, slots, emb_weight, w8=None, wide=False):
+def decode_layers(tr, h0, absmax0, slots, emb_weight, wq=None, wide=False):
     """One decode step layer by layer: _layer_forward's inference chain on b * m <= 8 rows (every Sandwich-LN its own launch,
     decode attention with its combine, four plain skinny products per layer), the final LayerNorm and the tied-logits product.
-    h0 [b, m, h] -> logits [b, m, V]; m > 1: a chunk step, as in decode_chain.  w8 (W8Weights | W4Weights): the products read the 8-bit
+    h0 [b, m, h] -> logits [b, m, V]; m > 1: a chunk step, as in decode_chain.  wq (W8Weights | W4Weights): the products read the 8-bit
     or 4-bit copies (emb_weight is not read).  What a decoder runs above COGV_DECODE_CHAIN_MAX_ROWS for the 8-bit weights and for chunk steps, and
     the comparison path of the chain.  wide=True (up to 64 rows): the five products go to the weight-streaming form above 8 rows --
     ops.gemm_rows on the 16-bit weights (decode_wide_supported), ops.gemm_rows_w8 / ops.gemm_rows_w4 on the quantized copies
@@ -1200,13 +1199,11 @@ def decode_layers(tr, h0, absmax0, slots, emb_weight, w8=None, wide=False):
     b, s, h = h0.shape
     rows = b * s
     dev = h0.device
-    if w8 is None:
-        gemm, logits_w = (ops.gemm_rows if wide else ops.gemm), emb_weight
-        operands = ((l.attention.query_key_value.weight, l.attention.dense.weight, l.mlp.dense_h_to_4h.weight, l.mlp.dense_4h_to_h.weight)
-                    for l in tr.layers)
+    if wq is None:
+        gemm, logits_w, operands = (ops.gemm_rows if wide else ops.gemm), emb_weight, (_linear_weights(l) for l in tr.layers)
     else:
-        gemm = (ops.gemm_rows_w4 if isinstance(w8, W4Weights) else ops.gemm_rows_w8) if wide else _quantized_products(w8)[1]
-        logits_w, operands = w8.emb, w8.layers
+        gemm = _q_op(wq.fmt, "gemm_rows" if wide else "gemm")
+        logits_w, operands = wq.emb, wq.layers
     x, absmax_x = (h0 if h0.is_contiguous() else h0.contiguous()), absmax0
     for layer, slot, (w_qkv, w_dense, w_h4h, w_4hh) in zip(tr.layers, slots, operands):
         att_m, mlp_m = layer.attention, layer.mlp
@@ -1233,11 +1230,6 @@ def decode_layers(tr, h0, absmax0, slots, emb_weight, w8=None, wide=False):
     out, _, _ = ops.sandwich_ln_fwd(x, fl.weight, fl.bias, fl.eps, absmax_x, save_stats=False)
     logits = gemm(out.view(rows, h), logits_w)
     return logits.view(b, s, logits.shape[1])
-
-
-def decode_layers_w8(tr, h0, absmax0, slots, w8):
-    """decode_layers on the 8-bit weights: what the 8-bit decoder runs above COGV_DECODE_CHAIN_MAX_ROWS."""
-    return decode_layers(tr, h0, absmax0, slots, None, w8=w8)
 
 
 def transformer_layer_kv(layer, x, absmax_x, sep, kv_slot, mask=None):

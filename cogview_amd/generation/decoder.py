@@ -120,7 +120,7 @@ class GraphDecoder:
         0 (default): nothing is allocated or captured, the decoder is what it was.
         wide=True (opt-in; a later change makes it the default): with weights= set and 9 ... 64 rows the step runs layer by layer on
         the quantized copies through the wide weight-streaming products (ops.gemm_rows_w8 / ops.gemm_rows_w4; functional.decode_layers(
-        w8=..., wide=True)) instead of being refused as more than 8 rows.  Composes with kv= and ragged=; chunk= keeps batch * chunk
+        wq=..., wide=True)) instead of being refused as more than 8 rows.  Composes with kv= and ragged=; chunk= keeps batch * chunk
         <= 8.  Captured 4B step: 5.13 / 6.87 / 7.85 / 12.75 ms on "e4m3" and 4.91 / 6.71 / 7.74 / 12.63 ms on "mxfp4" at 12 /
         24 / 32 / 64 rows against 5.72 / 7.62 / 8.67 / 13.35 ms on the 16-bit wide step of the same process -- faster at every row
         count measured; against the tile kernels, which the 16-bit decoder takes above 24 rows, not faster from 48 rows on.  With
@@ -176,12 +176,12 @@ class GraphDecoder:
             if self.fused and F_.decode_chain_supported(tr, self.batch):
                 # five launches per layer: the LayerNorms ride as prologues of the GEMVs, the cache append inside the
                 # decode attention kernel (functional.decode_chain); w8: the same chain on the 8-bit copies of the weights
-                return F_.decode_chain(tr, h, h._cogv_absmax, self.slots, self.gpt.word_embeddings.weight, w8=self.wq)
+                return F_.decode_chain(tr, h, h._cogv_absmax, self.slots, self.gpt.word_embeddings.weight, wq=self.wq)
             if self.wide_q:
                 # 9 .. 64 rows on the quantized copies: the five products as weight streams (ops.gemm_rows_w8 / ops.gemm_rows_w4)
-                return F_.decode_layers(tr, h, h._cogv_absmax, self.slots, None, w8=self.wq, wide=True)
+                return F_.decode_layers(tr, h, h._cogv_absmax, self.slots, None, wq=self.wq, wide=True)
             if self.wq is not None:
-                return F_.decode_layers_w8(tr, h, h._cogv_absmax, self.slots, self.wq)
+                return F_.decode_layers(tr, h, h._cogv_absmax, self.slots, None, wq=self.wq)
             if F_.decode_wide_supported(tr, self.batch):
                 # 9 .. 64 rows on the 16-bit weights: layer by layer, the five products as weight streams (ops.gemm_rows)
                 return F_.decode_layers(tr, h, h._cogv_absmax, self.slots, self.gpt.word_embeddings.weight, wide=True)
@@ -198,8 +198,8 @@ class GraphDecoder:
         with ops.scalar_slab(self.slab):
             h = tr.embed(self.tok_chunk, self.pos_chunk, self.gpt.word_embeddings)
             if self.fused and F_.decode_chain_supported(tr, self.batch * self.chunk):
-                return F_.decode_chain(tr, h, h._cogv_absmax, self.slots, self.gpt.word_embeddings.weight, w8=self.wq)
-            return F_.decode_layers(tr, h, h._cogv_absmax, self.slots, self.gpt.word_embeddings.weight, w8=self.wq)
+                return F_.decode_chain(tr, h, h._cogv_absmax, self.slots, self.gpt.word_embeddings.weight, wq=self.wq)
+            return F_.decode_layers(tr, h, h._cogv_absmax, self.slots, self.gpt.word_embeddings.weight, wq=self.wq)
 
     def capture(self):
         """Warm up on a side stream (first-use allocations inside the library and the caching allocator), then capture."""

@@ -359,8 +359,31 @@ def gemm_rows(a, w, bias=None, gelu=False, absmax=None, out=None):
     return out
 
 
-def _rows_q(a, K, N, bias, gelu, absmax, out):
-    """(descriptor, out) of a wide product on a quantized weight with N rows: the operand itself is the caller's."""
+_Q_SUFFIX = {"e4m3": "_w8", "mxfp4": "_w4"}       # weight format -> what the C entry points of its products end in
+
+
+def _q_operand(fmt, qs, K=None):
+    """(N, K, cogv_w8_weight | cogv_w4_weight) of the quantized weight qs = (q, scale) of format `fmt`, validated.  K: the
+    contraction length the product's input has (None: the weight's own)."""
+    q, scale = qs
+    _need_gpu(q, scale)
+    per_byte, what = (2, "q [N, K / 2] uint8") if fmt == "mxfp4" else (1, "q [N, K] uint8")
+    assert q.dim() == 2 and q.dtype == torch.uint8 and q.stride(1) == 1 and K in (None, q.shape[1] * per_byte), \
+        what + ("" if K is None else " with K matching the input")
+    N, K = q.shape[0], q.shape[1] * per_byte
+    if fmt == "mxfp4":
+        assert scale.dim() == 2 and scale.dtype == torch.uint8 and scale.stride(1) == 1 and scale.shape == (N, K // 32)
+        w = L.W4Weight()
+        w.lds = scale.stride(0)
+    else:
+        assert scale.dtype == torch.float32 and scale.is_contiguous() and scale.numel() == N
+        w = L.W8Weight()
+    w.q, w.ldq, w.scale = q.data_ptr(), q.stride(0), scale.data_ptr()
+    return N, K, w
+
+
+def _gemm_rows_q(fmt, a, qs, bias, gelu, absmax, out):
+    N, K, w = _q_operand(fmt, qs)
     _need_gpu(a)
     assert a.dim() == 2 and a.stride(1) == 1 and a.shape[1] == K, "a [M, K] with K matching the weight"
     assert bias is None or bias.dtype == a.dtype
@@ -371,38 +394,23 @@ def _rows_q(a, K, N, bias, gelu, absmax, out):
     d = _skinny_desc(out, K, bias, gelu, absmax)
     d.ldc = out.stride(0)
     d.A, d.lda = a.data_ptr(), a.stride(0)
-    return d, out
+    name = "cogv_gemm_rows" + _Q_SUFFIX[fmt]
+    L.check(getattr(L.lib(), name)(C.byref(d), C.byref(w), _stream()), name)
+    return out
 
 
 def gemm_rows_w8(a, qs, bias=None, gelu=False, absmax=None, out=None):
     """gemm_rows on an 8-bit weight qs = (q [N, K] uint8, scale [N] fp32) from quantize_rows_e4m3 (cogv_gemm_rows_w8): out [M, N] =
     epilogue(scale * (a . e4m3(q)^T) + bias) in a's dtype for 1 <= M <= 64 rows; gemm_w8 stops at 8.  Rows of a, q and a given
     `out` may be strided (q: a multiple of 16 bytes).  Shapes outside raise: there is no other kernel."""
-    q, scale = qs
-    _need_gpu(q, scale)
-    assert q.dim() == 2 and q.dtype == torch.uint8 and q.stride(1) == 1, "q [N, K] uint8"
-    assert scale.dtype == torch.float32 and scale.is_contiguous() and scale.numel() == q.shape[0]
-    d, out = _rows_q(a, q.shape[1], q.shape[0], bias, gelu, absmax, out)
-    w = L.W8Weight()
-    w.q, w.ldq, w.scale = q.data_ptr(), q.stride(0), scale.data_ptr()
-    L.check(L.lib().cogv_gemm_rows_w8(C.byref(d), C.byref(w), _stream()), "cogv_gemm_rows_w8")
-    return out
+    return _gemm_rows_q("e4m3", a, qs, bias, gelu, absmax, out)
 
 
 def gemm_rows_w4(a, qs, bias=None, gelu=False, absmax=None, out=None):
     """gemm_rows on a 4-bit weight qs = (q [N, K / 2] uint8, scale [N, K / 32] uint8) from quantize_rows_mxfp4 (cogv_gemm_rows_w4):
     out [M, N] = epilogue(a . dequantize_rows_mxfp4(q, scale)^T + bias) in a's dtype for 1 <= M <= 64 rows; gemm_w4 stops at 8.
     Rows of a, q (a multiple of 16 bytes), scale and a given `out` may be strided.  Shapes outside raise: there is no other kernel."""
-    q, scale = qs
-    _need_gpu(q, scale)
-    assert q.dim() == 2 and q.dtype == torch.uint8 and q.stride(1) == 1, "q [N, K / 2] uint8"
-    K = q.shape[1] * 2
-    assert scale.dim() == 2 and scale.dtype == torch.uint8 and scale.stride(1) == 1 and scale.shape == (q.shape[0], K // 32)
-    d, out = _rows_q(a, K, q.shape[0], bias, gelu, absmax, out)
-    w = L.W4Weight()
-    w.q, w.ldq, w.scale, w.lds = q.data_ptr(), q.stride(0), scale.data_ptr(), scale.stride(0)
-    L.check(L.lib().cogv_gemm_rows_w4(C.byref(d), C.byref(w), _stream()), "cogv_gemm_rows_w4")
-    return out
+    return _gemm_rows_q("mxfp4", a, qs, bias, gelu, absmax, out)
 
 
 def _ln_prologue(z, gamma, beta, eps, z_absmax, post, residual, want_t):
@@ -842,52 +850,66 @@ def quantize_rows_e4m3(w):
     return q, scale
 
 
-def _w8_call(x_dtype, M, K, qs, bias, gelu, absmax):
-    """(descriptor, operand, out) of a skinny-M product on the 8-bit weight qs = (q, scale)."""
-    q, scale = qs
-    _need_gpu(q, scale)
-    assert q.dim() == 2 and q.dtype == torch.uint8 and q.stride(1) == 1 and q.shape[1] == K, "q [N, K] uint8 with K matching the input"
-    assert scale.dtype == torch.float32 and scale.is_contiguous() and scale.numel() == q.shape[0]
-    N = q.shape[0]
+def _q_call(fmt, x_dtype, M, K, qs, bias, gelu, absmax):
+    """(descriptor, operand, out) of a skinny-M product on the quantized weight qs = (q, scale) of format `fmt`."""
+    N, K, w = _q_operand(fmt, qs, K)
     assert bias is None or bias.dtype == x_dtype
-    out = torch.empty((M, N), dtype=x_dtype, device=q.device)
-    d = _skinny_desc(out, K, bias, gelu, absmax)
-    w = L.W8Weight()
-    w.q, w.ldq, w.scale = q.data_ptr(), q.stride(0), scale.data_ptr()
-    return d, w, out
+    out = torch.empty((M, N), dtype=x_dtype, device=qs[0].device)
+    return _skinny_desc(out, K, bias, gelu, absmax), w, out
+
+
+def _w8_call(x_dtype, M, K, qs, bias, gelu, absmax):
+    """_q_call on the E4M3 weight (tests/test_gemv_cells_gpu.py fills the descriptor and the operand itself around it)"""
+    return _q_call("e4m3", x_dtype, M, K, qs, bias, gelu, absmax)
+
+
+# the three skinny-M kinds on a quantized weight of format `fmt`; the public functions below bind it
+def _gemm_q(fmt, a, qs, bias, gelu, absmax):
+    _need_gpu(a)
+    assert a.dim() == 2 and a.stride(1) == 1
+    M, K = a.shape
+    d, w, out = _q_call(fmt, a.dtype, M, K, qs, bias, gelu, absmax)
+    d.A, d.lda = a.data_ptr(), a.stride(0)
+    name = "cogv_gemm" + _Q_SUFFIX[fmt]
+    L.check(getattr(L.lib(), name)(C.byref(d), C.byref(w), _stream()), name)
+    return out
+
+
+def _gemv_ln_q(fmt, z, qs, bias, gamma, beta, eps, z_absmax, post, residual, want_t, gelu, absmax):
+    _need_gpu(z, gamma)
+    assert z.dim() == 2 and z.is_contiguous()
+    M, K = z.shape
+    d, w, out = _q_call(fmt, gamma.dtype, M, K, qs, bias, gelu, absmax)
+    ln, t = _ln_prologue(z, gamma, beta, eps, z_absmax, post, residual, want_t)
+    name = "cogv_gemv_ln" + _Q_SUFFIX[fmt]
+    L.check(getattr(L.lib(), name)(C.byref(d), C.byref(ln), C.byref(w), _stream()), name)
+    return out, t
+
+
+def _gemv_attn_q(fmt, partials, batch, heads, capacity, qs, dtype, bias, absmax):
+    _need_gpu(partials)
+    assert batch <= 8
+    d, w, out = _q_call(fmt, dtype, batch, heads * 64, qs, bias, False, absmax)
+    name = "cogv_gemv_attn" + _Q_SUFFIX[fmt]
+    L.check(getattr(L.lib(), name)(C.byref(d), C.byref(w), _p(partials), int(heads), int(capacity), _stream()), name)
+    return out
 
 
 def gemm_w8(a, qs, bias=None, gelu=False, absmax=None):
     """gemm's skinny case (a [M, K], M <= 8) on an 8-bit weight qs = (q [N, K] uint8, scale [N]) from quantize_rows_e4m3
     (cogv_gemm_w8): out [M, N] = epilogue(scale * (a . e4m3(q)^T) + bias) in a's dtype.  Shapes outside the kernels' classes raise:
     there is no other kernel behind this one."""
-    _need_gpu(a)
-    assert a.dim() == 2 and a.stride(1) == 1
-    M, K = a.shape
-    d, w, out = _w8_call(a.dtype, M, K, qs, bias, gelu, absmax)
-    d.A, d.lda = a.data_ptr(), a.stride(0)
-    L.check(L.lib().cogv_gemm_w8(C.byref(d), C.byref(w), _stream()), "cogv_gemm_w8")
-    return out
+    return _gemm_q("e4m3", a, qs, bias, gelu, absmax)
 
 
 def gemv_ln_w8(z, qs, bias, gamma, beta, eps, z_absmax=None, post=None, residual=None, want_t=False, gelu=False, absmax=None):
     """gemv_ln on an 8-bit weight qs = (q, scale) (cogv_gemv_ln_w8); everything else as there.  The output takes gamma's dtype."""
-    _need_gpu(z, gamma)
-    assert z.dim() == 2 and z.is_contiguous()
-    M, K = z.shape
-    d, w, out = _w8_call(gamma.dtype, M, K, qs, bias, gelu, absmax)
-    ln, t = _ln_prologue(z, gamma, beta, eps, z_absmax, post, residual, want_t)
-    L.check(L.lib().cogv_gemv_ln_w8(C.byref(d), C.byref(ln), C.byref(w), _stream()), "cogv_gemv_ln_w8")
-    return out, t
+    return _gemv_ln_q("e4m3", z, qs, bias, gamma, beta, eps, z_absmax, post, residual, want_t, gelu, absmax)
 
 
 def gemv_attn_w8(partials, batch, heads, capacity, qs, dtype, bias=None, absmax=None):
     """gemv_attn on an 8-bit weight qs = (q, scale) (cogv_gemv_attn_w8); `dtype`: the 16-bit type of the output (and bias)."""
-    _need_gpu(partials)
-    assert batch <= 8
-    d, w, out = _w8_call(dtype, batch, heads * 64, qs, bias, False, absmax)
-    L.check(L.lib().cogv_gemv_attn_w8(C.byref(d), C.byref(w), _p(partials), int(heads), int(capacity), _stream()), "cogv_gemv_attn_w8")
-    return out
+    return _gemv_attn_q("e4m3", partials, batch, heads, capacity, qs, dtype, bias, absmax)
 
 
 # ------------------------------------------------------------------------------------------ 4-bit weights (decode step)
@@ -920,52 +942,21 @@ def dequantize_rows_mxfp4(q, scale, dtype=torch.float32):
     return torch.ldexp(val, (scale.long() - 127).repeat_interleave(32, dim=1)).to(dtype)
 
 
-def _w4_call(x_dtype, M, K, qs, bias, gelu, absmax):
-    """(descriptor, operand, out) of a skinny-M product on the 4-bit weight qs = (q, scale)."""
-    q, scale = qs
-    _need_gpu(q, scale)
-    assert q.dim() == 2 and q.dtype == torch.uint8 and q.stride(1) == 1 and q.shape[1] * 2 == K, "q [N, K / 2] uint8 with K matching the input"
-    assert scale.dim() == 2 and scale.dtype == torch.uint8 and scale.stride(1) == 1 and scale.shape == (q.shape[0], K // 32)
-    N = q.shape[0]
-    assert bias is None or bias.dtype == x_dtype
-    out = torch.empty((M, N), dtype=x_dtype, device=q.device)
-    d = _skinny_desc(out, K, bias, gelu, absmax)
-    w = L.W4Weight()
-    w.q, w.ldq, w.scale, w.lds = q.data_ptr(), q.stride(0), scale.data_ptr(), scale.stride(0)
-    return d, w, out
-
-
 def gemm_w4(a, qs, bias=None, gelu=False, absmax=None):
     """gemm's skinny case (a [M, K], M <= 8) on a 4-bit weight qs = (q [N, K / 2] uint8, scale [N, K / 32] uint8) from
     quantize_rows_mxfp4 (cogv_gemm_w4): out [M, N] = epilogue(a . dequantize_rows_mxfp4(q, scale)^T + bias) in a's dtype.  Shapes
     outside the kernels' classes raise: there is no other kernel behind this one."""
-    _need_gpu(a)
-    assert a.dim() == 2 and a.stride(1) == 1
-    M, K = a.shape
-    d, w, out = _w4_call(a.dtype, M, K, qs, bias, gelu, absmax)
-    d.A, d.lda = a.data_ptr(), a.stride(0)
-    L.check(L.lib().cogv_gemm_w4(C.byref(d), C.byref(w), _stream()), "cogv_gemm_w4")
-    return out
+    return _gemm_q("mxfp4", a, qs, bias, gelu, absmax)
 
 
 def gemv_ln_w4(z, qs, bias, gamma, beta, eps, z_absmax=None, post=None, residual=None, want_t=False, gelu=False, absmax=None):
     """gemv_ln on a 4-bit weight qs = (q, scale) (cogv_gemv_ln_w4); everything else as there.  The output takes gamma's dtype."""
-    _need_gpu(z, gamma)
-    assert z.dim() == 2 and z.is_contiguous()
-    M, K = z.shape
-    d, w, out = _w4_call(gamma.dtype, M, K, qs, bias, gelu, absmax)
-    ln, t = _ln_prologue(z, gamma, beta, eps, z_absmax, post, residual, want_t)
-    L.check(L.lib().cogv_gemv_ln_w4(C.byref(d), C.byref(ln), C.byref(w), _stream()), "cogv_gemv_ln_w4")
-    return out, t
+    return _gemv_ln_q("mxfp4", z, qs, bias, gamma, beta, eps, z_absmax, post, residual, want_t, gelu, absmax)
 
 
 def gemv_attn_w4(partials, batch, heads, capacity, qs, dtype, bias=None, absmax=None):
     """gemv_attn on a 4-bit weight qs = (q, scale) (cogv_gemv_attn_w4); `dtype`: the 16-bit type of the output (and bias)."""
-    _need_gpu(partials)
-    assert batch <= 8
-    d, w, out = _w4_call(dtype, batch, heads * 64, qs, bias, False, absmax)
-    L.check(L.lib().cogv_gemv_attn_w4(C.byref(d), C.byref(w), _p(partials), int(heads), int(capacity), _stream()), "cogv_gemv_attn_w4")
-    return out
+    return _gemv_attn_q("mxfp4", partials, batch, heads, capacity, qs, dtype, bias, absmax)
 
 
 def _sparse_desc(d, kv_index, sparse, b, s_q):
