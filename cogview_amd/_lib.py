@@ -117,6 +117,21 @@ class AttnDecodeKv8Desc(C.Structure):
     ]
 
 
+class AttnDecodeChunkKv8Desc(C.Structure):
+    _fields_ = [
+        ("dtype", C.c_int), ("B", C.c_int), ("H", C.c_int), ("capacity", C.c_int), ("head_dim", C.c_int),
+        ("m", C.c_int),
+        ("scale", C.c_float),
+        ("qkv", C.c_void_p), ("qkv_rs", C.c_longlong),
+        ("kv_q", C.c_void_p), ("kv_q_bs", C.c_longlong),
+        ("kv_scale", C.c_void_p), ("kv_scale_bs", C.c_longlong),
+        ("out", C.c_void_p), ("out_rs", C.c_longlong),
+        ("pos", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("skip_combine", C.c_int),
+        ("first", C.c_void_p),
+    ]
+
+
 class AdamDesc(C.Structure):
     _fields_ = [
         ("dtype", C.c_int),
@@ -232,6 +247,7 @@ SIGNATURES = {
     "cogv_gemm_rows_w4_plan": (_i, [C.POINTER(GemmDesc), C.POINTER(W4Weight), C.POINTER(C.c_int)]),
     "cogv_kv_quantize_e4m3": (_i, [_i, _vp, _i64, _i64, _i, _i, _i, _vp, _i64, _vp, _i64, _i, _i, _vp]),
     "cogv_attention_decode_kv8": (_i, [C.POINTER(AttnDecodeKv8Desc), _vp]),
+    "cogv_attention_decode_chunk_kv8": (_i, [C.POINTER(AttnDecodeChunkKv8Desc), _vp]),
     "cogv_attention_decode_workspace_bytes": (_sz, [_i, _i, _i]),
     "cogv_attention_keep_bits_bytes": (_sz, [_i, _i, _i, _i]),
     "cogv_sparse_slot_reduce": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i64, _i, _i, _i, _i, _i, _i, _i, _vp]),

@@ -1,6 +1,7 @@
 // Attention of a decode step: ONE query token per batch row (cogv_attention_decode), m <= 8 tokens per row
-// (cogv_attention_decode_chunk) or one token on an 8-bit cache (cogv_kv_quantize_e4m3, cogv_attention_decode_kv8) against a
-// fixed-capacity key/value cache (generation/sampling.py:139-148, one model call per generated token; generation/decoder.py).
+// (cogv_attention_decode_chunk), one token on an 8-bit cache (cogv_kv_quantize_e4m3, cogv_attention_decode_kv8) or m <= 8 tokens
+// on it (cogv_attention_decode_chunk_kv8) against a fixed-capacity key/value cache (generation/sampling.py:139-148, one model
+// call per generated token; generation/decoder.py).
 // The 128-query tile kernels of attention.hip spend a whole workgroup per (batch, head) on one row (40 workgroups on 256 CUs,
 // 34 us per layer at 1152 slots); the kernels here split the KEYS: grid (capacity / 128, H, B), a partial (max, sum, output)
 // per split; a second small launch combines the partials in split order (deterministic).  The new token's key / value come
@@ -441,8 +442,167 @@ __global__ __launch_bounds__(256) void attn_decode_kv8_kernel(const DecodeKv8Arg
   }
 }
 
+// ---------------------------------------------------------------------------------------------------- m tokens, 8-bit cache
+// The chunk step (attn_decode_chunk_kernel) on the 8-bit cache: lanes, loads and reduction are attn_decode_kv8_kernel's, the
+// chunk's rows go through LDS as in attn_decode_chunk_kernel.  The chunk's m keys and m values are QUANTIZED FIRST, as m one-token
+// steps would quantize them: the 2 * m 4-lane groups of wave 0 do one quantize_head16 each (16 divisions per lane; every group
+// redoing all 2 * m of them would cost up to 256) and publish bytes and scales through LDS; wave 1 stages the m queries.  Once *pos is
+// known, the registers that hold slots [*pos, *pos + m) take the chunk's bytes and scales (and store them): they hold the cache
+// as it will be after the step.  Then, per query j, the one-token kernel's arithmetic at position *pos + j: a slot that query j
+// does not attend takes row j's own bytes AND scales through the masks (0 * NaN of a stale value scale would reach the output)
+// and a score of -inf.  Partials, indexed by row r = b * m + j, outputs and cache are bit-identical to m one-token calls'.  Three
+// barriers per query, as in the one-token kernel.  (Its own loops and reduction, written out: see the header of this file.)
+struct ChunkKv8Args {
+  const void* qkv; uint8_t* q; float* scale; const long long* pos; float* ws;
+  long long qkv_rs, q_bs, scale_bs;
+  int B, H, cap, nsplit, m; float scale_l2e;
+  const int* first;
+};
+template <typename T, bool RAGGED = false>
+__global__ __launch_bounds__(256) void attn_decode_chunk_kv8_kernel(const ChunkKv8Args p) {
+  __shared__ __attribute__((aligned(16))) float red_o[64 * RED_LD];
+  __shared__ float red_p[4][64];
+  __shared__ float red_m[4], red_l[64];
+  __shared__ __attribute__((aligned(16))) u32x4 sq[MAX_M][8];               // queries: row j, 16-byte word of the head (16-bit)
+  __shared__ __attribute__((aligned(16))) u32x4 skv[2][MAX_M][4];           // K | V of row j as E4M3 bytes
+  __shared__ float sscale[2][MAX_M];                                        // and their scales
+  const int t = threadIdx.x, part = t & 3, kg = t >> 2, lane = t & 63, wave = t >> 6;
+  const int split = blockIdx.x, head = blockIdx.y, b = blockIdx.z;
+  const int hp = p.H * HD;
+  // the chunk's rows first: the wait for them then leaves the cache rows in flight.  Wave 0: group kg = 2 * j + (K | V) holds one
+  // head of 64 elements, 16 per lane; wave 1: lane = 8 * j + word of query j.  (Groups / lanes past the chunk redo its last row
+  // and publish nothing: the shuffles of the quantization run with every lane of the wave.)
+  const T* rows = reinterpret_cast<const T*>(p.qkv) + (long long)b * p.m * p.qkv_rs + head * HD;
+  u32x4 st0 = {0u, 0u, 0u, 0u}, st1 = {0u, 0u, 0u, 0u};
+  const int g2 = kg < 2 * p.m ? kg : 2 * p.m - 1;                           // wave 0: kg = 0 ... 15
+  const int qj = (lane >> 3) < p.m ? (lane >> 3) : p.m - 1;
+  if (wave == 0) {
+    const T* src = rows + (long long)(g2 >> 1) * p.qkv_rs + (1 + (g2 & 1)) * hp + part * 16;
+    st0 = *reinterpret_cast<const u32x4*>(src); st1 = *reinterpret_cast<const u32x4*>(src + 8);
+  } else if (wave == 1) {
+    st0 = *reinterpret_cast<const u32x4*>(rows + (long long)qj * p.qkv_rs + (lane & 7) * 8);
+  }
+  // planes of this (batch row, head): keys at kq / ks, values one plane (H * cap rows) further
+  const size_t prow = (size_t)head * p.cap, plane = (size_t)p.H * p.cap;
+  uint8_t* kq = p.q + b * p.q_bs + prow * HD + part * 16;
+  float* ks = p.scale + b * p.scale_bs + prow;
+  u32x4 kc[2], vc[2]; uint32_t ksc[2], vsc[2];
+  int first_b = 0;
+  if (RAGGED) first_b = p.first[b];          // requested with the cache rows, ahead of *pos
+#pragma unroll
+  for (int ps = 0; ps < 2; ++ps) {
+    const int key = split * SPLIT_KEYS + ps * 64 + kg;
+    const int krow = key < p.cap ? key : p.cap - 1;          // requested whatever *pos says
+    kc[ps] = ld_stream<u32x4>(kq + (size_t)krow * HD);
+    vc[ps] = ld_stream<u32x4>(kq + (plane + krow) * HD);
+    ksc[ps] = ld_stream<uint32_t>(ks + krow);
+    vsc[ps] = ld_stream<uint32_t>(ks + plane + krow);
+  }
+  // (the scheduler otherwise sinks the 16-byte loads below the quantization, behind the wait for the qkv rows)
+  __builtin_amdgcn_sched_barrier(0);
+  if (wave == 0) {                           // the chunk's keys and values, quantized while the loads fly
+    float s;
+    const u32x4 q16 = quantize_head16<T>(st0, st1, s);
+    if (kg < 2 * p.m) {
+      skv[kg & 1][kg >> 1][part] = q16;
+      if (part == 0) sscale[kg & 1][kg >> 1] = s;
+    }
+  } else if (wave == 1) {
+    if ((lane >> 3) < p.m) sq[lane >> 3][lane & 7] = st0;
+  }
+  const long long pos = *p.pos;
+  __syncthreads();
+#pragma unroll
+  for (int ps = 0; ps < 2; ++ps) {
+    const int key = split * SPLIT_KEYS + ps * 64 + kg;
+    const long long off = key - pos;
+    const bool own = off >= 0 && off < p.m && key < p.cap;          // a slot of the chunk: row `off` of this cache row
+    const int i = own ? (int)off : 0;
+    const u32x4 kn = skv[0][i][part], vn = skv[1][i][part];
+    const uint32_t kns = __float_as_uint(sscale[0][i]), vns = __float_as_uint(sscale[1][i]);
+    const uint32_t mk = own ? 0xffffffffu : 0u;
+    kc[ps] = (kc[ps] & ~mk) | (kn & mk);
+    vc[ps] = (vc[ps] & ~mk) | (vn & mk);
+    ksc[ps] = (ksc[ps] & ~mk) | (kns & mk);
+    vsc[ps] = (vsc[ps] & ~mk) | (vns & mk);
+    if (own) {                               // stored for the steps to come (by the lanes that loaded this slot)
+      *reinterpret_cast<u32x4*>(kq + (size_t)key * HD) = kn;
+      *reinterpret_cast<u32x4*>(kq + (plane + key) * HD) = vn;
+      if (part == 0) { ks[key] = __uint_as_float(kns); ks[plane + key] = __uint_as_float(vns); }
+    }
+  }
+  for (int j = 0; j < p.m; ++j) {
+    float qf[16];
+    unpack8<T>(sq[j][2 * part], qf); unpack8<T>(sq[j][2 * part + 1], qf + 8);
+    const u32x4 knew = skv[0][j][part], vnew = skv[1][j][part];
+    const uint32_t kns = __float_as_uint(sscale[0][j]), vns = __float_as_uint(sscale[1][j]);
+    const long long posj = pos + j;
+    const long long first = RAGGED ? clamp_first(first_b, posj) : 0;
+    float sc[2], m_loc = -INFINITY;
+    u32x4 vj[2]; uint32_t vsj[2];
+#pragma unroll
+    for (int ps = 0; ps < 2; ++ps) {
+      const int key = split * SPLIT_KEYS + ps * 64 + kg;
+      const bool valid = (!RAGGED || key >= first) && key <= posj && key < p.cap;
+      // a slot that query j does not attend takes row j's own bytes and scales: whatever the cache holds there never enters a product
+      const uint32_t mk = valid ? 0xffffffffu : 0u;
+      const u32x4 k16 = (kc[ps] & mk) | (knew & ~mk);
+      vj[ps] = (vc[ps] & mk) | (vnew & ~mk);
+      const float kscale = __uint_as_float((ksc[ps] & mk) | (kns & ~mk));
+      vsj[ps] = (vsc[ps] & mk) | (vns & ~mk);
+      float kf[16]; unpack16_e4m3(k16, kf);
+      float d = 0.f;
+#pragma unroll
+      for (int e = 0; e < 16; ++e) d = fmaf(qf[e], kf[e], d);
+      d += __shfl_xor(d, 1, 64); d += __shfl_xor(d, 2, 64);                  // the key's 4 lanes
+      sc[ps] = valid ? d * kscale * p.scale_l2e : -INFINITY;
+      m_loc = fmaxf(m_loc, sc[ps]);
+    }
+    m_loc = fmaxf(m_loc, __shfl_xor(m_loc, 4, 64)); m_loc = fmaxf(m_loc, __shfl_xor(m_loc, 8, 64));
+    m_loc = fmaxf(m_loc, __shfl_xor(m_loc, 16, 64)); m_loc = fmaxf(m_loc, __shfl_xor(m_loc, 32, 64));
+    // (red_m, red_l, red_o and red_p of the previous query were last read before, or by the threads that write them after, its third barrier)
+    if (lane == 0) red_m[wave] = m_loc;
+    __syncthreads();
+    const float m = fmaxf(fmaxf(red_m[0], red_m[1]), fmaxf(red_m[2], red_m[3]));
+    float o[16], l = 0.f;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) o[e] = 0.f;
+#pragma unroll
+    for (int ps = 0; ps < 2; ++ps) {
+      const float pr = (sc[ps] == -INFINITY) ? 0.f : fast_exp2(sc[ps] - m);
+      const float w = pr * __uint_as_float(vsj[ps]);
+      float vf[16]; unpack16_e4m3(vj[ps], vf);
+      l += pr;
+#pragma unroll
+      for (int e = 0; e < 16; ++e) o[e] = fmaf(w, vf[e], o[e]);
+    }
+#pragma unroll
+    for (int w4 = 0; w4 < 4; ++w4)
+      *reinterpret_cast<f32x4*>(&red_o[kg * RED_LD + part * 16 + w4 * 4]) = f32x4{o[4 * w4], o[4 * w4 + 1], o[4 * w4 + 2], o[4 * w4 + 3]};
+    if (part == 0) red_l[kg] = l;
+    __syncthreads();
+    {                                          // 64 key groups -> 4 quarter sums per column, then one: fixed order
+      const int c = t & 63, qr = t >> 6;
+      float s = 0.f;
+#pragma unroll
+      for (int g = 0; g < 16; ++g) s += red_o[(qr * 16 + g) * RED_LD + c];
+      red_p[qr][c] = s;
+    }
+    __syncthreads();
+    float* part_out = partial_of(p.ws, (size_t)b * p.m + j, p.H, head, p.nsplit, split);
+    if (t < 64) {
+      part_out[2 + t] = (red_p[0][t] + red_p[1][t]) + (red_p[2][t] + red_p[3][t]);
+      if (t == 0) {
+        float ls = 0.f;
+        for (int g = 0; g < 64; ++g) ls += red_l[g];
+        part_out[0] = m; part_out[1] = ls;
+      }
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------- host
-// What the three entry points share of their descriptors.  rows = B * m: the rows of the workspace and of the combine launch.
+// What the entry points share of their descriptors.  rows = B * m: the rows of the workspace and of the combine launch.
 struct DecodeCall {
   int dtype, B, rows, H, capacity, head_dim;
   const void* qkv; long long qkv_stride; const long long* pos;
@@ -470,6 +630,7 @@ int decode_check(const DecodeCall& c, int head_dim_rc) {
 template <typename T, bool R> constexpr auto decode_kernel(const DecodeArgs&) { return &attn_decode_kernel<T, R>; }
 template <typename T, bool R> constexpr auto decode_kernel(const ChunkArgs&) { return &attn_decode_chunk_kernel<T, R>; }
 template <typename T, bool R> constexpr auto decode_kernel(const DecodeKv8Args&) { return &attn_decode_kv8_kernel<T, R>; }
+template <typename T, bool R> constexpr auto decode_kernel(const ChunkKv8Args&) { return &attn_decode_chunk_kv8_kernel<T, R>; }
 
 // The end of a call: the combine launch (partials in split order -> out) -- or none: skip_combine, the consumer (cogv_gemv_attn /
 // cogv_gemv_attn_w8: the attention-output projection of a decode step) recombines the partials itself.
@@ -570,6 +731,24 @@ extern "C" int cogv_attention_decode_kv8(const cogv_attn_decode_kv8_desc* d, voi
   a.ws = reinterpret_cast<float*>(d->workspace);
   a.qkv_bs = d->qkv_bs; a.q_bs = d->kv_q_bs; a.scale_bs = d->kv_scale_bs;
   a.B = d->B; a.H = d->H; a.cap = d->capacity; a.nsplit = nsplit_of(d->capacity);
+  a.scale_l2e = d->scale * 1.4426950408889634f;
+  return decode_run(c, a, stream);
+}
+
+extern "C" int cogv_attention_decode_chunk_kv8(const cogv_attn_decode_chunk_kv8_desc* d, void* stream) {
+  if (!d) return COGV_ERR_UNSUPPORTED;
+  // (B * m rows go to the workspace query and the combine launch as an int)
+  if (d->m < 1 || d->m > MAX_M || (long long)d->B * d->m > (1 << 20)) return COGV_ERR_ARG;
+  const DecodeCall c = {d->dtype, d->B, d->B * d->m, d->H, d->capacity, d->head_dim, d->qkv, d->qkv_rs, d->pos, d->out, d->out_rs,
+                        d->workspace, d->workspace_bytes, d->skip_combine, d->first};
+  if (!d->kv_q || !d->kv_scale || misaligned(d->kv_q, 16) || misaligned(d->kv_scale, 4) || (d->kv_q_bs & 15)) return COGV_ERR_ARG;
+  if (d->kv_q_bs < 2LL * d->H * d->capacity * HD || d->kv_scale_bs < 2LL * d->H * d->capacity) return COGV_ERR_ARG;
+  if (const int rc = decode_check(c, COGV_ERR_UNSUPPORTED)) return rc;
+  ChunkKv8Args a;
+  a.qkv = d->qkv; a.q = reinterpret_cast<uint8_t*>(d->kv_q); a.scale = d->kv_scale; a.pos = d->pos; a.first = d->first;
+  a.ws = reinterpret_cast<float*>(d->workspace);
+  a.qkv_rs = d->qkv_rs; a.q_bs = d->kv_q_bs; a.scale_bs = d->kv_scale_bs;
+  a.B = d->B; a.H = d->H; a.cap = d->capacity; a.nsplit = nsplit_of(d->capacity); a.m = d->m;
   a.scale_l2e = d->scale * 1.4426950408889634f;
   return decode_run(c, a, stream);
 }

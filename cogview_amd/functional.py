@@ -980,15 +980,17 @@ def decode_attention(qkv, slot, heads, combine=True):
     the slot at pos_index.  combine=False: the split partials for gemv_attn / gemv_attn_w8.  A slot that carries `.first` (a
     ragged decoder: one first attended slot per cache row) hands it on; without one the calls are what they always were.
     qkv [b, m, 3 * heads * 64] with m > 1 (a chunk step: m tokens per cache row, slots pos_index ... pos_index + m - 1) goes to
-    ops.attention_decode_chunk on the 16-bit cache; the 8-bit cache has no such form."""
+    ops.attention_decode_chunk on the 16-bit cache, and to ops.attention_decode_chunk_kv8 on an 8-bit slot that carries the mark
+    `.chunk` (KV8Cache(..., chunk=True): a decoder built with kv_chunk=True -- opt-in; a later change makes it the default).  A
+    plain StaticKV8Slot raises for such a step, as it always did."""
     kw = {} if combine else {"combine": False}
     if getattr(slot, "first", None) is not None:
         kw["first"] = slot.first
     kv8 = getattr(slot, "scale", None) is not None
     if qkv.dim() == 3 and qkv.shape[1] > 1:
-        if kv8:
+        if kv8 and not getattr(slot, "chunk", False):
             raise NotImplementedError("the 8-bit key/value cache serves one-token decode steps only: use kv=None for chunk steps")
-        op = ops.attention_decode_chunk
+        op = ops.attention_decode_chunk_kv8 if kv8 else ops.attention_decode_chunk
     else:
         op = ops.attention_decode_kv8 if kv8 else ops.attention_decode
     res = op(qkv, slot if kv8 else slot.cache, slot.pos_index, heads, **kw)

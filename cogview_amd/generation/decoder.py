@@ -29,7 +29,8 @@ def unwrap(model):
 MAX_STEP_ROWS = 8          # rows of one decode step: what the skinny products and the chunk attention take
 
 
-def refuse_unsupported(weights=None, kv=None, ragged=False, args=None, model=None, batch=None, use=None, chunk=0, wide=False):
+def refuse_unsupported(weights=None, kv=None, ragged=False, args=None, model=None, batch=None, use=None, chunk=0, wide=False,
+                       kv_chunk=False):
     """The one rule for what the decode step's options do not cover, applied before anything is allocated or quantized.
     Asked for: weights= / kv= (formats), ragged=True and chunk=C (a second step of C tokens per cache row: 2 <= C <= 8 and
     batch * C <= 8 rows, on the 16-bit cache).  Known, each optional: `args` (a caller's .is_sparse), `model` (its storage
@@ -37,7 +38,10 @@ def refuse_unsupported(weights=None, kv=None, ragged=False, args=None, model=Non
     advises instead (a caller's host form; default: the decoder's own plain options).  Sparse generation and model parallelism > 1
     are refused for every caller that hands in `args`, with or without options; a plain decoder refuses nothing.
     wide=True (opt-in; a later change makes it the default): with weights= set, 9 ... 64 rows are put to the wide products' launch
-    plan (functional.decode_wide_q_supported) instead of being refused as more than 8 rows.  False: every refusal is what it was."""
+    plan (functional.decode_wide_q_supported) instead of being refused as more than 8 rows.  False: every refusal is what it was.
+    kv_chunk=True (opt-in; a later change makes it the default): chunk=C together with kv= is accepted (the chunk step on the 8-bit
+    cache, ops.attention_decode_chunk_kv8) under the same limits 2 <= C <= 8 and batch * C <= 8; with kv=None or chunk=0 it does
+    nothing.  False: every refusal is what it was."""
     from ..mpu.initialize import mp_world_size_or_1
     if weights is not None and weights not in WEIGHT_FORMATS:
         raise ValueError(f"weights={weights!r}: None (16-bit) or one of {WEIGHT_FORMATS}")
@@ -54,7 +58,7 @@ def refuse_unsupported(weights=None, kv=None, ragged=False, args=None, model=Non
     if use is None:
         off = {"ragged": False, "chunk": 0}
         use = ", ".join(f"{name}={off.get(name)}" for name in asked)
-    if chunk and kv is not None:
+    if chunk and kv is not None and not kv_chunk:
         raise NotImplementedError(f"chunk={chunk} with kv={kv!r}: the 8-bit cache quantizes a key before it is attended, so it serves "
                                   f"one-token steps only -- use kv=None")
     if args is not None:
@@ -85,7 +89,7 @@ def refuse_unsupported(weights=None, kv=None, ragged=False, args=None, model=Non
 
 
 class GraphDecoder:
-    def __init__(self, model, batch=1, capacity=1152, weights=None, kv=None, ragged=False, chunk=0, wide=False):
+    def __init__(self, model, batch=1, capacity=1152, weights=None, kv=None, ragged=False, chunk=0, wide=False, kv_chunk=False):
         """model: GPT2Model (optionally inside FP16_Module) in eval mode, dense attention; capacity: slots per cache
         (<= 4096, the gathered form's limit).
         weights="e4m3": the decode step streams 8-bit copies of the weights (OCP E4M3 bytes with one fp32 scale per row,
@@ -116,8 +120,14 @@ class GraphDecoder:
         chunk=C (2 <= C <= 8, batch * C <= 8): a SECOND step, of C tokens per cache row (step_chunk): rows b * C + j are the tokens
         of slots *pos_index + j, appended to and attended over the same caches by ops.attention_decode_chunk; capture() captures
         it as a second graph.  The Sandwich-LN scale of a chunk step is the abs-max over all its rows, as in a multi-token model
-        call, so its logits are not bit-equal to C one-token steps'.  Composes with weights= and ragged=; the 16-bit cache only.
-        0 (default): nothing is allocated or captured, the decoder is what it was.
+        call, so its logits are not bit-equal to C one-token steps'.  Composes with weights= and ragged=; the 16-bit cache only,
+        unless kv_chunk=True.  0 (default): nothing is allocated or captured, the decoder is what it was.
+        kv_chunk=True (opt-in; a later change makes it the default): chunk=C together with kv="e4m3" is accepted instead of refused.
+        The cache's slots carry the mark StaticKV8Slot.chunk and the chunk step's attention is ops.attention_decode_chunk_kv8: the
+        chunk's C keys / values are quantized, stored and attended in their dequantized form, bit for bit what C one-token steps'
+        attentions on the same rows leave.  Same limits (2 <= C <= 8, batch * C <= 8); composes with weights= and
+        ragged=.  With kv=None or chunk=0 the keyword does nothing.  False (default): every refusal, allocation and launch is
+        what it was.
         wide=True (opt-in; a later change makes it the default): with weights= set and 9 ... 64 rows the step runs layer by layer on
         the quantized copies through the wide weight-streaming products (ops.gemm_rows_w8 / ops.gemm_rows_w4; functional.decode_layers(
         wq=..., wide=True)) instead of being refused as more than 8 rows.  Composes with kv= and ragged=; chunk= keeps batch * chunk
@@ -129,7 +139,8 @@ class GraphDecoder:
         self.gpt, tr = m, m.transformer
         assert capacity <= 4096
         self.w8, self.w4, self.kv, self.first = None, None, kv, None
-        refuse_unsupported(weights, kv, ragged, model=m, batch=batch, chunk=chunk, wide=wide)
+        more = {"kv_chunk": True} if kv_chunk else {}       # handed on only where it is set
+        refuse_unsupported(weights, kv, ragged, model=m, batch=batch, chunk=chunk, wide=wide, **more)
         self.chunk = int(chunk)
         if weights == "mxfp4":
             with torch.no_grad():
@@ -156,7 +167,8 @@ class GraphDecoder:
             self.caches = [torch.zeros((batch, capacity, 2 * hp), dtype=dt, device=dev) for _ in tr.layers]
             self.slots = [StaticKVSlot(c, self.pos_index, self.table, self.first) for c in self.caches]
         else:
-            self.kv8 = KV8Cache(len(tr.layers), batch, hp // 64, capacity, self.pos_index, dev, self.first)
+            more = {"chunk": True} if kv_chunk and self.chunk else {}       # the slots' mark for chunk steps
+            self.kv8 = KV8Cache(len(tr.layers), batch, hp // 64, capacity, self.pos_index, dev, self.first, **more)
             self.caches, self.slots = None, self.kv8.slots
         self.slab = torch.zeros(8 * len(tr.layers) + 16, dtype=torch.float32, device=dev)
         self.graph, self.logits = None, None
@@ -328,10 +340,12 @@ class SamplingDecoder(GraphDecoder):
     and a run of them needs no host work.  Reference path: generation/sampling.py:139-186 (model call, filter, multinomial,
     beam score) once per token.  Use start() + generate() (step() feeds tokens from the host and is not for this mode)."""
 
-    def __init__(self, model, batch=1, capacity=1152, weights=None, kv=None, ragged=False, chunk=0, wide=False):
+    def __init__(self, model, batch=1, capacity=1152, weights=None, kv=None, ragged=False, chunk=0, wide=False, kv_chunk=False):
         """chunk=C: generate(n, widths=...) may feed runs of given ids as chunk steps (GraphDecoder's `chunk`; _step_chunk below).
-        wide: GraphDecoder's (opt-in: quantized weights at 9 ... 64 rows)."""
-        super().__init__(model, batch, capacity, weights=weights, kv=kv, ragged=ragged, chunk=chunk, wide=wide)
+        wide: GraphDecoder's (opt-in: quantized weights at 9 ... 64 rows).  kv_chunk: GraphDecoder's (opt-in; a later change makes
+        it the default: chunk=C on the 8-bit cache)."""
+        more = {"kv_chunk": True} if kv_chunk else {}
+        super().__init__(model, batch, capacity, weights=weights, kv=kv, ragged=ragged, chunk=chunk, wide=wide, **more)
         self.sampling = None
         self.chunk_steps = 0         # chunk steps run by generate() so far
 

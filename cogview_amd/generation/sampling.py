@@ -464,14 +464,18 @@ class _DeviceRun:
     .out [batch, width] receives the id drawn for sequence position out_base + j in column j; .given (DeviceFiller: [capacity],
     DeviceBatchFiller: [rows, capacity]) is the sampler's given table.  batch: the decoder's rows where the caller knows them
     before the first call (the refusal rule then also judges chunk= and weights= at that row count).  wide: SamplingDecoder's
-    opt-in keyword (quantized weights at 9 ... 64 rows), handed on only where it is set."""
+    opt-in keyword (quantized weights at 9 ... 64 rows), handed on only where it is set.  kv_chunk: SamplingDecoder's opt-in keyword
+    (opt-in; a later change makes it the default: chunk=C together with kv=), handed on only where it is set."""
     given = None
 
-    def __init__(self, model, args, seed=0, capture=True, weights=None, kv=None, ragged=False, chunk=0, batch=None, wide=False):
+    def __init__(self, model, args, seed=0, capture=True, weights=None, kv=None, ragged=False, chunk=0, batch=None, wide=False,
+                 kv_chunk=False):
+        more = {}
         if wide:
-            decoder.refuse_unsupported(weights, kv, ragged, args=args, model=model, use="filling_sequence", chunk=chunk, batch=batch, wide=True)
-        else:
-            decoder.refuse_unsupported(weights, kv, ragged, args=args, model=model, use="filling_sequence", chunk=chunk, batch=batch)
+            more["wide"] = True
+        if kv_chunk:
+            more["kv_chunk"] = True
+        decoder.refuse_unsupported(weights, kv, ragged, args=args, model=model, use="filling_sequence", chunk=chunk, batch=batch, **more)
         self.model, self.seed, self.capture, self.ragged, self.chunk = model, int(seed), capture, ragged, int(chunk)
         self.formats = {"weights": weights}           # only the keywords that are set: a default build issues the call it always did
         if kv is not None:
@@ -482,6 +486,8 @@ class _DeviceRun:
             self.formats["chunk"] = self.chunk
         if wide:
             self.formats["wide"] = True
+        if kv_chunk:
+            self.formats["kv_chunk"] = True
         self.dec, self.key, self.out = None, None, None
 
     def size(self, batch, capacity, width=None, out_base=0):
@@ -663,10 +669,14 @@ class DeviceFiller(_DeviceRun):
     tokens -- one model call in place of C replays, planned per call by plan_chunk_steps; a second graph is captured next to
     the one-token one.  The draws keep their generator counters (one per position), but a chunk step's logits differ in the last
     bits from one-token steps' (the Sandwich-LN scale spans the chunk's rows), so a draw can differ from the chunk=0 filler's
-    where two ids are about equally likely.  .model_calls: the decode steps of the last call.  0 (default): nothing changes."""
+    where two ids are about equally likely.  .model_calls: the decode steps of the last call.  0 (default): nothing changes.
+    kv_chunk=True (opt-in; a later change makes it the default): chunk=C together with kv="e4m3" is accepted -- the chunk steps run
+    on the 8-bit cache (GraphDecoder's `kv_chunk`, ops.attention_decode_chunk_kv8).  With kv=None or chunk=0 it does
+    nothing; False: the pair is refused as it always was."""
 
-    def __init__(self, model, args, seed=0, capacity=1408, capture=True, weights=None, kv=None, chunk=0):
-        super().__init__(model, args, seed, capture, weights, kv, chunk=chunk)
+    def __init__(self, model, args, seed=0, capacity=1408, capture=True, weights=None, kv=None, chunk=0, kv_chunk=False):
+        more = {"kv_chunk": True} if kv_chunk else {}
+        super().__init__(model, args, seed, capture, weights, kv, chunk=chunk, **more)
         self.size(1, capacity)
         self.scores = None
         self.model_calls = 0
@@ -721,14 +731,17 @@ class DeviceBatchFiller(_DeviceRun):
     DeviceFiller's.  Temperature, top-k / top-p and the drawable range are baked into the capture (a call with other values
     re-arms and captures again); the generator offset keeps counting across calls.
     capture / weights / kv as DeviceFiller's.  chunk=C: runs of given ids are fed as chunk steps on a second graph (rows * C <= 8
-    rows per step, 16-bit cache only).  Above 8 rows the decoder takes the wide step (9 ... 24 rows) or the tile kernels by
+    rows per step; 16-bit cache only, unless kv_chunk=True -- opt-in; a later change makes it the default: the chunk steps then run on
+    the 8-bit cache of kv="e4m3", GraphDecoder's `kv_chunk`).  Above 8 rows the decoder takes the wide step (9 ... 24 rows) or the tile kernels by
     itself; weights="e4m3" covers up to 8 rows, so it is refused above them -- unless wide=True (opt-in; a later change makes it
     the default): 9 ... 64 rows then run on the wide products of the quantized copies (GraphDecoder's `wide`: 1.05-1.17x the 16-bit
     wide step's speed at 12 ... 64 rows of the captured 4B step, not faster than the tile kernels from 48 rows on).  Dense attention, one model-parallel partition, fp16 / bf16, P + replays + 1 <= capacity
     slots."""
 
-    def __init__(self, model, args, rows, capacity=1408, seed=0, capture=True, weights=None, kv=None, chunk=0, wide=False):
-        super().__init__(model, args, seed, capture, weights, kv, ragged=True, chunk=chunk, batch=rows, wide=wide)
+    def __init__(self, model, args, rows, capacity=1408, seed=0, capture=True, weights=None, kv=None, chunk=0, wide=False,
+                 kv_chunk=False):
+        more = {"kv_chunk": True} if kv_chunk else {}
+        super().__init__(model, args, seed, capture, weights, kv, ragged=True, chunk=chunk, batch=rows, wide=wide, **more)
         if rows < 1:
             raise ValueError(f"rows = {rows} must be positive")
         self.size(rows, capacity)

@@ -136,11 +136,14 @@ class StaticKV8Slot(KVCacheSlot):
     fp32, one per (slot, head, K | V) (ops.kv_quantize_e4m3).  The decode attention on it (ops.attention_decode_kv8) quantizes
     the new token's key / value and writes them at the device-side position `pos_index`.  It travels through
     `mem=` like the other slots, but there is no 16-bit memory to append to or to gather from: whatever asks for one raises.
-    first (optional): as StaticKVSlot's."""
+    first (optional): as StaticKVSlot's.  chunk=True (a decoder built with chunk=C, kv="e4m3", kv_chunk=True): the mark by which
+    functional.decode_attention sends a step of several tokens per cache row to ops.attention_decode_chunk_kv8; without it
+    such a step raises, as it always did."""
 
-    def __init__(self, q, scale, pos_index, first=None):
+    def __init__(self, q, scale, pos_index, first=None, chunk=False):
         super().__init__(None, 0)
         self.q, self.scale, self.pos_index, self.first = q, scale, pos_index, first
+        self.chunk = bool(chunk)
 
     @property
     def capacity(self):
@@ -167,13 +170,14 @@ class StaticKV8Slot(KVCacheSlot):
 
 
 class KV8Cache:
-    """The 8-bit key/value caches of a decoder: one StaticKV8Slot per layer on shared allocations."""
+    """The 8-bit key/value caches of a decoder: one StaticKV8Slot per layer on shared allocations.  chunk=True marks the slots
+    for chunk steps (StaticKV8Slot.chunk); the allocations are the same."""
 
-    def __init__(self, layers, batch, heads, capacity, pos_index, device, first=None):
+    def __init__(self, layers, batch, heads, capacity, pos_index, device, first=None, chunk=False):
         self.q = torch.zeros((layers, batch, 2, heads, capacity, 64), dtype=torch.uint8, device=device)
         self.scale = torch.ones((layers, batch, 2, heads, capacity), dtype=torch.float32, device=device)
         self.pos_index = pos_index
-        self.slots = [StaticKV8Slot(self.q[i], self.scale[i], pos_index, first) for i in range(layers)]
+        self.slots = [StaticKV8Slot(self.q[i], self.scale[i], pos_index, first, chunk=chunk) for i in range(layers)]
 
     def dequantize(self):
         """Per layer [b, capacity, 2 * hp] fp32 (keys | values)."""

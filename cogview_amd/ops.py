@@ -821,6 +821,30 @@ def attention_decode_kv8(qkv, cache8, pos_index, heads, combine=True, first=None
     return out if combine else ws
 
 
+def attention_decode_chunk_kv8(qkv, cache8, pos_index, heads, combine=True, first=None):
+    """attention_decode_chunk on an 8-bit cache (cogv_attention_decode_chunk_kv8): qkv [b, m, 3 * heads * 64] with 1 <= m <= 8,
+    output and workspace as attention_decode_chunk's; cache8 as attention_decode_kv8's.  The chunk's m keys / values are
+    quantized, written into slots [pos, pos + m) as bytes + scales (none at or past the capacity), and attended in their
+    dequantized form; row (b, j) attends slots [first[b], pos + j].  Returns out [b, m, heads * 64], or with combine=False the
+    partials of b * m rows.  Bit-identical (outputs, partials, cache) to m attention_decode_kv8 calls at pos, pos + 1, ..."""
+    q, scale = (cache8.q, cache8.scale) if hasattr(cache8, "scale") else cache8
+    _need_gpu(qkv, q, scale, pos_index)
+    b, cap = q.shape[0], q.shape[3]
+    hp = heads * 64
+    assert qkv.dim() == 3 and qkv.shape[0] == b and qkv.shape[2] == 3 * hp
+    m = qkv.shape[1]
+    assert qkv.stride(2) == 1 and (b == 1 or qkv.stride(0) == m * qkv.stride(1)), "rows b * m + j one stride apart"
+    assert q.dtype == torch.uint8 and q.shape == (b, 2, heads, cap, 64) and q[0].is_contiguous()
+    assert scale.dtype == torch.float32 and scale.shape == (b, 2, heads, cap) and scale[0].is_contiguous()
+    assert pos_index.dtype == torch.int64
+    d, out, ws = _decode_desc(L.AttnDecodeChunkKv8Desc(), qkv, pos_index, b, heads, cap, combine, first, rows=b * m, out_shape=(b, m, hp))
+    d.m, d.qkv_rs, d.out_rs = m, qkv.stride(1), hp
+    d.kv_q, d.kv_q_bs = q.data_ptr(), q.stride(0)
+    d.kv_scale, d.kv_scale_bs = scale.data_ptr(), scale.stride(0)
+    L.check(L.lib().cogv_attention_decode_chunk_kv8(C.byref(d), _stream()), "cogv_attention_decode_chunk_kv8")
+    return out if combine else ws
+
+
 def gemv_attn(partials, batch, heads, capacity, w, bias=None, absmax=None):
     """Attention-output projection of a decode step with the split-combine as its prologue (cogv_gemv_attn):
     out [batch, N] = (combined attention output [batch, heads * 64]) . w^T + bias.  `partials`: what

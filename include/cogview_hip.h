@@ -418,7 +418,7 @@ int cogv_attention_decode(const cogv_attn_decode_desc* d, void* stream);
  * cogv_attention_decode with B * m rows -- workspace: cogv_attention_decode_workspace_bytes(B * m, H, capacity); skip_combine,
  * cogv_gemv_attn and cogv_gemv_attn_w8 (M = B * m) as there -- but a workgroup loads its 128 keys and values ONCE for the m
  * queries.  Output, partials and cache are bit-identical to m successive cogv_attention_decode calls at *pos, *pos + 1, ...;
- * m = 1 is that call.  The 8-bit cache has no such form.
+ * m = 1 is that call.  The 8-bit cache's form is cogv_attention_decode_chunk_kv8.
  * 1 (bad argument): m outside [1, 8], misaligned qkv / cache (16 B) / first (4 B), strides % 8, short workspace; 3
  * (unsupported): other dtypes, head_dim != 64. */
 typedef struct cogv_attn_decode_chunk_desc {
@@ -470,6 +470,34 @@ typedef struct cogv_attn_decode_kv8_desc {
 } cogv_attn_decode_kv8_desc;
 /* one decode step's attention per layer on the 8-bit cache (the model call of generation/sampling.py:139-148) */
 int cogv_attention_decode_kv8(const cogv_attn_decode_kv8_desc* d, void* stream);
+/* cogv_attention_decode_chunk on that cache (generation/sampling.py:139-148 makes one model call per token, also for a token that
+ * is already known; a run of m known tokens is one call here, on the 8-bit cache as on the 16-bit one).  Rows r = b * m + j: qkv
+ * [B * m][3 * H * 64] (qkv_rs), out [B * m][H * 64] (out_rs), as in cogv_attn_decode_chunk_desc; kv_q / kv_scale as in
+ * cogv_attn_decode_kv8_desc.  The chunk's m keys and m values are QUANTIZED FIRST (the rule of cogv_kv_quantize_e4m3), WRITTEN into
+ * slots [*pos, *pos + m) below the capacity as bytes + scales, and attended in their dequantized form; row (b, j) attends slots
+ * [first[b], *pos + j].  A slot that a row does not attend -- past its own, below first[b], at or past the capacity -- is without
+ * influence whatever bytes AND scales it holds (NaN included); a row whose slot lies at or past the capacity writes nothing and
+ * attends [first[b], capacity).  *pos stays device data and the cache loads are issued before it is read.  Grid, the 128 keys per
+ * split and the 66-float partials are cogv_attention_decode's with B * m rows: workspace
+ * cogv_attention_decode_workspace_bytes(B * m, H, capacity); skip_combine, cogv_gemv_attn and cogv_gemv_attn_w8 (M = B * m) as
+ * there.  Output, partials and the cache's bytes and scales are bit-identical to m successive cogv_attention_decode_kv8 calls at
+ * *pos, *pos + 1, ...; m = 1 is that call.
+ * 1 (bad argument): m outside [1, 8], B * m > 2^20, misaligned qkv / kv_q (16 B) / kv_scale / first (4 B), qkv_rs % 8, kv_q_bs % 16,
+ * short kv_q_bs / kv_scale_bs / workspace; 3 (unsupported): a NULL descriptor, other dtypes, head_dim != 64. */
+typedef struct cogv_attn_decode_chunk_kv8_desc {
+  int dtype; int B, H, capacity, head_dim;
+  int m;                             /* tokens per cache row, 1 ... 8 */
+  float scale;                       /* 1/sqrt(head_dim) */
+  const void* qkv; long long qkv_rs;
+  void* kv_q; long long kv_q_bs;
+  float* kv_scale; long long kv_scale_bs;
+  void* out; long long out_rs;
+  const long long* pos;
+  void* workspace; size_t workspace_bytes;
+  int skip_combine;
+  const int* first;                  /* NULL, or int32 [B] */
+} cogv_attn_decode_chunk_kv8_desc;
+int cogv_attention_decode_chunk_kv8(const cogv_attn_decode_chunk_kv8_desc* d, void* stream);
 /* Sparse training form, backward: cogv_attention_bwd with sparse_window > 0 writes dq as usual, but dk / dv are
  * SLOT-SPACE buffers [B * s_q / sparse_window][s_k slots][H][64] (dk_bs / dv_bs = the stride of one (batch, query block)
  * plane) -- the gradient of each gathered copy of a key, the same quantity the reference's autograd holds for pivot_k

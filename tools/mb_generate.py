@@ -12,7 +12,8 @@ difference, peak allocated memory of each), ranked by rerank_generated, the best
 of the weights (generate_on_device / DeviceFiller `weights=`), timed next to the 16-bit ones.  `--kv e4m3`: the same legs with the
 8-bit key/value cache (`kv=`), alone or together with `--weights`.  `--chunk C` (`--super-resolution` leg): the same image again in
 the same process with DeviceFiller(chunk=C) -- runs of given ids fed as chunk steps of C tokens -- next to the chunk=0 leg above:
-seconds per image, model calls, and ms per replay of the one-token and of the chunk graph.
+seconds per image, model calls, and ms per replay of the one-token and of the chunk graph.  With `--kv e4m3` the chunk leg runs
+once more on the 8-bit cache (DeviceFiller(chunk=C, kv="e4m3", kv_chunk=True), the opt-in).
 `--super-resolution --images 1,4,8,16` (alone: no other leg runs): G images of different text lengths on ONE decode graph
 (magnify_batch with DeviceBatchFiller(rows=G)), also rows=2 chunk=4 and rows=4 chunk=2, against images one after another
 (magnify with DeviceFiller, chunk=0 and chunk=8, timed at the start and at the end of the process); seconds per image for each.
@@ -167,8 +168,9 @@ if SR:
         assert big8.shape == (1, 4096) and int(big8.max()) < 8192
         print(f"DeviceFiller weights={W8} kv={KV8}: {t_w8:.2f} s (quantization + prefills + capture included), "
               f"{t_w8 / (replays + len(plans)) * 1e3:.2f} ms per model call; {t_dev / t_w8:.2f}x the 16-bit device form", flush=True)
-    if CHUNK:
-        filler_c = DeviceFiller(model, args, seed=1, chunk=CHUNK)
+    def chunk_leg(**formats):
+        """the same image with DeviceFiller(chunk=CHUNK, **formats): seconds, model calls, ms per replay of both graphs"""
+        filler_c = DeviceFiller(model, args, seed=1, chunk=CHUNK, **formats)
         calls = []
 
         def fill_c(model_, seq, args_, invalid_slices=None, tokenizer=None):
@@ -190,10 +192,20 @@ if SR:
             torch.cuda.synchronize()
             return (time.time() - t0) / n * 1e3
 
-        print(f"DeviceFiller chunk={CHUNK}: {t_c:.2f} s per image (prefills + capture of both graphs included) against "
+        what = "".join(f" {k}={v}" for k, v in formats.items())
+        cache = dec.kv8.tensors() if dec.kv8 is not None else dec.caches
+        print(f"DeviceFiller chunk={CHUNK}{what}: {t_c:.2f} s per image (prefills + capture of both graphs included) against "
               f"{t_dev:.2f} s with chunk=0 in this process ({t_dev / t_c:.3f}x); {sum(calls)} decode calls of which {dec.chunk_steps} "
               f"chunk steps, against {replays}; one-token replay {replay_ms(dec.graph):.2f} ms, chunk replay "
-              f"{replay_ms(dec.graph_chunk):.2f} ms", flush=True)
+              f"{replay_ms(dec.graph_chunk):.2f} ms; resident cache {sum(t.numel() * t.element_size() for t in cache) / 2 ** 30:.3f} GiB", flush=True)
+        return t_c
+
+    if CHUNK:
+        t_c16 = chunk_leg()
+        if KV8:
+            # the chunk steps on the 8-bit cache (opt-in: kv_chunk=True), in the same process as the 16-bit chunk leg above
+            t_c8 = chunk_leg(**({"weights": W8} if W8 else {}), kv=KV8, kv_chunk=True)
+            print(f"chunk={CHUNK} on the 8-bit cache: {t_c16 / t_c8:.3f}x the 16-bit cache's chunk={CHUNK} filler", flush=True)
     sys.exit(0)
 args = types.SimpleNamespace(temperature=1.0, top_k=200, top_p=0.0, is_sparse=0)
 
