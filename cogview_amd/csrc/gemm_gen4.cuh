@@ -49,14 +49,42 @@ __device__ __forceinline__ void mfma16_inplace(f32x4& c, const typename HT<T>::v
   else
     asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
 }
-// LDS-DMA of 16 bytes per lane in the "SGPR base + 32-bit lane offset" form, LDS destination (wave-uniform) through M0
-__device__ __forceinline__ void dma16(const void* base, uint32_t lane_off, uint32_t lds_addr) {
-  const uint64_t b64 = (uint64_t)(uintptr_t)base;
+// The first MFMA of an item on an accumulator block: C = 0 as an inline constant, the block is written, not updated -- no
+// clearing pass over the 256 AGPRs in front of the k-loop (the matrix pipe idles through one).
+template <typename T>
+__device__ __forceinline__ void mfma16_first(f32x4& c, const typename HT<T>::v8& a, const typename HT<T>::v8& b) {
+  if constexpr (std::is_same<T, bf16_t>::value)
+    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=a"(c) : "v"(a), "v"(b));
+  else
+    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=a"(c) : "v"(a), "v"(b));
+}
+// LDS-DMA of 16 bytes per lane in the "SGPR base + 32-bit lane offset" form, LDS destination (wave-uniform) through M0.
+// M0 must NOT be written by a scalar add directly in front of the DMA: `s_add_i32 m0, s, imm` followed at once by
+// global_load_lds_dwordx4 sends pieces to a stale destination on the MI355X (measured: every product of two or more k-tiles
+// wrong), while `s_mov_b32 m0, s` in the same place works.  So either the destination is computed into a temporary and moved
+// (dma16: the prologue, 32 pieces per item) or the add into M0 goes out at least one instruction AHEAD of its DMA (w4_set_m0 /
+// dma16_issue: the k-loop puts an MFMA between them, and no temporary and no move remain there).
+template <typename P>
+__device__ __forceinline__ const P* sgpr_ptr(const P* p) {           // a wave-uniform pointer, in scalar registers
+  const uint64_t b64 = (uint64_t)(uintptr_t)p;
   const uint64_t bu = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(b64 >> 32)) << 32) |
                       (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)b64);
-  base = reinterpret_cast<const void*>((uintptr_t)bu);
+  return reinterpret_cast<const P*>((uintptr_t)bu);
+}
+__device__ __forceinline__ void dma16(const void* base, uint32_t lane_off, uint32_t lds_addr) {
+  base = sgpr_ptr(reinterpret_cast<const char*>(base));
   lds_addr = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_addr);
   asm volatile("s_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(lane_off), "s"(base), "s"(lds_addr) : "memory", "m0");
+}
+// the wave's LDS base plus the compile-time (operand, buffer, granule, piece) offset, added straight into M0 ...
+template <int LOFF>
+__device__ __forceinline__ void w4_set_m0(uint32_t lds_base) {
+  asm volatile("s_add_i32 m0, %0, %1" : : "s"(lds_base), "n"(LOFF) : "m0");
+}
+// ... for the DMA that follows it with nothing but MFMAs (asm volatile, order pinned) in between: M0 stays what it was set to
+__device__ __forceinline__ void dma16_issue(const void* base, uint32_t lane_off) {
+  base = sgpr_ptr(reinterpret_cast<const char*>(base));
+  asm volatile("global_load_lds_dwordx4 %0, %1" : : "v"(lane_off), "s"(base) : "memory");
 }
 template <int V> using IC = std::integral_constant<int, V>;
 template <typename F, int... R>
@@ -216,7 +244,8 @@ void gemm_w4_kernel(const GroupArgs ga) {
   const int wr = wave >> 1, wc = wave & 1;
   const int l15 = lane & 15, kb = lane >> 4;
   const int nitems = ga.item_start[ga.count];
-  const uint32_t smem_u32 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)smem);
+  // LDS base of this wave's DMA pieces (piece i of a granule lands at (i * NW + wave) KiB): the rest of a destination is an immediate
+  const uint32_t dma_lds = (uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)(uintptr_t)smem + (uint32_t)wave * 1024u));
 
   struct Item {
     int pi, m0, n0, ksplit, kt0, nk;
@@ -279,39 +308,36 @@ void gemm_w4_kernel(const GroupArgs ga) {
     }
   };
   // one piece of granule gi from k-tile source `src` (an operand base of an item, already advanced to the k-tile)
-  auto dma_from = [&](const char* src, const Item& it, int gi, int i, int buf) {
+  auto dma_from = [&](const char* src, const Item& it, auto gic, auto ic, auto bufc) {
     if (COGV_EXP & 1) return;
-    const bool isB = gi >= 2;
-    const uint32_t l = smem_u32 + (uint32_t)((isB ? BREG : 0) + buf * BUF + (gi & 1) * GRAN + (i * NW + wave) * 1024);
-    dma16(src, it.off[gi][i], l);
+    constexpr int gi = decltype(gic)::value, i = decltype(ic)::value, buf = decltype(bufc)::value;
+    dma16(src, it.off[gi][i], dma_lds + (uint32_t)((gi >= 2 ? BREG : 0) + buf * BUF + (gi & 1) * GRAN + i * NW * 1024));
   };
-  auto dma = [&](const Item& it, int gi, int i, int kt, int buf) {
-    const GemmArgs& p = ga.g[it.pi];
-    const bool isB = gi >= 2;
-    const bool trn = isB ? BT : AT;
-    const int ld = isB ? p.ldb : p.lda;
-    const size_t kstride = trn ? (size_t)KT * ld * 2 : (size_t)KT * 2;
-    dma_from((isB ? it.baseB : it.baseA) + (size_t)kt * kstride, it, gi, i, buf);
+  // the same in two parts for the k-loop: M0 one MFMA ahead, then the DMA alone
+  auto dma_m0 = [&](auto gic, auto ic, auto bufc) {
+    if (COGV_EXP & 1) return;
+    constexpr int gi = decltype(gic)::value, i = decltype(ic)::value, buf = decltype(bufc)::value;
+    w4_set_m0<(gi >= 2 ? BREG : 0) + buf * BUF + (gi & 1) * GRAN + i * NW * 1024>(dma_lds);
+  };
+  auto dma_go = [&](const char* src, const Item& it, auto gic, auto ic) {
+    if (COGV_EXP & 1) return;
+    constexpr int gi = decltype(gic)::value, i = decltype(ic)::value;
+    dma16_issue(src, it.off[gi][i]);
   };
   // two whole k-tiles, in the order the loop certifies them: [A01 B01](0) [B23 A23](0) [A01 B01](1) [B23 A23](1)
   auto prologue = [&](const Item& it) {
-    const int t1 = min(1, it.nk - 1);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) dma(it, G_A01, i, 0, 0);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) dma(it, G_B01, i, 0, 0);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) dma(it, G_B23, i, 0, 0);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) dma(it, G_A23, i, 0, 0);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) dma(it, G_A01, i, t1, 1);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) dma(it, G_B01, i, t1, 1);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) dma(it, G_B23, i, t1, 1);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) dma(it, G_A23, i, t1, 1);
+    const GemmArgs& p = ga.g[it.pi];
+    const size_t ksA = AT ? (size_t)KT * p.lda * 2 : (size_t)KT * 2, ksB = BT ? (size_t)KT * p.ldb * 2 : (size_t)KT * 2;
+    const char* const a1 = it.nk > 1 ? it.baseA + ksA : it.baseA;
+    const char* const b1 = it.nk > 1 ? it.baseB + ksB : it.baseB;
+    static_for<4>([&](auto ic) { dma_from(it.baseA, it, IC<G_A01>{}, ic, IC<0>{}); });
+    static_for<4>([&](auto ic) { dma_from(it.baseB, it, IC<G_B01>{}, ic, IC<0>{}); });
+    static_for<4>([&](auto ic) { dma_from(it.baseB, it, IC<G_B23>{}, ic, IC<0>{}); });
+    static_for<4>([&](auto ic) { dma_from(it.baseA, it, IC<G_A23>{}, ic, IC<0>{}); });
+    static_for<4>([&](auto ic) { dma_from(a1, it, IC<G_A01>{}, ic, IC<1>{}); });
+    static_for<4>([&](auto ic) { dma_from(b1, it, IC<G_B01>{}, ic, IC<1>{}); });
+    static_for<4>([&](auto ic) { dma_from(b1, it, IC<G_B23>{}, ic, IC<1>{}); });
+    static_for<4>([&](auto ic) { dma_from(a1, it, IC<G_A23>{}, ic, IC<1>{}); });
   };
 
   // per-lane fragment addresses inside a granule (k-step 0): v_mfma_f32_16x16x32, lane l supplies row (l & 15)
@@ -337,15 +363,25 @@ void gemm_w4_kernel(const GroupArgs ga) {
     if (isB ? BT : AT) tr_issue16_o<off + ks * 32 * ROWB, ROWB>(isB ? adB[0][blk] : adA[0][blk], f.t[ks][blk]);
     else nat_issue_o<off>(isB ? adB[ks][blk] : adA[ks][blk], f.n[ks][blk]);
   };
+  // ONE wait for the eight fragments of a register set: all of them are in/out operands of the statement, so no use of
+  // any of them can be scheduled in front of it (build.py's hazard scan checks the result).  `land` waits; `tie` emits no
+  // instruction and puts a second set behind the wait in front of it (the pre-step: two sets are 32 operands, more than
+  // one asm statement takes).
+#define W4_FRAG_OPS_T(f_) "+v"(f_.t[0][0].lo), "+v"(f_.t[0][0].hi), "+v"(f_.t[0][1].lo), "+v"(f_.t[0][1].hi), "+v"(f_.t[0][2].lo), \
+    "+v"(f_.t[0][2].hi), "+v"(f_.t[0][3].lo), "+v"(f_.t[0][3].hi), "+v"(f_.t[1][0].lo), "+v"(f_.t[1][0].hi), "+v"(f_.t[1][1].lo),   \
+    "+v"(f_.t[1][1].hi), "+v"(f_.t[1][2].lo), "+v"(f_.t[1][2].hi), "+v"(f_.t[1][3].lo), "+v"(f_.t[1][3].hi)
+#define W4_FRAG_OPS_N(f_) "+v"(f_.n[0][0]), "+v"(f_.n[0][1]), "+v"(f_.n[0][2]), "+v"(f_.n[0][3]), "+v"(f_.n[1][0]), "+v"(f_.n[1][1]), \
+    "+v"(f_.n[1][2]), "+v"(f_.n[1][3])
   auto land = [&](Frag& f, bool trn) {
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int b = 0; b < 4; ++b) {
-        if (trn) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f.t[ks][b].lo), "+v"(f.t[ks][b].hi) : : "memory");
-        else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f.n[ks][b]) : : "memory");
-      }
+    if (trn) asm volatile("s_waitcnt lgkmcnt(0)" : W4_FRAG_OPS_T(f) : : "memory");
+    else asm volatile("s_waitcnt lgkmcnt(0)" : W4_FRAG_OPS_N(f) : : "memory");
   };
+  auto tie = [&](Frag& f, bool trn) {
+    if (trn) asm volatile("" : W4_FRAG_OPS_T(f) : : "memory");
+    else asm volatile("" : W4_FRAG_OPS_N(f) : : "memory");
+  };
+#undef W4_FRAG_OPS_T
+#undef W4_FRAG_OPS_N
 
   // Work items are taken from the XCD's queue TWO ahead (round 4): while item i is computed the index of item i + 1 is
   // already known, so that its first two k-tiles can ride in the DMA slots of item i's last two k-tiles (cross-item
@@ -371,13 +407,17 @@ void gemm_w4_kernel(const GroupArgs ga) {
   while (item < nitems) {
     const GemmArgs& p = ga.g[cur.pi];
     const int nk = cur.nk;
-    f32x4 acc[2][8][4];                // [column half][16-row block 4a+i][16-column block j]
+    // [column half][16-row block 4a+i][16-column block j].  Not cleared: k-step 0 of each quarter-step of the item's first
+    // k-tile WRITES its 16 blocks (mfma16_first), and every path into the k-loop below starts with such a k-tile.
+    f32x4 acc[2][8][4];
+    if (COGV_EXP & 4) {                // probe without MFMAs: nothing else writes them
 #pragma unroll
-    for (int b = 0; b < 2; ++b)
+      for (int b = 0; b < 2; ++b)
 #pragma unroll
-      for (int i = 0; i < 8; ++i)
+        for (int i = 0; i < 8; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[b][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+          for (int j = 0; j < 4; ++j) acc[b][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
 
     Frag fA, fI, fB0, fB1;
     // pre-step: the first A01 / B01 fragments (the only exposed LDS latency of the item)
@@ -390,6 +430,10 @@ void gemm_w4_kernel(const GroupArgs ga) {
     // (Also measured in round 3, removed: issuing the work-queue atomic by hand and reading it after the k-loop -- no
     //  change, profiles/r03_gemm_async_grab_peel_ab_v1.log.)
     if (!certified) wait_vmcnt<24>();
+    // lgkmcnt(0) through the builtin, so that the compiler's own counter model is settled HERE: it cannot see the asm waits
+    // below, and a result it still believes in flight (the queue read, a scalar load of the epilogue) otherwise costs a
+    // wait of its own at that register's first use inside the k-loop
+    __builtin_amdgcn_s_waitcnt(0xc07f);
     __builtin_amdgcn_s_barrier();
     W4_TS(0);
     int grabbed = 0;                                       // the item after the next: asked for now, used after the k-loop
@@ -411,21 +455,34 @@ void gemm_w4_kernel(const GroupArgs ga) {
       set_bases(p, nx);
       xp = cur.m0 + TBM <= p.M && cur.n0 + TBN <= p.N && nx.m0 + TBM <= p.M && nx.n0 + TBN <= p.N;
     }
-    const char* const xA = xp ? nx.baseA : cur.baseA;      // source of the k-tiles past this item's end
-    const char* const xB = xp ? nx.baseB : cur.baseB;
-    const size_t ksA = AT ? (size_t)KT * p.lda * 2 : (size_t)KT * 2, ksB = BT ? (size_t)KT * p.ldb * 2 : (size_t)KT * 2;
+    // source of the k-tiles past this item's end (the next tile's coordinates come from the VALU: back to scalar registers)
+    const char* const xA = sgpr_ptr(xp ? nx.baseA : cur.baseA);
+    const char* const xB = sgpr_ptr(xp ? nx.baseB : cur.baseB);
+    size_t ksA = AT ? (size_t)KT * p.lda * 2 : (size_t)KT * 2, ksB = BT ? (size_t)KT * p.ldb * 2 : (size_t)KT * 2;
+    if (AT) pin_s(ksA);
+    if (BT) pin_s(ksB);
+    // Running sources of the DMA slots: k-tile kt + 2 of this item while there is one, then -- switched once, by the k-tile
+    // with kt + 2 == nk -- what follows the item: the next item's k-tiles 0 and 1 (cross-item prefetch) or, without it,
+    // this item's own k-tiles 0 and 1 once more (never read: the prologue path re-issues both buffers; they only keep the
+    // DMA count of every half-step the same).  One 64-bit add per operand and k-tile, no multiplication by the k-tile index.
+    // (pin_s: the selects and adds stay on the scalar unit; left alone the compiler moves the whole chain to the VALU)
+    const char* pA = nk > 2 ? cur.baseA + 2 * ksA : xA;
+    const char* pB = nk > 2 ? cur.baseB + 2 * ksB : xB;
+    pin_s(pA); pin_s(pB);
     static_for<8>([&](auto rc) {
       constexpr int r = decltype(rc)::value;
       read1(fA, IC<G_A01>{}, IC<0>{}, IC<(r >> 2)>{}, IC<(r & 3)>{});
       read1(fB0, IC<G_B01>{}, IC<0>{}, IC<(r >> 2)>{}, IC<(r & 3)>{});
     });
-    land(fA, AT); land(fB0, BT);
+    land(fA, AT); tie(fB0, BT);
     W4_TS(1);
 
     // one quarter-step: acc[bh][4 ah + i][j] += A(fa) x B(fb) while granule gin of buffer bin is read into fin and
     // granule gd of k-tile ktd is DMA'd into buffer bd
-    auto quarter = [&](auto ahc, auto bhc, Frag& fa, Frag& fb, Frag& fin, auto ginc, auto binc, int gd, const char* gsrc, int bd) {
+    // (firstc: the item's first k-tile -- k-step 0 starts the 16 accumulator blocks of the quarter-step from C = 0)
+    auto quarter = [&](auto firstc, auto ahc, auto bhc, Frag& fa, Frag& fb, Frag& fin, auto ginc, auto binc, auto gdc, const char* gsrc, auto bdc) {
       constexpr int ah = decltype(ahc)::value, bh = decltype(bhc)::value, gin = decltype(ginc)::value;
+      constexpr bool first = decltype(firstc)::value != 0;
       static_for<8>([&](auto rc) {
           constexpr int r = decltype(rc)::value, ks = r >> 2, i = r & 3;
           // the 8 incoming fragments go out in front of the first four MFMA groups (two each: >= 256 MFMA cycles
@@ -434,7 +491,7 @@ void gemm_w4_kernel(const GroupArgs ga) {
             read1(fin, ginc, binc, IC<((2 * r) >> 2)>{}, IC<((2 * r) & 3)>{});
             read1(fin, ginc, binc, IC<((2 * r + 1) >> 2)>{}, IC<((2 * r + 1) & 3)>{});
           } else {
-            dma_from(gsrc, cur, gd, r - 4, bd);
+            dma_go(gsrc, cur, gdc, IC<(r >= 4 ? r - 4 : 0)>{});     // its M0 went out behind the previous group's first MFMA
           }
           typename HT<T>::v8 va;
           if (AT) va = tr_pack<T>(fa.t[ks][i]); else __builtin_memcpy(&va, &fa.n[ks][i], 16);
@@ -445,48 +502,56 @@ void gemm_w4_kernel(const GroupArgs ga) {
             if (BT) vb = tr_pack<T>(fb.t[ks][j]); else __builtin_memcpy(&vb, &fb.n[ks][j], 16);
             if (COGV_EXP & 4) { asm volatile("" :: "v"(vb)); continue; }
             // operands swapped: D[n][m] -> lane (m = l & 15) holds columns n = 4 (l >> 4) .. +3 of its row
-            mfma16_inplace<T>(acc[bh][4 * ah + i][j], vb, va);
+            if constexpr (first && ks == 0) mfma16_first<T>(acc[bh][4 * ah + i][j], vb, va);
+            else mfma16_inplace<T>(acc[bh][4 * ah + i][j], vb, va);
+            if constexpr (r >= 3 && r <= 6) {
+              if (j == 0) dma_m0(gdc, IC<r - 3>{}, bdc);
+            }
           }
           __builtin_amdgcn_sched_barrier(0);
       });
       land(fin, gin >= 2 ? BT : AT);
     };
     // one k-tile; fb01 holds B01(kt), fbx is free and ends up holding B01(kt + 1)
-    auto tile = [&](int kt, auto bufc, Frag& fb01, Frag& fbx, auto w0c, auto w1c) {
+    auto tile = [&](int kt, auto bufc, Frag& fb01, Frag& fbx, auto w0c, auto w1c, auto firstc) {
       constexpr int buf = decltype(bufc)::value;
       constexpr bool W0 = decltype(w0c)::value != 0, W1 = decltype(w1c)::value != 0;   // vmcnt waits of the two half-steps
-      // k-tile kt + 2 of this item; past its end: k-tile kt + 2 - nk of the next item (cross-item prefetch) or, without it,
-      // this item's last k-tile once more.  Scalar selects, no branch.
-      const bool past = kt + 2 >= nk;
-      const int ktd = past ? (xp ? kt + 2 - nk : nk - 1) : kt + 2;
-      const char* const gA = (past ? xA : cur.baseA) + (size_t)ktd * ksA;
-      const char* const gB = (past ? xB : cur.baseB) + (size_t)ktd * ksB;
+      // the DMA slots carry k-tile kt + 2 of this item; the first k-tile past its end switches the running sources
+      // (above).  One scalar compare and two 64-bit selects, no branch.
+      if (kt + 2 == nk) { pA = xA; pB = xB; }
+      const char* const gA = pA;
+      const char* const gB = pB;
+      pA += ksA; pB += ksB;
+      pin_s(pA); pin_s(pB);
       if (W0 && !(COGV_EXP & 8192)) wait_vmcnt<16>();
       __builtin_amdgcn_sched_barrier(0);
       if (!(COGV_EXP & 4096)) __builtin_amdgcn_s_barrier();      // probes: results are garbage without them
       __builtin_amdgcn_sched_barrier(0);
-      quarter(IC<0>{}, IC<0>{}, fA, fb01, fbx, IC<G_B23>{}, IC<buf>{}, G_A01, gA, buf);
-      quarter(IC<0>{}, IC<1>{}, fA, fbx, fI, IC<G_A23>{}, IC<buf>{}, G_B01, gB, buf);
+      quarter(firstc, IC<0>{}, IC<0>{}, fA, fb01, fbx, IC<G_B23>{}, IC<buf>{}, IC<G_A01>{}, gA, IC<buf>{});
+      quarter(firstc, IC<0>{}, IC<1>{}, fA, fbx, fI, IC<G_A23>{}, IC<buf>{}, IC<G_B01>{}, gB, IC<buf>{});
       if (W1 && !(COGV_EXP & 8192)) wait_vmcnt<16>();
       __builtin_amdgcn_sched_barrier(0);
       if (!(COGV_EXP & 4096)) __builtin_amdgcn_s_barrier();
       __builtin_amdgcn_sched_barrier(0);
-      quarter(IC<1>{}, IC<1>{}, fI, fbx, fA, IC<G_A01>{}, IC<(buf ^ 1)>{}, G_B23, gB, buf);
-      quarter(IC<1>{}, IC<0>{}, fI, fb01, fbx, IC<G_B01>{}, IC<(buf ^ 1)>{}, G_A23, gA, buf);
+      quarter(firstc, IC<1>{}, IC<1>{}, fI, fbx, fA, IC<G_A01>{}, IC<(buf ^ 1)>{}, IC<G_B23>{}, gB, IC<buf>{});
+      quarter(firstc, IC<1>{}, IC<0>{}, fI, fb01, fbx, IC<G_B01>{}, IC<(buf ^ 1)>{}, IC<G_A23>{}, gA, IC<buf>{});
     };
-    int kt = 0;
-    // half-steps 0..2 read the prologue's granules (all certified above); half-step 3 reads what half-step 0 issued:
-    // its vmcnt(16) is the first wait that also covers the previous item's C stores, >= 2 us of MFMA work after the last one
+    // Every path starts with a `first` k-tile.  Certified: half-steps 0..2 read the prologue's granules (all certified
+    // above); half-step 3 reads what half-step 0 issued: its vmcnt(16) is the first wait that also covers the previous item's
+    // C stores, >= 2 us of MFMA work after the last one.  Not certified (a workgroup's first item): every half-step waits.
+    // A single k-tile (nk == 1) takes the second form and nothing else.
     if (certified && nk >= 2) {
-      tile(0, IC<0>{}, fB0, fB1, IC<0>{}, IC<0>{});
-      tile(1, IC<1>{}, fB1, fB0, IC<0>{}, IC<1>{});
-      kt = 2;
+      tile(0, IC<0>{}, fB0, fB1, IC<0>{}, IC<0>{}, IC<1>{});
+      tile(1, IC<1>{}, fB1, fB0, IC<0>{}, IC<1>{}, IC<0>{});
+    } else {
+      tile(0, IC<0>{}, fB0, fB1, IC<1>{}, IC<1>{}, IC<1>{});
+      if (nk >= 2) tile(1, IC<1>{}, fB1, fB0, IC<1>{}, IC<1>{}, IC<0>{});
     }
-    for (; kt + 1 < nk; kt += 2) {                         // two k-tiles per trip: the B register sets swap roles
-      tile(kt, IC<0>{}, fB0, fB1, IC<1>{}, IC<1>{});
-      tile(kt + 1, IC<1>{}, fB1, fB0, IC<1>{}, IC<1>{});
+    for (int kt = 2; kt + 1 < nk; kt += 2) {               // two k-tiles per trip: the B register sets swap roles
+      tile(kt, IC<0>{}, fB0, fB1, IC<1>{}, IC<1>{}, IC<0>{});
+      tile(kt + 1, IC<1>{}, fB1, fB0, IC<1>{}, IC<1>{}, IC<0>{});
     }
-    if (nk & 1) tile(nk - 1, IC<0>{}, fB0, fB1, IC<1>{}, IC<1>{});
+    if (nk > 2 && (nk & 1)) tile(nk - 1, IC<0>{}, fB0, fB1, IC<1>{}, IC<1>{}, IC<0>{});
     __builtin_amdgcn_sched_barrier(0);
     W4_TS(2);
     wait_vmcnt<0>();                                        // the tail prefetches: the next item's first two k-tiles (or redundant)
