@@ -164,6 +164,7 @@ class ConvWgradDesc(C.Structure):
         ("splits", C.c_int),
         ("x", C.c_void_p), ("dy", C.c_void_p), ("dw", C.c_void_p),
         ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+        ("relu_x", C.c_int), ("topologies", C.c_int),
     ]
 
 
@@ -413,11 +414,13 @@ CONV_WGRAD_PLAN_INTS = 6
 CONV_WGRAD_PLAN_FIELDS = ("splits", "span", "workgroups", "cout_tiles", "k_tiles", "parities")
 
 
-def conv_wgrad_plan(kind, B, IH, IW, Cin, Cout, splits=0):
+def conv_wgrad_plan(kind, B, IH, IW, Cin, Cout, splits=0, relu_x=0, topologies=0):
     """cogv_conv_wgrad_plan: (error code, dict of CONV_WGRAD_PLAN_FIELDS; empty where the layer is refused) of what
-    cogv_conv_wgrad_nhwc_f32 launches for that forward layer.  Host only."""
+    cogv_conv_wgrad_nhwc_f32 launches for that forward layer.  Host only.  topologies=1: CONV_3X3_S1 is planned too, and
+    cout_tiles counts 32-wide tiles where Cout <= 32."""
     d = ConvWgradDesc()
     d.kind, d.B, d.IH, d.IW, d.Cin, d.Cout, d.splits = kind, B, IH, IW, Cin, Cout, splits
+    d.relu_x, d.topologies = relu_x, topologies
     out = (C.c_int * CONV_WGRAD_PLAN_INTS)(*([-1] * CONV_WGRAD_PLAN_INTS))
     rc = lib().cogv_conv_wgrad_plan(C.byref(d), out)
     return rc, dict(zip(CONV_WGRAD_PLAN_FIELDS, out)) if rc == OK else {}

@@ -19,9 +19,13 @@ namespace {
 // operands arrive NHWC, so an LDS row is a pixel and the 32 lanes of an MFMA operand read 32 consecutive channels of one
 // row -- no transposition.  A column chunk of 4 consecutive k lies inside one tap (Cin % 4 == 0), and a thread stages the
 // same chunk of every pixel, so its tap offset is fixed for the whole kernel.
-// Tile: 128 co x 128 k, 32 pixels per contraction step, 4 waves of 64 x 64 (2 x 2 MFMA 32x32x2).  Workgroup ->
-// (pixel split s, parity z, co tile, k tile); split s writes slab s, wgrad_reduce_kernel adds the slabs in order.
-constexpr int TC = 128;      // channels per tile, both operands
+// Tile: TCO co x 128 k, 32 pixels per contraction step, 4 waves.  TCO = 128: waves of 64 x 64 (2 x 2 MFMA 32x32x2).
+// TCO = 32 (the plan's choice for Cout <= 32 under topologies == 1: a ResBlock's 3x3 has 32 output channels, and a 128-wide
+// tile would spend three quarters of its MFMAs on zero rows): waves of 32 x 32, side by side over k.  Both widths add an
+// element's pixels in the same order.  Workgroup -> (pixel split s, parity z, co tile, k tile); split s writes slab s,
+// wgrad_reduce_kernel adds the slabs in order.
+constexpr int TC = 128;      // k (= tap * Cin + ci) columns per tile; output channels per tile in the wide form
+constexpr int TCN = 32;      // output channels per tile in the narrow form
 constexpr int KP = 32;       // pixels per contraction step
 
 struct WgradArgs {
@@ -37,23 +41,32 @@ struct WgradArgs {
   long long slab;           // floats of one slab = nz * Cout * K
 };
 
+template <int TCO, bool RELU_X>
 __global__ __launch_bounds__(NT) void wgrad_kernel(const WgradArgs p) {
-  __shared__ __attribute__((aligned(16))) float la[KP * TC];     // [pixel][co]
+  constexpr int WM = TCO == TC ? 64 : 32;          // output channels per wave
+  constexpr int WN = TC / (4 / (TCO / WM));        // k columns per wave: 64 (2 x 2 waves) or 32 (1 x 4 waves)
+  constexpr int MI = WM / 32, NJ = WN / 32;
+  constexpr int ACH = TCO / 4;                     // 16-byte chunks of a dy row
+  constexpr int AROWS = NT / ACH, AQ = KP / AROWS; // pixel rows per staging pass and passes per step, dy operand
+  static_assert(TCO == TC || AQ == 1, "the narrow form stages one chunk of dy per thread and step");
+  __shared__ __attribute__((aligned(16))) float la[KP * TCO];    // [pixel][co]
   __shared__ __attribute__((aligned(16))) float lb[KP * TC];     // [pixel][k]
   int r = blockIdx.x;
   const int kti = r % p.kt; r /= p.kt;
   const int ct = r % p.cot; r /= p.cot;
   const int z = r % p.nz;
   const int s = r / p.nz;
-  const int co0 = ct * TC, k0 = kti * TC;
+  const int co0 = ct * TCO, k0 = kti * TC;
   const int m_begin = s * p.span, m_end = min(p.M, m_begin + p.span);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
+  const int wm = TCO == TC ? (wave >> 1) * 64 : 0, wn = TCO == TC ? (wave & 1) * 64 : wave * 32;
   const int fr = lane & 31, fg = lane >> 5;
 
-  // staging: thread t -> 16-byte chunk t % 32 of the 128 channels, pixel rows t / 32 + 8 q
+  // staging: x operand: thread t -> 16-byte chunk t % 32 of the 128 columns, pixel rows t / 32 + 8 q; dy operand: chunk
+  // t % ACH of the TCO channels, pixel rows t / ACH + AROWS q (the same rows as x in the wide form)
   const int chunk = threadIdx.x & 31, prow = threadIdx.x >> 5;
-  const bool a_ok = co0 + chunk * 4 < p.Cout;
+  const int achunk = TCO == TC ? chunk : threadIdx.x % ACH, arow = TCO == TC ? prow : threadIdx.x / ACH;
+  const bool a_ok = co0 + achunk * 4 < p.Cout;
   const int k = k0 + chunk * 4;
   const bool b_ok = k < p.K;
   const int tap = b_ok ? k / p.Cin : 0;
@@ -62,15 +75,15 @@ __global__ __launch_bounds__(NT) void wgrad_kernel(const WgradArgs p) {
   tap_offset(p.kind, z, tap, dy, dx);
   const int gpix = p.GH * p.GW;
 
-  f32x16 acc[2][2];
+  f32x16 acc[MI][NJ];
 #pragma unroll
-  for (int i = 0; i < 2; ++i)
+  for (int i = 0; i < MI; ++i)
 #pragma unroll
-    for (int j = 0; j < 2; ++j)
+    for (int j = 0; j < NJ; ++j)
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
 
-  f32x4 ra[4], rb[4];
+  f32x4 ra[AQ], rb[4];
   // a pixel past the split's range, a channel chunk past the tensor and a tap outside the image contribute zero; nothing is
   // loaded from an address that is not inside its tensor
   auto load = [&](int m0) {
@@ -82,7 +95,7 @@ __global__ __launch_bounds__(NT) void wgrad_kernel(const WgradArgs p) {
         const int b = m / gpix;
         const int rem = m - b * gpix;
         const int y = rem / p.GW, x = rem - y * p.GW;
-        if (a_ok) {
+        if (TCO == TC && a_ok) {           // the wide form stages dy from the pixel rows it stages x from
           const int oy = y * p.out_mul + (z >> 1), ox = x * p.out_mul + (z & 1);     // z = 0 unless transposed
           va = ld4(p.dy + (((size_t)b * p.OH + oy) * p.OW + ox) * p.Cout + co0 + chunk * 4);
         }
@@ -90,7 +103,20 @@ __global__ __launch_bounds__(NT) void wgrad_kernel(const WgradArgs p) {
         if (b_ok && (unsigned)iy < (unsigned)p.IH && (unsigned)ix < (unsigned)p.IW)
           vb = ld4(p.x + (((size_t)b * p.IH + iy) * p.IW + ix) * p.Cin + ci);
       }
-      ra[q] = va; rb[q] = vb;
+      if (TCO == TC) ra[q] = va;
+      rb[q] = vb;
+    }
+    if (TCO != TC) {                       // the narrow form: one chunk of dy per thread, pixel row t / ACH
+      const int m = m0 + arow;
+      f32x4 va = {0.f, 0.f, 0.f, 0.f};
+      if (m < m_end && a_ok) {
+        const int b = m / gpix;
+        const int rem = m - b * gpix;
+        const int y = rem / p.GW, x = rem - y * p.GW;
+        const int oy = y * p.out_mul + (z >> 1), ox = x * p.out_mul + (z & 1);
+        va = ld4(p.dy + (((size_t)b * p.OH + oy) * p.OW + ox) * p.Cout + co0 + achunk * 4);
+      }
+      ra[0] = va;
     }
   };
   load(m_begin);
@@ -98,30 +124,38 @@ __global__ __launch_bounds__(NT) void wgrad_kernel(const WgradArgs p) {
   for (int m0 = m_begin; m0 < m_end; m0 += KP) {
     __syncthreads();                       // the previous step's fragment reads are done
 #pragma unroll
+    for (int q = 0; q < AQ; ++q) st4(la + (arow + AROWS * q) * TCO + achunk * 4, ra[q]);
+#pragma unroll
     for (int q = 0; q < 4; ++q) {
-      st4(la + (prow + 8 * q) * TC + chunk * 4, ra[q]);
-      st4(lb + (prow + 8 * q) * TC + chunk * 4, rb[q]);
+      f32x4 vb = rb[q];
+      if (RELU_X) {                        // on the staged registers, after the loads have landed: -0.0, +0.0 and negatives -> +0.0
+#pragma unroll
+        for (int i = 0; i < 4; ++i) vb[i] = vb[i] > 0.f ? vb[i] : 0.f;
+      }
+      st4(lb + (prow + 8 * q) * TC + chunk * 4, vb);
     }
     __syncthreads();
     if (m0 + KP < m_end) load(m0 + KP);    // the next step's loads fly under this step's MFMAs
 #pragma unroll
     for (int kk = 0; kk < KP / 2; ++kk) {  // one MFMA contracts two pixels: lanes 0..31 pixel 2 kk, lanes 32..63 pixel 2 kk + 1
-      const int row = (2 * kk + fg) * TC;
-      float fa[2], fb[2];
+      const int prw = 2 * kk + fg;
+      float fa[MI], fb[NJ];
 #pragma unroll
-      for (int i = 0; i < 2; ++i) { fa[i] = la[row + wm + 32 * i + fr]; fb[i] = lb[row + wn + 32 * i + fr]; }
+      for (int i = 0; i < MI; ++i) fa[i] = la[prw * TCO + wm + 32 * i + fr];
 #pragma unroll
-      for (int i = 0; i < 2; ++i)
+      for (int j = 0; j < NJ; ++j) fb[j] = lb[prw * TC + wn + 32 * j + fr];
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
+      for (int i = 0; i < MI; ++i)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i], fb[j], acc[i][j], 0, 0, 0);
     }
   }
   float* out = p.out + (size_t)s * p.slab + (size_t)z * p.Cout * p.K;
 #pragma unroll
-  for (int i = 0; i < 2; ++i)
+  for (int i = 0; i < MI; ++i)
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
+    for (int j = 0; j < NJ; ++j) {
       const int kc = k0 + wn + 32 * j + fr;
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
@@ -140,23 +174,27 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* slabs, f
   }
 }
 
-struct WgradPlan { WgradArgs a; int splits; long long blocks; };
+struct WgradPlan { WgradArgs a; int splits; long long blocks; bool narrow, relu_x; };     // narrow, relu_x: the kernel instance
 
 // host only: geometry, argument checks and the split of the pixel range
 int wgrad_plan(const cogv_conv_wgrad_desc* d, WgradPlan& pl) {
   if (!d) return COGV_ERR_ARG;
   if (d->B <= 0 || d->IH <= 0 || d->IW <= 0 || d->Cin <= 0 || d->Cout <= 0 || (d->Cin & 3) || (d->Cout & 7) || d->splits < 0) return COGV_ERR_ARG;
+  if ((unsigned)d->relu_x > 1u || (unsigned)d->topologies > 1u) return COGV_ERR_ARG;
   WgradArgs& a = pl.a;
   a.x = (const float*)d->x; a.dy = (const float*)d->dy; a.out = (float*)d->dw;
   a.B = d->B; a.IH = d->IH; a.IW = d->IW; a.Cin = d->Cin; a.Cout = d->Cout; a.kind = d->kind;
   ConvGeom g;
   const int rc = conv_geometry(d->kind, d->B, d->IH, d->IW, d->Cin, g);
   if (rc != COGV_OK) return rc;
-  if (d->kind == COGV_CONV_3X3_S1) return COGV_ERR_UNSUPPORTED;        // 3x3 (ResBlock, stride-4 / stride-2 encoders): no weight gradient
+  if (d->kind == COGV_CONV_3X3_S1 && !d->topologies) return COGV_ERR_UNSUPPORTED;     // 3x3 (ResBlock, stride-4 / stride-2 encoders): opt-in
   if (g.M >= (1ll << 31) - KP || (long long)g.ntaps * a.Cin >= (1 << 24)) return COGV_ERR_ARG;
   a.GH = g.GH; a.GW = g.GW; a.OH = g.OH; a.OW = g.OW; a.in_mul = g.in_mul; a.out_mul = g.out_mul; a.nz = g.nz;
   a.M = (int)g.M; a.K = g.K;
-  a.cot = (a.Cout + TC - 1) / TC; a.kt = (a.K + TC - 1) / TC;
+  pl.relu_x = d->relu_x != 0;
+  pl.narrow = d->topologies == 1 && a.Cout <= TCN;
+  const int tco = pl.narrow ? TCN : TC;
+  a.cot = (a.Cout + tco - 1) / tco; a.kt = (a.K + TC - 1) / TC;
   a.slab = (long long)a.nz * a.Cout * a.K;
   // when (tiles x parities) does not fill the chip -- the first and the last layer, small batches -- the pixel range is
   // split: aim at four workgroups per CU, at least 256 pixels per split, at most 256 slabs
@@ -427,7 +465,11 @@ extern "C" int cogv_conv_wgrad_nhwc_f32(const cogv_conv_wgrad_desc* d, void* str
     if (!d->workspace || d->workspace_bytes < (size_t)pl.splits * (size_t)pl.a.slab * 4) return COGV_ERR_ARG;
     pl.a.out = (float*)d->workspace;
   }
-  hipLaunchKernelGGL(wgrad_kernel, dim3((unsigned)pl.blocks), dim3(NT), 0, st, pl.a);
+  const dim3 grid((unsigned)pl.blocks), block(NT);
+  if (pl.narrow && pl.relu_x) hipLaunchKernelGGL((wgrad_kernel<TCN, true>), grid, block, 0, st, pl.a);
+  else if (pl.narrow) hipLaunchKernelGGL((wgrad_kernel<TCN, false>), grid, block, 0, st, pl.a);
+  else if (pl.relu_x) hipLaunchKernelGGL((wgrad_kernel<TC, true>), grid, block, 0, st, pl.a);
+  else hipLaunchKernelGGL((wgrad_kernel<TC, false>), grid, block, 0, st, pl.a);
   int e = cogv_check_launch();
   if (e != COGV_OK || pl.splits == 1) return e;
   const size_t n4 = (size_t)pl.a.slab / 4;           // Cin % 4 == 0

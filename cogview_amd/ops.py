@@ -1537,11 +1537,13 @@ def nchw3_to_nhwc4(x):
 
 
 # ------------------------------------------------------------------------------------------ VQ-VAE tokenizer training
-def conv_wgrad(kind, x, dy, splits=0):
-    """Weight gradient of the convolution layer `kind` (L.CONV_4X4_S2 / CONV_1X1 / CONVT_4X4_S2) with input x
-    [b, ih, iw, cin] and pre-activation output gradient dy [b, oh, ow, cout], both NHWC fp32, in the PACKED layout the
-    forward kernel reads: [cout, taps, cin], or [4, cout, 4, cin] for the transposed convolution
-    (vqvae_zc.unpack_*_weight_grad turn it into the parameter's layout).  splits: pixel-range splits, 0 = the plan's."""
+def conv_wgrad(kind, x, dy, splits=0, relu_x=0, topologies=0):
+    """Weight gradient of the convolution layer `kind` (L.CONV_4X4_S2 / CONV_1X1 / CONVT_4X4_S2; with topologies=1 also
+    CONV_3X3_S1) with input x [b, ih, iw, cin] and pre-activation output gradient dy [b, oh, ow, cout], both NHWC fp32, in
+    the PACKED layout the forward kernel reads: [cout, taps, cin], or [4, cout, 4, cin] for the transposed convolution
+    (vqvae_zc.unpack_*_weight_grad turn it into the parameter's layout).  splits: pixel-range splits, 0 = the plan's.
+    relu_x=1: the gradient against max(x, 0) -- x is the PRE-ReLU input of a layer whose forward ran with relu_in.
+    topologies=1 (opt-in): 3x3 layers, and 32-wide output-channel tiles where cout <= 32."""
     _need_gpu(x, dy)
     assert x.dtype == torch.float32 and dy.dtype == torch.float32 and x.dim() == 4 and dy.dim() == 4
     x, dy = x.contiguous(), dy.contiguous()
@@ -1549,9 +1551,10 @@ def conv_wgrad(kind, x, dy, splits=0):
     cout = dy.shape[3]
     d = L.ConvWgradDesc()
     d.kind, d.B, d.IH, d.IW, d.Cin, d.Cout, d.splits = kind, b, ih, iw, cin, cout, int(splits)
+    d.relu_x, d.topologies = int(relu_x), int(topologies)
     plan = (C.c_int * L.CONV_WGRAD_PLAN_INTS)()
     L.check(L.lib().cogv_conv_wgrad_plan(C.byref(d), plan), f"cogv_conv_wgrad_plan(kind {kind}, {b}x{ih}x{iw}x{cin}->{cout})")
-    par, taps = (4, 4) if kind == L.CONVT_4X4_S2 else (1, 16 if kind == L.CONV_4X4_S2 else 1)
+    par, taps = (4, 4) if kind == L.CONVT_4X4_S2 else (1, {L.CONV_4X4_S2: 16, L.CONV_3X3_S1: 9}.get(kind, 1))
     om = {L.CONV_4X4_S2: (ih // 2, iw // 2), L.CONVT_4X4_S2: (ih * 2, iw * 2)}.get(kind, (ih, iw))
     assert tuple(dy.shape) == (b, om[0], om[1], cout), "dy does not have the layer's output shape"
     dw = torch.empty((4, cout, taps, cin) if par == 4 else (cout, taps, cin), dtype=torch.float32, device=x.device)

@@ -23,6 +23,14 @@ def set_precision(model, precision):
     return model.set_precision(precision)
 
 
+def set_train_topologies(model, which):
+    """"plain" (default): train_step covers new_model() and the other n_res_block=0 stride-6 configurations; ResBlocks and 3x3
+    convolutions raise NotImplementedError in training mode.  "all" (opt-in, VQVAE.set_train_topologies; a later change makes
+    it the default): every topology VQVAE's constructor builds trains, VQVAE() with its default arguments among them.  The
+    Gumbel-softmax branch (continuous_relax=True) raises in both.  Returns the model."""
+    return model.set_train_topologies(which)
+
+
 def img2code(model, img):
     """[b, 3, H, W] normalised image -> LongTensor [b, (H/8)*(W/8)]."""
     with torch.no_grad():
@@ -62,6 +70,7 @@ def train_step(model, optimizer, img, latent_loss_weight=0.25):
     """One training step of the tokenizer (model.train(); the default, non-relaxed path of vqvae/vqvae_zc.py:67-86 and
     :261-268): forward, loss = mse(dec, img) + latent_loss_weight * diff, backward, optimizer.step() -- any torch.optim
     optimizer over the fp32 parameters.  The EMA codebook update happens inside the forward, as in the reference.
+    Which topologies train: set_train_topologies.
     Returns dict(loss, recon_loss, latent_loss) as device scalars (no host read)."""
     optimizer.zero_grad(set_to_none=True)
     dec, diff = model(img)

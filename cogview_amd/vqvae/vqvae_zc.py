@@ -18,8 +18,18 @@ Training (module.train(), vqvae/vqvae_zc.py:67-86): the default, non-relaxed pat
 convolutions, 4x4 stride-2 transposed convolutions, 1x1 convolutions and ReLU (new_model() and every n_res_block=0 stride-6
 configuration).  The stacks run layer by layer, each layer a torch.autograd.Function on the kernels of
 cogview_amd/csrc/conv.hip (forward, data gradient) and conv_bwd.hip (weight gradient, ReLU mask + bias gradient, codebook
-statistics, EMA update, straight-through gradient).  What still raises NotImplementedError in training mode: ResBlock
-topologies and 3x3 convolutions (no weight gradient kernel), and continuous_relax=True (the Gumbel-softmax branch) in any mode.
+statistics, EMA update, straight-through gradient).
+
+Every other topology trains after an opt-in, VQVAE.set_train_topologies("all") (a later change makes it the default): VQVAE()
+with its own default arguments, the stride-4 and stride-2 encoders (they end in a 3x3 convolution) and any n_res_block > 0.
+A 3x3 convolution is a layer like the others (weight gradient: conv_bwd.hip with topologies=1; data gradient: the 3x3
+forward kernel on the weight with in / out swapped and both tap axes flipped).  A ResBlock is ONE autograd.Function
+(_ResBlockLayer): the two launches of run_block_list forward, and backward the 1x1 pair, the ReLU mask, the 3x3 weight
+gradient against max(x, 0) (relu_x=1), the 3x3 data gradient with the skip connection's gradient added in its residual
+epilogue, and the gate of the block's leading in-place ReLU.  A convolution behind the ReLU that closes a ResBlock chain runs
+with relu_in, keeps its pre-ReLU input, and gates its data gradient the same way.  What still raises NotImplementedError in
+training mode: without the opt-in, ResBlock topologies and 3x3 convolutions, exactly as before; with or without it,
+continuous_relax=True (the Gumbel-softmax branch), in any mode.
 """
 import ctypes as C
 
@@ -39,6 +49,7 @@ def _p(t):
 
 
 PRECISIONS = ("fp32", "bf16x3")
+TRAIN_TOPOLOGIES = ("plain", "all")
 
 
 def split_weight_limbs(wp):
@@ -255,6 +266,7 @@ class _ConvStack(nn.Module):
         self.blocks = nn.Sequential(*blocks)
         self._packed = None
         self._precision = "fp32"          # VQVAE.set_precision; eval-mode launches only
+        self._train_topologies = "plain"  # VQVAE.set_train_topologies; training-mode launches only
 
     def _weights(self, packers):
         key = tuple((m.weight.data_ptr(), m.weight._version) for m in self.blocks if hasattr(m, "weight"))
@@ -377,62 +389,147 @@ def _dgrad_weight(m, kind, cin_x, cout_p):
     reads the cout_p channels of the output gradient and writes the cin_x channels of the input gradient.
       Conv2d k4 s2 p1, W [Cout, Cin, 4, 4]          -> transposed convolution whose [in, out, 4, 4] weight is W itself
       ConvTranspose2d k4 s2 p1, W [Cin, Cout, 4, 4] -> convolution whose [out, in, 4, 4] weight is W itself
-      1x1                                            -> 1x1 with the transposed matrix"""
+      1x1                                            -> 1x1 with the transposed matrix
+      Conv2d k3 s1 p1, W [Cout, Cin, 3, 3]          -> 3x3 convolution whose [out, in, 3, 3] weight is W with in and out
+                                                        swapped and both tap axes flipped"""
     w = m.weight.detach().float()
     if kind == L.CONV_4X4_S2:
         k2, wp = L.CONVT_4X4_S2, pack_convt_weight(w)
     elif kind == L.CONVT_4X4_S2:
         k2, wp = L.CONV_4X4_S2, pack_conv_weight(w)
+    elif kind == L.CONV_3X3_S1:
+        k2, wp = L.CONV_3X3_S1, pack_conv_weight(w.permute(1, 0, 2, 3).flip(2, 3))
     else:
         k2, wp = L.CONV_1X1, pack_conv_weight(w if isinstance(m, nn.ConvTranspose2d) else w.permute(1, 0, 2, 3))
     wp = torch.nn.functional.pad(wp, (0, cout_p - wp.shape[-1], 0, 0, 0, cin_x - wp.shape[-3]))
     return k2, wp.contiguous()
 
 
+def _unpack_weight_grad(m, kind, dwp):
+    """The packed weight gradient of convolution module m (forward kind `kind`) in the parameter's own layout."""
+    if kind == L.CONVT_4X4_S2:
+        return unpack_convt_weight_grad(dwp, m.weight.shape)
+    if isinstance(m, nn.ConvTranspose2d):                 # 1x1 transposed: the parameter is the transposed matrix
+        return dwp[:m.out_channels, 0, :m.in_channels].t().reshape(m.weight.shape).contiguous()
+    return unpack_conv_weight_grad(dwp, m.weight.shape)
+
+
+def _packed_for(m, x):
+    """_pack_generic(m) with the weight's input channels padded up to x's (the previous layer's zero-padded output channels
+    meet zero weights)."""
+    kind, wp, bp, _ = _pack_generic(m)
+    if x.shape[-1] > wp.shape[-1]:
+        wp = torch.nn.functional.pad(wp, (0, x.shape[-1] - wp.shape[-1])).contiguous()
+    return kind, wp, bp
+
+
 class _ConvLayer(torch.autograd.Function):
     """One convolution layer (+ the ReLU that follows it) of a training-mode stack.  Saves its input and, with a ReLU, its
     post-ReLU output; backward launches the ReLU mask + bias gradient, the data gradient (the forward kernel on repacked
-    weights) and the weight gradient -- each only when something needs it."""
+    weights) and the weight gradient -- each only when something needs it.
+
+    relu_in (topologies "all"): the layer reads max(x, 0) -- a ReLU that follows a ResBlock is applied inside the kernel.
+    x is saved as it is, PRE-ReLU: the weight gradient runs with relu_x=1 and the data gradient is gated by x > 0
+    (relu_bias_bwd, whose mask only tests act > 0).
+
+    Column-sum carriers (topologies "all").  That gate's column sum IS the bias gradient of the layer that produced x, when
+    that layer has no ReLU of its own.  To hand it back through autograd, such a producer (emit=True) returns a second
+    output, an uninitialised [C] tensor nobody reads; the gating consumer takes it as its input `carrier` and returns the
+    column sum as that input's gradient; the producer finds it as the gradient of its second output and launches no bias
+    sum of its own.  Without a carrier gradient the producer sums for itself."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, m, relu):
-        kind, wp, bp, _ = _pack_generic(m)
-        if x.shape[-1] > wp.shape[-1]:               # the previous layer's zero-padded output channels: zero weights for them
-            wp = torch.nn.functional.pad(wp, (0, x.shape[-1] - wp.shape[-1])).contiguous()
-        y = _conv(kind, x, wp, bp, bp.numel(), relu)
-        ctx.m, ctx.kind, ctx.relu = m, kind, relu
+    def forward(ctx, x, weight, bias, carrier, m, relu, relu_in, emit, topo):
+        kind, wp, bp = _packed_for(m, x)
+        y = _conv(kind, x, wp, bp, bp.numel(), relu, relu_in=relu_in)
+        ctx.m, ctx.kind, ctx.relu, ctx.relu_in, ctx.topo = m, kind, relu, relu_in, topo
         ctx.save_for_backward(x, y if relu else None)
-        return y
+        ctx.set_materialize_grads(False)
+        assert not (emit and relu)
+        return (y, y.new_empty(y.shape[-1])) if emit else y
 
     @staticmethod
-    def backward(ctx, g):
+    def backward(ctx, g, g_carrier=None):
+        if g is None:
+            return (None,) * 9
         x, y = ctx.saved_tensors
         m, kind = ctx.m, ctx.kind
-        need_x, need_w, need_b = ctx.needs_input_grad[:3]
+        need_x, need_w, need_b, need_c = ctx.needs_input_grad[:4]
         g = g.contiguous()
-        db = None
-        if ctx.relu or need_b:
+        db = g_carrier
+        if ctx.relu or (need_b and db is None):
             g, db = ops.relu_bias_bwd(g, y if ctx.relu else None)
-        dx = dw = None
+        dx = dw = dc = None
         if need_x:
             k2, wp = _dgrad_weight(m, kind, x.shape[-1], g.shape[-1])
             dx = _conv(k2, g, wp, None, x.shape[-1], False)
+            if ctx.relu_in:
+                dx, dc = ops.relu_bias_bwd(dx, x)
         if need_w:
-            dwp = ops.conv_wgrad(kind, x, g)
-            if kind == L.CONVT_4X4_S2:
-                dw = unpack_convt_weight_grad(dwp, m.weight.shape)
-            elif isinstance(m, nn.ConvTranspose2d):       # 1x1 transposed: the parameter is the transposed matrix
-                dw = dwp[:m.out_channels, 0, :m.in_channels].t().reshape(m.weight.shape).contiguous()
-            else:
-                dw = unpack_conv_weight_grad(dwp, m.weight.shape)
+            dw = _unpack_weight_grad(m, kind, ops.conv_wgrad(kind, x, g, relu_x=int(ctx.relu_in), topologies=ctx.topo))
         if need_b:
             db = db[:m.out_channels].contiguous()
-        return dx, dw, (db if need_b else None), None, None
+        return dx, dw, (db if need_b else None), (dc if need_c else None), None, None, None, None, None
 
 
-def _training_kind(m):
+class _ResBlockLayer(torch.autograd.Function):
+    """One ResBlock of a training-mode stack (topologies "all").  Forward, the two launches of run_block_list:
+        t = relu(conv3x3(relu(x)))            relu_in, ReLU epilogue
+        y = conv1x1(t) + relu(x)              residual epilogue with relu_residual
+    saving x (PRE-ReLU) and t.  Backward from g:
+        db1 = column sum of g                 (the carrier's gradient when a gating consumer handed it back, see _ConvLayer)
+        dW1 = wgrad 1x1 (t, g)
+        d_t = dgrad 1x1 (g), masked by t > 0, with db3 out of the same launch
+        dW3 = wgrad 3x3 (x, d_t, relu_x=1)
+        d_r = dgrad 3x3 (d_t) + g             the add rides the forward kernel's residual epilogue
+        dx  = d_r gated by x > 0              its column sum goes to the carrier: the bias gradient of what produced x"""
+
+    @staticmethod
+    def forward(ctx, x, w3, b3, w1, b1, carrier, block, emit):
+        c3, c1 = block.conv[1], block.conv[3]
+        k3, wp3, bp3 = _packed_for(c3, x)
+        t = _conv(k3, x, wp3, bp3, bp3.numel(), True, relu_in=True)
+        k1, wp1, bp1 = _packed_for(c1, t)
+        if bp1.numel() != x.shape[-1]:
+            raise NotImplementedError(f"training a ResBlock whose input has {x.shape[-1]} channels for {c1.out_channels} of its own")
+        y = _conv(k1, t, wp1, bp1, bp1.numel(), False, residual=x, relu_residual=True)
+        ctx.c3, ctx.c1 = c3, c1
+        ctx.save_for_backward(x, t)
+        ctx.set_materialize_grads(False)
+        return (y, y.new_empty(y.shape[-1])) if emit else y
+
+    @staticmethod
+    def backward(ctx, g, g_carrier=None):
+        if g is None:
+            return (None,) * 8
+        x, t = ctx.saved_tensors
+        c3, c1 = ctx.c3, ctx.c1
+        need_x, need_w3, need_b3, need_w1, need_b1, need_c = ctx.needs_input_grad[:6]
+        g = g.contiguous()
+        dx = dw3 = db3 = dw1 = db1 = dc = None
+        if need_b1:
+            db1 = g_carrier if g_carrier is not None else ops.relu_bias_bwd(g, None)[1]
+            db1 = db1[:c1.out_channels].contiguous()
+        if need_w1:
+            dw1 = unpack_conv_weight_grad(ops.conv_wgrad(L.CONV_1X1, t, g, topologies=1), c1.weight.shape)
+        if need_x or need_w3 or need_b3:
+            _, wp = _dgrad_weight(c1, L.CONV_1X1, t.shape[-1], g.shape[-1])
+            d_t, db3 = ops.relu_bias_bwd(_conv(L.CONV_1X1, g, wp, None, t.shape[-1], False), t)
+            db3 = db3[:c3.out_channels].contiguous() if need_b3 else None
+            if need_w3:
+                dw3 = unpack_conv_weight_grad(ops.conv_wgrad(L.CONV_3X3_S1, x, d_t, relu_x=1, topologies=1), c3.weight.shape)
+            if need_x:
+                _, wp = _dgrad_weight(c3, L.CONV_3X3_S1, x.shape[-1], d_t.shape[-1])
+                dx, dc = ops.relu_bias_bwd(_conv(L.CONV_3X3_S1, d_t, wp, None, x.shape[-1], False, residual=g), x)
+        return dx, dw3, db3, dw1, db1, (dc if need_c else None), None, None
+
+
+def _training_kind(m, topologies="plain"):
     """The kernel kind of a module the training path supports; NotImplementedError naming what is missing otherwise."""
+    everything = topologies == "all"
     if isinstance(m, ResBlock):
+        if everything:
+            return
         raise NotImplementedError("training a ResBlock topology is not implemented: the ResBlock backward (3x3 weight gradient, "
                                   "residual branch) is missing; n_res_block=0 topologies train")
     if isinstance(m, nn.ConvTranspose2d):
@@ -442,30 +539,63 @@ def _training_kind(m):
         ks, st, pd = m.kernel_size, m.stride, m.padding
         if (ks == (4, 4) and st == (2, 2) and pd == (1, 1)) or (ks == (1, 1) and st == (1, 1) and pd == (0, 0)):
             return
+        if everything and ks == (3, 3) and st == (1, 1) and pd == (1, 1):
+            return
         if ks == (3, 3):
             raise NotImplementedError("training a topology with a 3x3 convolution is not implemented: the 3x3 weight gradient is "
                                       "missing (stride 6 encoders and their decoders train)")
     raise NotImplementedError(f"training through {m} is not implemented")
 
 
-def train_block_list(blocks, x):
+def _gated_next(mods, i):
+    """Is the first convolution or ResBlock from mods[i] on one that gates its data gradient by its input's sign -- a ResBlock,
+    or a convolution behind a ReLU?  (Then its gate's column sum is the bias gradient of the module in front of mods[i].)"""
+    relu = False
+    while i < len(mods) and isinstance(mods[i], nn.ReLU):
+        relu, i = True, i + 1
+    return i < len(mods) and (relu or isinstance(mods[i], ResBlock))
+
+
+def train_block_list(blocks, x, topologies="plain"):
     """run_block_list for training mode: the same blocks on the same forward kernels, one _ConvLayer per convolution so that
-    autograd reaches the weights.  Every ReLU of the supported topologies follows a convolution and rides in its epilogue."""
+    autograd reaches the weights.  topologies="plain" (default): the topologies of 4x4 stride-2, transposed 4x4 stride-2 and
+    1x1 convolutions, where every ReLU follows a convolution and rides in its epilogue; everything else raises.
+    topologies="all": 3x3 convolutions and ResBlocks (_ResBlockLayer) too, a ReLU behind a ResBlock applied to the input of
+    the next convolution inside the kernel, as run_block_list does."""
+    if topologies not in TRAIN_TOPOLOGIES:
+        raise ValueError(f"topologies must be one of {TRAIN_TOPOLOGIES}, not {topologies!r}")
     mods = list(blocks)
     for m in mods:
         if not isinstance(m, nn.ReLU):
-            _training_kind(m)
+            _training_kind(m, topologies)
+    everything = topologies == "all"
+    relu_pending, carrier = False, None
     i = 0
     while i < len(mods):
         m = mods[i]
         if isinstance(m, nn.ReLU):
-            raise NotImplementedError("training: a ReLU that does not follow a convolution (ResBlock topologies) is not implemented")
-        fuse = i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
-        cin_p = (m.in_channels + 3) // 4 * 4
-        if x.shape[-1] < cin_p:
-            x = torch.nn.functional.pad(x, (0, cin_p - x.shape[-1]))
-        x = _ConvLayer.apply(x, m.weight, m.bias, m, fuse)
-        i += 2 if fuse else 1
+            if not everything:
+                raise NotImplementedError("training: a ReLU that does not follow a convolution (ResBlock topologies) is not implemented")
+            relu_pending = True
+            i += 1
+            continue
+        if isinstance(m, ResBlock):
+            emit = _gated_next(mods, i + 1)
+            c3, c1 = m.conv[1], m.conv[3]
+            out = _ResBlockLayer.apply(x, c3.weight, c3.bias, c1.weight, c1.bias, carrier, m, emit)
+            i += 1                                       # (a ReLU pending from before the block is subsumed by the block's own)
+        else:
+            fuse = i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
+            emit = everything and not fuse and _gated_next(mods, i + 1)
+            cin_p = (m.in_channels + 3) // 4 * 4
+            if x.shape[-1] < cin_p:
+                x, carrier = torch.nn.functional.pad(x, (0, cin_p - x.shape[-1])), None
+            out = _ConvLayer.apply(x, m.weight, m.bias, carrier if relu_pending else None, m, fuse, relu_pending, emit, int(everything))
+            i += 2 if fuse else 1
+        relu_pending = False
+        x, carrier = out if emit else (out, None)
+    if relu_pending:                                     # a stack that ENDS in a ReLU behind a ResBlock (decoder stride 0), as run_block_list
+        x = torch.relu(x)
     return x
 
 
@@ -505,7 +635,7 @@ class Encoder(_ConvStack):
         assert x4.dim() == 4 and x4.shape[3] == 4 and x4.dtype == torch.float32, "encoder expects NHWC4 fp32 input"
         x4 = x4.contiguous()
         if self.training:
-            y = train_block_list(self.blocks, x4)
+            y = train_block_list(self.blocks, x4, self._train_topologies)
             return y[..., :self.embed_dim].contiguous() if y.shape[-1] != self.embed_dim else y
         if not self._fast:
             y = run_block_list(self.blocks, x4, self._generic_cache, self._precision)
@@ -546,7 +676,8 @@ class Decoder(_ConvStack):
 
     def forward_nhwc(self, q_nhwc, scale=None, shift=None):
         if self.training or not self._fast:
-            run = train_block_list if self.training else (lambda b, x: run_block_list(b, x, self._generic_cache, self._precision))
+            run = ((lambda b, x: train_block_list(b, x, self._train_topologies)) if self.training else
+                   (lambda b, x: run_block_list(b, x, self._generic_cache, self._precision)))
             y = run(self.blocks, q_nhwc.contiguous().float())
             img = y[..., :self.out_channel].permute(0, 3, 1, 2).contiguous()
             if scale is not None:
@@ -605,6 +736,22 @@ class VQVAE(nn.Module):
         if precision not in PRECISIONS:
             raise ValueError(f"precision must be one of {PRECISIONS}, not {precision!r}")
         self.enc_b._precision = self.dec._precision = precision
+        return self
+
+    @property
+    def train_topologies(self):
+        """"plain" or "all": what module.train() covers (set_train_topologies)."""
+        return self.enc_b._train_topologies
+
+    def set_train_topologies(self, which):
+        """"plain" (default): training covers the topologies made of 4x4 stride-2, transposed 4x4 stride-2 and 1x1
+        convolutions with a ReLU behind a convolution (new_model(), every n_res_block=0 stride-6 configuration); ResBlocks
+        and 3x3 convolutions raise NotImplementedError, as they always did.  "all" (opt-in; a later change makes it the
+        default): every topology the constructors build trains -- VQVAE() itself, the stride-4 and stride-2 encoders, any
+        n_res_block.  continuous_relax=True raises in both.  Eval-mode results do not depend on it.  Returns self."""
+        if which not in TRAIN_TOPOLOGIES:
+            raise ValueError(f"which must be one of {TRAIN_TOPOLOGIES}, not {which!r}")
+        self.enc_b._train_topologies = self.dec._train_topologies = which
         return self
 
     def encode(self, input, continuous_relax=False, temperature=1., hard=False, KL=False):

@@ -725,13 +725,24 @@ int cogv_conv1x1_to_rgb_f32(const float* in, const float* w, const float* bias, 
  *   x  [B][IH][IW][Cin] the layer's input, dy [B][OH][OW][Cout] the gradient of its pre-activation output, both NHWC fp32.
  *   splits: the pixel range is cut into that many pieces, each summed into a slab of its own in `workspace`, and a second
  *   launch adds the slabs in order; 0 = the plan's choice (enough to fill the chip).
+ *   relu_x (0 / 1): 1 contracts against max(x, 0) instead of x -- the weight gradient of a layer whose forward ran with
+ *   relu_in (a ResBlock's 3x3, the convolution behind the ReLU that closes a ResBlock chain); x is the saved PRE-ReLU input,
+ *   -0.0, +0.0 and negatives contribute nothing.  Valid for every kind.
+ *   topologies (0 / 1): 0 = the kinds and tiles of the n_res_block=0 stride-6 tokenizer: COGV_CONV_3X3_S1 is refused and a
+ *   tile is 128 output channels wide.  1 (opt-in; a later change makes it the default) also takes COGV_CONV_3X3_S1
+ *   (K = 9 * Cin: ResBlocks, the stride-4 / stride-2 encoders) and, where Cout <= 32, runs tiles 32 output channels wide
+ *   (a ResBlock's 3x3 has Cout = n_res_channel), the plan's Cout tiles counted in that width.  The order of the pixel sum
+ *   of an element is the same in both widths.  A zero-initialised descriptor behaves as before these fields existed.
  * COGV_ERR_ARG: null or misaligned (16 B) pointers, Cin % 4, Cout % 8, odd IH / IW for the k4 s2 convolution, a workspace
- * smaller than cogv_conv_wgrad_workspace_bytes; COGV_ERR_UNSUPPORTED: COGV_CONV_3X3_S1 (no weight gradient). */
+ * smaller than cogv_conv_wgrad_workspace_bytes, relu_x or topologies other than 0 / 1; COGV_ERR_UNSUPPORTED:
+ * COGV_CONV_3X3_S1 with topologies == 0. */
 typedef struct cogv_conv_wgrad_desc {
   int kind; int B, IH, IW, Cin, Cout;
   int splits;
   const void* x; const void* dy; void* dw;
   void* workspace; size_t workspace_bytes;
+  int relu_x;
+  int topologies;
 } cogv_conv_wgrad_desc;
 /* HOST ONLY (pointers are not looked at): plan = {splits, pixels per split, workgroups, Cout tiles, tap*Cin tiles, parities} */
 #define COGV_CONV_WGRAD_PLAN_INTS 6

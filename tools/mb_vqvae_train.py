@@ -1,4 +1,6 @@
-"""Images per second of vqvae.train_step on the production tokenizer (vqvae.new_model(), 256 x 256 images), with a yardstick
+"""Images per second of vqvae.train_step on the production tokenizer (vqvae.new_model(), 256 x 256 images) or, with
+--topology default, on VQVAE() with its own default arguments (stride 4, two ResBlocks of 32 channels per stack, 1024 codes;
+trained under set_train_topologies("all")), with a yardstick
 in the same process: the same step written with plain torch.nn modules in fp32 (F.conv2d / F.conv_transpose2d and their
 autograd, distances by one matmul, the EMA sums by index_add_ -- not the reference's one-hot product, which needs
 batch x 1024 x 8192 floats).  Both use SGD.  Per batch: a warm-up, then the two routes alternate and the median of 7 steps of
@@ -8,7 +10,7 @@ weight-gradient family's share of the 157.3 TFLOP/s fp32-MFMA peak; then the pea
 Batches: 32, and the largest power of two up to --max-batch at which train_step fits (the yardstick is left out of a batch
 it does not fit).  Progress goes to stderr, one JSON line per batch to stdout.
 
-    python tools/mb_vqvae_train.py [--batch 32] [--max-batch 256] [--reps 7] [--size 256] [--no-torch]
+    python tools/mb_vqvae_train.py [--topology production|default] [--batch 32] [--max-batch 256] [--reps 7] [--size 256] [--no-torch]
 """
 import argparse
 import json
@@ -25,16 +27,35 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 FP32_MFMA_PEAK_TFLOPS = 157.3
 
 
-class TorchVQVAE(nn.Module):
-    """The production topology in plain torch.nn, channels-first, fp32."""
+class TorchResBlock(nn.Module):
+    """vqvae/vqvae_zc.py:99-114 without the in-place ReLU: branch(relu(x)) + relu(x), which is what that block computes."""
 
-    def __init__(self, channel=512, embed_dim=256, n_embed=8192, decay=0.99, eps=1e-5):
+    def __init__(self, in_channel, channel):
+        super().__init__()
+        self.conv = nn.Sequential(nn.Conv2d(in_channel, channel, 3, padding=1), nn.ReLU(), nn.Conv2d(channel, in_channel, 1))
+
+    def forward(self, x):
+        r = F.relu(x)
+        return self.conv(r) + r
+
+
+class TorchVQVAE(nn.Module):
+    """The production topology (default arguments) or, with topology="default", VQVAE()'s own default topology, in plain
+    torch.nn, channels-first, fp32."""
+
+    def __init__(self, channel=512, embed_dim=256, n_embed=8192, decay=0.99, eps=1e-5, topology="production"):
         super().__init__()
         c = channel
-        self.enc = nn.Sequential(nn.Conv2d(3, c, 4, 2, 1), nn.ReLU(), nn.Conv2d(c, c, 4, 2, 1), nn.ReLU(), nn.Conv2d(c, c, 4, 2, 1), nn.ReLU(),
-                                 nn.Conv2d(c, embed_dim, 1))
-        self.dec = nn.Sequential(nn.ConvTranspose2d(embed_dim, c, 4, 2, 1), nn.ReLU(), nn.ConvTranspose2d(c, c, 4, 2, 1), nn.ReLU(),
-                                 nn.ConvTranspose2d(c, c, 4, 2, 1), nn.ReLU(), nn.Conv2d(c, 3, 1))
+        if topology == "production":
+            self.enc = nn.Sequential(nn.Conv2d(3, c, 4, 2, 1), nn.ReLU(), nn.Conv2d(c, c, 4, 2, 1), nn.ReLU(), nn.Conv2d(c, c, 4, 2, 1), nn.ReLU(),
+                                     nn.Conv2d(c, embed_dim, 1))
+            self.dec = nn.Sequential(nn.ConvTranspose2d(embed_dim, c, 4, 2, 1), nn.ReLU(), nn.ConvTranspose2d(c, c, 4, 2, 1), nn.ReLU(),
+                                     nn.ConvTranspose2d(c, c, 4, 2, 1), nn.ReLU(), nn.Conv2d(c, 3, 1))
+        else:
+            self.enc = nn.Sequential(nn.Conv2d(3, c // 2, 4, 2, 1), nn.ReLU(), nn.Conv2d(c // 2, c, 4, 2, 1), nn.ReLU(), nn.Conv2d(c, c, 3, padding=1),
+                                     TorchResBlock(c, 32), TorchResBlock(c, 32), nn.ReLU(), nn.Conv2d(c, embed_dim, 1))
+            self.dec = nn.Sequential(nn.ConvTranspose2d(embed_dim, c, 4, 2, 1), TorchResBlock(c, 32), TorchResBlock(c, 32), nn.ReLU(),
+                                     nn.ConvTranspose2d(c, 3, 4, 2, 1))
         self.decay, self.eps, self.n_embed = decay, eps, n_embed
         embed = torch.randn(embed_dim, n_embed)
         self.register_buffer("embed", embed)
@@ -81,7 +102,7 @@ def say(msg):
     print(msg, file=sys.stderr, flush=True)
 
 
-def measure(batch, size, reps, routes):
+def measure(batch, size, reps, routes, topology):
     from cogview_amd import ops
     img = torch.randn(batch, 3, size, size, device="cuda", generator=torch.Generator("cuda").manual_seed(batch))
     for k in list(routes):                             # warm-up: code objects, library algorithm choices, allocator
@@ -97,7 +118,7 @@ def measure(batch, size, reps, routes):
         for k, f in routes.items():
             times[k].append(timed(lambda: f(img)))
         say(f"batch {batch}: repetition {i + 1} of {reps}")
-    res = {"batch": batch}
+    res = {"batch": batch, "topology": topology}
     for k, ts in times.items():
         med = sorted(ts)[len(ts) // 2]
         res[k] = {"images_per_s_median": round(batch / med, 2), "step_ms_median": round(med * 1e3, 2),
@@ -124,6 +145,8 @@ def measure(batch, size, reps, routes):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--topology", choices=("production", "default"), default="production",
+                    help="production: vqvae.new_model(); default: VQVAE() under set_train_topologies('all')")
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--max-batch", type=int, default=256)
     ap.add_argument("--reps", type=int, default=7)
@@ -133,14 +156,18 @@ def main():
     assert torch.cuda.is_available(), "needs an MI355X: nothing here is measured on a CPU"
     from cogview_amd import vqvae
     torch.manual_seed(0)
-    model = vqvae.new_model().cuda().train()
+    if args.topology == "production":
+        model = vqvae.new_model().cuda().train()
+    else:
+        model = vqvae.set_train_topologies(vqvae.VQVAE(), "all").cuda().train()
     opt = torch.optim.SGD(model.parameters(), lr=1e-4)
     routes = {"hip": lambda img: vqvae.train_step(model, opt, img)}
     if not args.no_torch:
-        ref = TorchVQVAE().cuda().train()
+        ref = (TorchVQVAE() if args.topology == "production" else
+               TorchVQVAE(channel=128, embed_dim=64, n_embed=1024, topology="default")).cuda().train()
         ropt = torch.optim.SGD(ref.parameters(), lr=1e-4)
         routes["torch_nn_fp32"] = lambda img: torch_step(ref, ropt, img)
-    out = [measure(args.batch, args.size, args.reps, routes)]
+    out = [measure(args.batch, args.size, args.reps, routes, args.topology)]
     print(json.dumps(out[-1]), flush=True)
     fits, b = args.batch, args.batch * 2
     while b <= args.max_batch:                          # the largest power of two at which train_step fits: one step each
@@ -158,7 +185,7 @@ def main():
             torch.cuda.empty_cache()
         b *= 2
     if fits != args.batch:
-        out.append(measure(fits, args.size, args.reps, routes))
+        out.append(measure(fits, args.size, args.reps, routes, args.topology))
         print(json.dumps(out[-1]), flush=True)
     print(json.dumps({"largest_batch_tried_that_fits": fits, "max_batch": args.max_batch}))
 
